@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — headline benchmark of the MI355X Filter -> Group -> Aggregate path.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path over one batch of synthetic columns that are already resident in HBM:
 reopen (drop the groups) -> scan kernel (Filter + InitialGroup + merge) -> FinalGroup -> groups copied to the host.
@@ -9,9 +9,12 @@ Workload at N=1 (BASELINE.json metric: rows/sec filter+group-by on 100M syntheti
     config 2's query  SELECT cat, SUM(price) FROM default WHERE price > 50 GROUP BY cat   at 100 M rows, K_cat = 1000
 (13 algorithmic bytes per row: price tag 1 + payload 8 + cat code 4).
 
-Prints ONE JSON line (rank 0).  `roofline` prices the dominant kernel (scan_spec_kernel + merge_slabs_kernel for
-config 2) against the HBM peak from its HIP-event duration; `cpu_baseline` times the CPU oracle (a port of the reference's algorithm) on a
-bounded sample of the same workload on this box's host cores.
+Prints ONE JSON line (rank 0).  `roofline` prices the whole query against the HBM peak from its HIP-event duration (the
+library's own stats of the last timed step: no run of its own).  A plain run does only that: set-up, warm-up, the timed
+steps, the outputs of the last step if --dump-outputs is given, the line.  --full adds what takes work of its own:
+the self-checks (groups == K_cat, survivors == an independent Filter-only count), `cpu_baseline` (the CPU oracle, a port
+of the reference's algorithm, on a bounded sample of the same workload on the host's cores), the ingest rates
+(`h2d_inclusive`, `json_end_to_end`) and the other configurations, skews and sizes (`by_config`, `zipf`, `by_rows`).
 """
 from __future__ import annotations
 
@@ -332,11 +335,62 @@ def roofline_of(wl: dict, rows: int, st: dict, workload: str, kcat: int, opts) -
     return r
 
 
+DUMP_BYTES = 48 << 20  # --dump-outputs stays under 64 MB in all: larger results are written as a fixed, seeded sample
+
+
+def dump_outputs(path: str, res: dict, wl: dict) -> None:
+    """--dump-outputs: what the caller of the timed path received in its last step, as .npy files (float64 values, float32
+    tags).  keys.npy / aggs.npy [groups, keys] / [groups, aggregates]: each value as a number (INT converted, FLOAT as is,
+    strings as their dictionary code, which the fixed dictionary makes stable; MISSING / NULL / booleans 0), key_tags.npy /
+    agg_tags.npy: the n1k_tag of each.  Groups come in no defined order unless the plan orders them, so without an ORDER BY
+    they are sorted by key.  Filter-only plans: selected.npy, the survivors' row ordinals.  Past DUMP_BYTES an output keeps
+    the rows at sorted positions drawn from a generator seeded with SEED (*_index.npy holds them)."""
+    import numpy as np
+    from query_amd import _ffi
+    os.makedirs(path, exist_ok=True)
+
+    def values(a):
+        tag, v = a["tag"], a["v"]
+        out = np.zeros(a.shape, dtype=np.float64)
+        out = np.where(tag == _ffi.T_INT, v.view(np.int64).astype(np.float64), out)
+        out = np.where(tag == _ffi.T_FLOAT, v.view(np.float64), out)
+        out = np.where((tag == _ffi.T_STRING) | (tag == _ffi.T_ARRAY) | (tag == _ffi.T_OBJECT), v.astype(np.float64), out)
+        return out, tag.astype(np.float32)
+
+    def sample(n, row_bytes):
+        cap = DUMP_BYTES // (row_bytes + 8)
+        if n <= cap:
+            return None
+        return np.unique(np.random.default_rng(SEED).integers(0, n, cap))
+
+    out = {}
+    if wl.get("filter_only"):
+        sel = res["selected"]
+        idx = sample(len(sel), 8)
+        out["selected"] = (sel if idx is None else sel[idx]).astype(np.float64)
+        if idx is not None:
+            out["selected_index"] = idx.astype(np.float64)
+    else:
+        kv, kt = values(res["keys"])
+        av, at = values(res["aggs"])
+        if not wl.get("order") and kv.shape[1]:
+            order = np.lexsort([c for k in reversed(range(kv.shape[1])) for c in (kv[:, k], kt[:, k])])
+            kv, kt, av, at = kv[order], kt[order], av[order], at[order]
+        idx = sample(kv.shape[0], 12 * (kv.shape[1] + av.shape[1]))
+        if idx is not None:
+            kv, kt, av, at = kv[idx], kt[idx], av[idx], at[idx]
+            out["groups_index"] = idx.astype(np.float64)
+        out.update(keys=kv, key_tags=kt, aggs=av, agg_tags=at)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+
+
 def run_resident(workload: str, rows: int, kcat: int, zipf: bool, local_rank: int, steps: int, warmup: int, opts=(), cols=None,
-                 three_calls=False) -> dict:
+                 three_calls=False, check=True, dump_dir=None) -> dict:
     """`steps` timed executions of one workload over columns resident in HBM (n1k_run_device_batch: reopen + scan + FinalGroup in
-    one call through the ABI).  Checks once, outside the timed region, that the groups are all there and that the Filter's
-    survivors equal an independent Filter-only count."""
+    one call through the ABI).  With `check`, checks once, outside the timed region, that the groups are all there and that
+    the Filter's survivors equal an independent Filter-only count.  With `dump_dir`, writes the last timed step's result there
+    (dump_outputs)."""
     import torch
     import query_amd
     wl = workloads()[workload]
@@ -371,16 +425,18 @@ def run_resident(workload: str, rows: int, kcat: int, zipf: bool, local_rank: in
     elapsed = time.perf_counter() - t0
     st = op.stats()  # (reopen zeroes the stats each step: these are the last query's)
     ngroups = int(res["ngroups"])
-    if wl.get("filter_only"):
-        sel = res["selected"]
-        assert len(sel) == st["rows_selected"] and (len(sel) < 2 or bool((sel[1:] > sel[:-1]).all())), "ordinals not ascending"
+    if dump_dir:
+        dump_outputs(dump_dir, res, wl)
     # parity seams, outside the timed region: every group of the key domain is there (uniform keys at these sizes), and an
     # independent kernel family (Filter-only: mask + compaction) counts the same survivors
     checks = {}
-    if len(wl["keys"]) == 1 and not wl.get("limit") and not zipf and rows >= 1000 * kcat:
+    if check and wl.get("filter_only"):
+        sel = res["selected"]
+        assert len(sel) == st["rows_selected"] and (len(sel) < 2 or bool((sel[1:] > sel[:-1]).all())), "ordinals not ascending"
+    if check and len(wl["keys"]) == 1 and not wl.get("limit") and not zipf and rows >= 1000 * kcat:
         assert ngroups == kcat, "%s: %d groups, the key domain has %d" % (workload, ngroups, kcat)
         checks["groups == K_cat"] = True
-    if wl["cond"] and not wl.get("filter_only"):
+    if check and wl["cond"] and not wl.get("filter_only"):
         fo = query_amd.GpuFilterGroup(query_amd.plan.filter_group_plan(wl["cond"], [], [], filter_only=True), device=local_rank)
         fo.intern(synth_dictionary(kcat))
         fb = fo.make_device_batch(rows, [cols.by_path[p] for p in fo.column_paths])
@@ -523,11 +579,15 @@ def main():
     ap.add_argument("--workload", default="config2")
     ap.add_argument("--kcat", type=int, default=None, help="distinct cat values (default: 1000; 100000 for config5*, as BASELINE.json names them)")
     ap.add_argument("--zipf", type=int, default=0)
+    ap.add_argument("--full", action="store_true", help="besides the headline: the self-checks, cpu_baseline, the ingest rates "
+                    "and the other configurations, skews and sizes (--no-cpu / --no-ingest / --no-sizes leave parts out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's result to DIR/<name>.npy")
     ap.add_argument("--cpu-sample", type=int, default=20_000_000)
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the cpu_baseline sub-record")
     ap.add_argument("--three-calls", action="store_true", help="n1k_reset / n1k_push_device_batch / n1k_finish as three calls from Python")
-    ap.add_argument("--no-sizes", action="store_true", help="skip the by_rows sub-record (the same query at 10 M and 1 B rows)")
-    ap.add_argument("--no-ingest", action="store_true", help="skip the h2d_inclusive / json_end_to_end sub-records")
+    ap.add_argument("--no-sizes", action="store_true", help="--full: skip the by_config / zipf / by_rows sub-records (other "
+                    "configurations, skews, and the same query at 10 M and 1 B rows)")
+    ap.add_argument("--no-ingest", action="store_true", help="--full: skip the h2d_inclusive / json_end_to_end sub-records")
     ap.add_argument("--ingest-rows", type=int, default=40_000_000, help="rows pushed from host buffers for h2d_inclusive")
     ap.add_argument("--json-docs", type=int, default=10_000_000, help="documents pushed as raw JSON for json_end_to_end")
     ap.add_argument("--opt", action="append", default=[], help="engine option name=value")
@@ -540,6 +600,10 @@ def main():
     ap.add_argument("--force-dist", action="store_true", help="take the multi-rank code path even with one rank")
     ap.add_argument("--dry-run", action="store_true", help="N > 1 start-up only, over gloo, no GPU (launcher, rendezvous, shard bounds)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and (args.gpus > 1 or args.force_dist or args.dry_run):
+        ap.error("--dump-outputs: one GPU, single-rank path only")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:  # no launcher: be one (before anything touches torch / HIP)
         raise SystemExit(launch_ranks(args))
     if args.kcat is None:
@@ -571,7 +635,7 @@ def main():
     total_rows = args.rows
     cols = DeviceColumns(args.rows, args.kcat, bool(args.zipf), 0, total_rows, local_rank)
     r = run_resident(args.workload, args.rows, args.kcat, bool(args.zipf), local_rank, args.steps, args.warmup, opts=args.opt, cols=cols,
-                     three_calls=args.three_calls)
+                     three_calls=args.three_calls, check=args.full, dump_dir=args.dump_outputs)
     out = {
         "metric": METRIC,
         "value": r["value"],
@@ -591,6 +655,9 @@ def main():
                    "agg_mode": r["agg_mode"], "spec_kernel": r["spec_kernel"], "checks": r["checks"]},
         "roofline": r["roofline"],
     }
+    if not args.full:
+        print(json.dumps(out))
+        return
     if not args.no_cpu:
         out["cpu_baseline"] = cpu_baseline(wl, args.kcat, bool(args.zipf), total_rows,
                                            min(args.cpu_sample, args.rows))

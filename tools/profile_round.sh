@@ -11,7 +11,7 @@ mkdir -p $DST
 #  last kernel of the query before left the device as a reopen would; config 3 / 5 still start with the reopen kernel)
 declare -A FIRST=( [config2]=scan_spec_kernel [config3]=init_table_kernel [config5]=init_table_kernel [arith]=n1k_jit_wide [filter]=init_table_kernel )
 for WL in config2 config3 config5 arith filter; do
-  python3 $ROOT/bench.py --workload $WL --steps 20 --warmup 3 $([ $WL = config2 ] || echo --no-sizes) 2>/dev/null | tail -1 > $DST/${TAG}_bench_${WL}_100M.json.log
+  python3 $ROOT/bench.py --full --workload $WL --steps 20 --warmup 3 $([ $WL = config2 ] || echo --no-sizes) 2>/dev/null | tail -1 > $DST/${TAG}_bench_${WL}_100M.json.log
   bash $ROOT/tools/prof.sh ${TAG}_$WL all -- --workload $WL > /dev/null
   cp $ROOT/gpurun_out/prof_${TAG}_$WL/stats/bench_kernel_stats.csv $DST/${TAG}_bench_${WL}_100M_kernel_stats.csv
   cp $ROOT/gpurun_out/prof_${TAG}_$WL/pmc_fetch_write.json $DST/${TAG}_bench_${WL}_100M_pmc_fetch_write.json
