@@ -919,7 +919,10 @@ n1k_status n1k_set_option(n1k_handle* h, const char* name, int64_t value) {
     } else if (n == "rows_per_lane") {
         if (value != 2 && value != 4) return fail(h, N1K_INVALID, "rows_per_lane must be 2 or 4");
         h->opt_rows_per_lane = (uint32_t)value;
-    } else if (n == "lds_bytes") h->opt_lds_bytes = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 1024), 160 * 1024);
+    }
+    // (at most 64 KiB, as the run-time-built kernels take it: a HASHED table of 160 KiB plus the scan kernels' own LDS is more
+    //  than a workgroup can have, and the launch failed)
+    else if (n == "lds_bytes") h->opt_lds_bytes = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 1024), 64 * 1024);
     else if (n == "device") {
         if (h->device_ready) return fail(h, N1K_INVALID, "device must be chosen before the first push");
         h->device = (int)value;

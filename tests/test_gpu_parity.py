@@ -1026,6 +1026,7 @@ def test_per_bin_tables_over_16_byte_records(aggs, opts):
     gpu, stats = pu.run_gpu(t, None, [D("k")], aggs, batches=2, agg_mode=4, jit=2, **opts)
     pu.assert_same_groups(gpu, ora, aggs=aggs)
     assert stats["agg_mode"] == 4
+    assert stats["spec_kernel"] != 0, "the records path fell back to the exact partitioned path"
 
 
 def test_partitioned_path_is_chosen_from_the_data():
