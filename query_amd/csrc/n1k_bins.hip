@@ -279,7 +279,7 @@ __global__ __launch_bounds__(BLOCK) void agg_bins16_kernel(const Program P, cons
             t[j] = is_int ? (uint32_t)T_INT : (boxed ? (uint32_t)(r[j].v >> 40) & 0xFFu : (uint32_t)T_FLOAT);
             p[j] = boxed ? (r[j].v & 0xFFFFFFFFFFull) : r[j].v;
             hs[j] = bin_slot(key[j], S);
-            const bool is_live = (mask >> j & 1u) && r[j].k != kEmptyKey && !(A.pad1 & 1u);  // beyond the bin / padding  (pad1: timing experiments only)
+            const bool is_live = (mask >> j & 1u) && r[j].k != kEmptyKey;  // beyond the bin / padding
             live |= is_live ? 1u << j : 0u;
         }
         const uint32_t valid = live;
@@ -384,15 +384,14 @@ __global__ __launch_bounds__(BLOCK) void agg_bins16_kernel(const Program P, cons
             // end of the bin: its groups join the compact region, every slot they used is reset
             lds_barrier();  // (LDS only: the chunks in flight stay in flight)
             const uint32_t n = *(volatile lds_u32*)fillp;
-            if (tid == 0) emit_base = n && !(A.pad1 & 2u) ? atomicAdd((unsigned long long*)&A.emit[0], (unsigned long long)n) : 0ull;
+            if (tid == 0) emit_base = n ? atomicAdd((unsigned long long*)&A.emit[0], (unsigned long long)n) : 0ull;
             lds_barrier();
             if (tid == 0) lds_fill = 0;  // (every thread has read n; the next chunk is processed behind the barrier below)
             const unsigned long long q0 = emit_base;
             for (uint32_t i = tid; i < n; i += BLOCK) {
                 const uint32_t s = slot_list[i];
                 const unsigned long long q = q0 + i;
-                if (A.pad1 & 2u) {
-                } else if (q < A.emit_cap) {
+                if (q < A.emit_cap) {
                     A.emit[2 + q] = lds[s];
                     store_slot(P, lds, S, s, A.emit + 2 + A.emit_cap + q * P.glob_words);
                 } else

@@ -152,7 +152,6 @@ n1k_status distinct_regions_finish(n1k_handle* h, const AggSpec& ag, uint64_t no
         D.words = R.dst;
         D.bin_count = h->d_cursor.p;
         D.count_stride = 1;
-        D.pad1 = h->opt_spec_debug >> 8;  // (timing experiments only)
         D.bin_stride = bin_cap;
         D.nbins = (uint32_t)nbins;
         D.set_slots = set_slots;

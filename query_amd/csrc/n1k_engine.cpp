@@ -723,10 +723,8 @@ static void destroy_handle(n1k_handle* h) {
         h->jd_codes.release();
         for (auto& b : h->jd_tags) b.release();
         for (auto& b : h->jd_payload) b.release();
-        h->d_mask.release();
         h->d_tile_off.release();
         h->d_sel.release();
-        h->d_tile_cnt.release();
         h->d_out.release();
         if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
     }
@@ -738,7 +736,6 @@ n1k_status n1k_reset(n1k_handle* h) {
     if (!h) return N1K_INVALID;
     h->stop_flag.store(0);
     h->failure_global = false;
-    h->tail_in_merge = false;
     h->row_base = 0;
     h->merged_groups_bound = 0;
     h->selected.clear();
@@ -839,14 +836,10 @@ n1k_status n1k_set_option(n1k_handle* h, const char* name, int64_t value) {
     else if (n == "spec") h->opt_spec = value ? 1 : 0;
     else if (n == "wide") h->opt_wide = value ? 1 : 0;
     else if (n == "fuse_arith") h->opt_fuse_arith = value ? 1 : 0;
-    else if (n == "pinned_out") h->opt_pinned_out = value ? 1 : 0;
     else if (n == "lean_topk") h->opt_lean_topk = value ? 1 : 0;
     else if (n == "topk_sample") h->opt_topk_sample = value ? 1 : 0;
-    else if (n == "filter_stream") h->opt_filter_stream = value ? 1 : 0;
-    else if (n == "fused_tail") h->opt_fused_tail = value ? 1 : 0;
     else if (n == "distinct_fill_pct") h->opt_distinct_fill_pct = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 1), 75);
     else if (n == "dedupe_unroll") h->opt_dedupe_unroll = (uint32_t)value;
-    else if (n == "tail_in_merge") h->opt_tail_in_merge = value ? 1 : 0;
     else if (n == "agg_spec") h->opt_agg_spec = value ? 1 : 0;
     else if (n == "merge_chunks") h->opt_merge_chunks = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 0), 16);
     else if (n == "inject_failure") h->opt_inject_failure = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 0), 3);
@@ -878,8 +871,6 @@ n1k_status n1k_set_option(n1k_handle* h, const char* name, int64_t value) {
         h->opt_rec_block = value <= 0 ? 0u : (value <= 256 ? 256u : 512u);
     } else if (n == "rec_unroll") {
         h->opt_rec_unroll = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 0), 8);
-    } else if (n == "spec_debug") {
-        h->opt_spec_debug = (uint32_t)value;
     } else if (n == "distinct_region_cap") {
         h->opt_region_cap = (uint64_t)std::max<int64_t>(value, 0);
     } else if (n == "dedupe_block") {
@@ -958,10 +949,7 @@ n1k_status n1k_run_device_batch(n1k_handle* h, const n1k_batch* batch, n1k_resul
     const double t0 = trace ? now() : 0;
     n1k_status st = n1k_reset(h);
     const double t1 = trace ? now() : 0;
-    h->one_call = true;  // (the batch is the whole query: the scan's merge may run the tail, n1k_scan.cpp)
-    h->tail_in_merge = false;
     if (st == N1K_OK) st = n1k_push_device_batch(h, batch);
-    h->one_call = false;
     const double t2 = trace ? now() : 0;
     if (st == N1K_OK) {
         h->clear_on_finish = true;  // the result leaves the device; the state behind it is the next execution's reset

@@ -92,7 +92,6 @@ struct n1k_handle {
     uint32_t opt_part_block = 256; // workgroup size of the run-time-built partition kernel (256 | 512; measured 0.43 vs 0.58 ms per 100 M rows)
     uint32_t opt_part_subs = 1;    // row exchange: sub-regions per destination with their own counters (0: one dense run)
     uint32_t opt_part_per_cu = 0;  // workgroups per CU of the run-time-built partition kernel (0 = 2)
-    uint32_t opt_pinned_out = 1;   // speculative FinalGroup writes its (few) groups straight into pinned host memory
     uint32_t opt_fuse_arith = 1;   // arithmetic nodes evaluated in registers by the run-time-built scan (no derived columns)
     bool derived_ready = true;     // the derived columns of the batch being pushed are materialised (or there are none)
     uint64_t opt_wide_values = 1u << 20;  // capacity of the wide key value tables (distinct big ints / floats)
@@ -160,18 +159,6 @@ struct n1k_handle {
     // n1k_reset would, so the next execution starts with its scan — device_clean says that the device state is what a reset
     // produces (any push / merge / partition clears it), clear_on_finish asks n1k_finish for that last kernel
     bool device_clean = false, clear_on_finish = false;
-    uint32_t opt_filter_stream = 1; // Filter-only plans: the one-pass kernel (0: mask + scan + compaction, the ablation)
-    uint32_t opt_fused_tail = 1;    // 0: finalize_kernel + publish_counters_kernel as separate launches (ablation)
-    // the speculative FinalGroup of a small table: where its pieces land (n1k_finish.cpp small_tail_layout) ...
-    struct SmallTailState { bool ok = false, fused = false, clear = false; uint64_t spec_groups = 0; size_t off_aggs = 0, off_parts = 0, off_rep = 0, total = 0; };
-    SmallTailState tail_done;     // ... and, when the merge kernel's last workgroup has run it already (tail_in_merge), what it used
-    bool tail_in_merge = false;
-    bool one_call = false;        // inside n1k_run_device_batch: the batch is the whole query and its result leaves the device next
-    // 1: the merge kernel's last workgroup runs the tail (scan -> merge+tail: two launches per query).  Measured, three
-    // alternations on one box: 0.311-0.319 vs 0.305-0.309 ms per step at 100 M rows, 0.107-0.112 vs 0.103 at 10 M — the fences
-    // and the wait for the last workgroup cost what the saved launch gains: off.
-    uint32_t opt_tail_in_merge = 0;
-    DevBuf<unsigned int> d_merge_done;
     uint32_t opt_agg_spec = 1;      // agg_bins16_kernel: the plan's one aggregate fixed at compile time (0: the generic kernel, A/B)
     uint32_t opt_merge_chunks = 0;  // merge_slabs_kernel: block rows (0 = from the grid)
     bool out_count_dirty = true;  // the finalize position counter holds a previous finish's count
@@ -220,7 +207,6 @@ struct n1k_handle {
     uint64_t wregion_cap = 0;
     bool wregion_used = false;             // some batch of this query went through the regions
     uint32_t opt_dedupe_block = 1025;      // workgroup size of the de-duplication kernel, +1: probe word by word (tuning)
-    uint32_t opt_spec_debug = 0;           // timing experiments: 1 words not stored, 2 word scatter skipped, 4 no workgroup cache, 8 finish skips the sets
     uint64_t opt_region_cap = 0;           // forced capacity of a hash region (tests: overflow into the plain log), 0 = from the rows
     uint32_t opt_distinct_words = 1;      // 0: every pair takes the (key, value, class) log and the global sets
     uint32_t opt_distinct_fill_pct = 25;     // a final bin's expected words, in % of the LDS set's slots (tuning)
@@ -261,8 +247,7 @@ struct n1k_handle {
     int st_cur = 0;
 
     // filter-only path
-    DevBuf<uint64_t> d_mask, d_tile_off, d_sel;
-    DevBuf<uint32_t> d_tile_cnt;
+    DevBuf<uint64_t> d_tile_off, d_sel;
     std::vector<uint64_t> selected;
 
     // results
@@ -311,9 +296,6 @@ n1k_status ensure_table(n1k_handle* h, uint64_t incoming_rows);
 n1k_status ensure_table_groups(n1k_handle* h, uint64_t groups);
 hipEvent_t get_event(n1k_handle* h);
 n1k_status ensure_pinned_counters(n1k_handle* h);
-typedef n1k_handle::SmallTailState SmallTail;
-bool small_tail_layout(n1k_handle* h, SmallTail& t);       // n1k_finish.cpp
-n1k_status small_tail_pinned(n1k_handle* h, const SmallTail& t);
 void drain_events(n1k_handle* h);
 n1k_status validate_batch(n1k_handle* h, const n1k_batch* b);
 uint64_t batch_bytes_per_row(const n1k_handle* h);

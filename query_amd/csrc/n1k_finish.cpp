@@ -10,26 +10,26 @@ static void mark_query_end(n1k_handle* h) {
     if (h->q0_recorded && h->ev_q1 && hipEventRecord(h->ev_q1, h->stream) == hipSuccess) h->q1_recorded = true;
 }
 
-namespace n1k_eng {
+// The speculative FinalGroup of a small table (n1k_finish below): whether the plan and the handle's state allow it, and where
+// its pieces land in the pinned buffer.
+struct SmallTail { bool fused = false; uint64_t spec_groups = 0; size_t off_aggs = 0, off_parts = 0, off_rep = 0, total = 0; };
 
-// The speculative FinalGroup of a small table (n1k_finish below; with the one-call path the merge kernel's last workgroup runs
-// it, n1k_scan.cpp): whether the plan and the handle's state allow it, and where its pieces land in the pinned buffer.
-bool small_tail_layout(n1k_handle* h, SmallTail& t) {
+static bool small_tail_layout(n1k_handle* h, SmallTail& t) {
     const ParsedPlan& pl = h->plan;
     const uint32_t nk = (uint32_t)pl.keys.size(), na = (uint32_t)pl.aggs.size();
     const bool topk_forced = pl.has_order && pl.limit >= 0 && !pl.has_having && h->opt_topk_min_groups < 4096;  // tests
-    t.ok = pl.has_group && !h->has_distinct && h->table.capacity && h->table.capacity <= (1u << 20) && !topk_forced && !h->pending.count;
-    if (!t.ok) return false;
+    if (!pl.has_group || h->has_distinct || !h->table.capacity || h->table.capacity > (1u << 20) || topk_forced || h->pending.count)
+        return false;
     t.spec_groups = std::min<uint64_t>(h->table.capacity, 4096);
     t.off_aggs = t.spec_groups * nk * sizeof(OutValue);
     t.off_parts = t.off_aggs + t.spec_groups * na * sizeof(OutValue);
     t.off_rep = t.off_parts + t.spec_groups * na * sizeof(OutPartial);
     t.total = t.off_rep + t.spec_groups * 8;
-    t.fused = h->opt_pinned_out && h->opt_fused_tail && h->table.capacity <= 8192;
+    t.fused = h->table.capacity <= 8192;
     return true;
 }
 
-n1k_status small_tail_pinned(n1k_handle* h, const SmallTail& t) {
+static n1k_status small_tail_pinned(n1k_handle* h, const SmallTail& t) {
     if (h->pin_cap < t.total + kCounters * sizeof(unsigned long long)) {
         if (h->pin_out) (void)hipHostFree(h->pin_out);
         h->pin_out = nullptr;
@@ -39,8 +39,6 @@ n1k_status small_tail_pinned(n1k_handle* h, const SmallTail& t) {
     }
     return N1K_OK;
 }
-
-}  // namespace n1k_eng
 
 extern "C" {
 
@@ -76,48 +74,31 @@ n1k_status n1k_finish(n1k_handle* h, n1k_result* out) {
         }
         // (a table of millions of slots is not worth scanning twice: the sized pass alone then)
         SmallTail tl;
-        if (h->tail_in_merge ? (tl = h->tail_done, true) : small_tail_layout(h, tl)) {
+        if (small_tail_layout(h, tl)) {
             spec_groups = tl.spec_groups;
             const size_t off_aggs = tl.off_aggs, off_parts = tl.off_parts, off_rep = tl.off_rep, total = tl.total;
-            const bool fused_tail = tl.fused;
-            if (!h->tail_in_merge) {
-                HIP_TRY(h, h->d_out.ensure(total + 16));
-                n1k_status ps = small_tail_pinned(h, tl);
-                if (ps != N1K_OK) return ps;
-            }
-            if (h->tail_in_merge) {
-                // the merge kernel's last workgroup has run the tail already (n1k_scan.cpp): nothing to launch
-                h->tail_in_merge = false;
-                h->out_count_dirty = !tl.clear;
-                h->device_clean = tl.clear;
-            } else if (fused_tail) {
+            n1k_status ps = small_tail_pinned(h, tl);
+            if (ps != N1K_OK) return ps;
+            // The few groups of a speculative FinalGroup are written by the kernel straight into the pinned host buffer (posted
+            // stores over PCIe), the counters behind them: no copy engine in the query's critical path (two hipMemcpyAsync D2H
+            // cost ~ 21 us of a 0.33 ms query: 2 x 4.7 us + a 12 us gap).
+            char* d = h->pin_out;
+            if (tl.fused) {
                 // small tables: FinalGroup, the counters behind it and — for a one-call execution, when nothing else on the
                 // device needs a reset (no wide-value tables) — the state the next execution starts from, in ONE last kernel
                 const bool clear = h->clear_on_finish && !h->prog.wide_int;
-                char* d = h->pin_out;
                 HIP_TRY(h, launch_finalize_small(h->prog, h->table, (OutValue*)d, (OutValue*)(d + off_aggs), (OutPartial*)(d + off_parts),
                                                  (uint64_t*)(d + off_rep), h->d_counters.p, (unsigned long long*)(h->pin_out + total), spec_groups,
                                                  h->d_errp, clear, h->stream));
                 h->out_count_dirty = !clear;
                 h->device_clean = clear;
             } else {
-            if (h->out_count_dirty) HIP_TRY(h, hipMemsetAsync(h->d_counters.p + 2, 0, sizeof(unsigned long long), h->stream));
-            h->out_count_dirty = true;  // (reopen zeroes every counter in its one launch)
-            if (h->opt_pinned_out) {
-                // The few groups of a speculative FinalGroup are written by the kernel straight into the pinned host buffer
-                // (posted stores over PCIe) and a one-wave kernel publishes the counters behind them: no copy engine in the
-                // query's critical path (two hipMemcpyAsync D2H cost ~ 21 us of a 0.33 ms query: 2 x 4.7 us + a 12 us gap).
-                char* d = h->pin_out;
+                if (h->out_count_dirty) HIP_TRY(h, hipMemsetAsync(h->d_counters.p + 2, 0, sizeof(unsigned long long), h->stream));
+                h->out_count_dirty = true;  // (reopen zeroes every counter in its one launch)
+                // larger tables: finalize_kernel, then a one-wave kernel publishes the counters
                 HIP_TRY(h, launch_finalize(h->prog, h->table, (OutValue*)d, (OutValue*)(d + off_aggs), (OutPartial*)(d + off_parts),
                                            (uint64_t*)(d + off_rep), h->d_counters.p + 2, spec_groups, h->d_errp, h->stream));
                 HIP_TRY(h, launch_publish_counters(h->d_counters.p, (unsigned long long*)(h->pin_out + total), kCounters, h->stream));
-            } else {
-                char* d = h->d_out.p;
-                HIP_TRY(h, launch_finalize(h->prog, h->table, (OutValue*)d, (OutValue*)(d + off_aggs), (OutPartial*)(d + off_parts),
-                                           (uint64_t*)(d + off_rep), h->d_counters.p + 2, spec_groups, h->d_errp, h->stream));
-                HIP_TRY(h, hipMemcpyAsync(h->pin_out, d, total, hipMemcpyDeviceToHost, h->stream));
-                HIP_TRY(h, hipMemcpyAsync(h->pin_out + total, h->d_counters.p, sizeof counters, hipMemcpyDeviceToHost, h->stream));
-            }
             }
             mark_query_end(h);
             {
@@ -192,7 +173,6 @@ redo_sets:
                 HIP_TRY(h, launch_distinct_insert(h->prog, h->table, D, h->d_errp, h->stream));
                 h->distinct_path |= 1u;
             }
-            if (h->opt_spec_debug & 8u) continue;
             if (h->wregion_used && h->distinct_words[ag.log_index]) {
                 n1k_status st = distinct_regions_finish(h, ag, nwords, sets_exact, &sets_deferred);
                 if (st != N1K_OK) return st;

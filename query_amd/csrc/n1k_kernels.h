@@ -7,7 +7,6 @@
 namespace n1k {
 
 constexpr int kFilterStreamTile = 8192;  // rows per tile of the one-pass Filter-only kernel (4 passes of 256 threads x 8 rows)
-constexpr int kFilterTile = 4096;  // rows per tile of the Filter-only path (64 ballot words)
 
 struct OutValue {  // same 16-byte layout as n1k_value
     uint64_t tag;  // low byte = tag (little endian), rest zero
@@ -46,18 +45,8 @@ hipError_t launch_scan_group(const Program& P, const ScanArgs& A, const GlobalTa
                              uint32_t grid, uint32_t block, uint32_t rows_per_lane, bool direct, hipStream_t st);
 hipError_t launch_scan_fast(const Program& P, const FastArgs& F, const GlobalTable& G, unsigned long long* ngroups,
                             uint32_t grid, uint32_t block, uint32_t rows_per_lane, hipStream_t st);
-// (tail: the query's last kernel — launch_finalize_small's work — done by the merge's last workgroup; null: merge only)
-struct TailArgs {
-    OutValue *out_keys, *out_aggs;
-    OutPartial* out_parts;
-    uint64_t* out_rep;
-    unsigned long long *counters, *host_counters;
-    uint64_t max_out;
-    unsigned int* done;  // workgroups finished (zero before the launch; the last workgroup leaves it zero)
-    uint32_t clear, enabled;
-};
 hipError_t launch_merge_slabs(const Program& P, const FastArgs& F, const GlobalTable& G, uint32_t nblocks,
-                              unsigned long long* ngroups, hipStream_t st, uint32_t ychunks_opt = 0, const TailArgs* tail = nullptr);
+                              unsigned long long* ngroups, hipStream_t st, uint32_t ychunks_opt = 0);
 // ORDER BY ... LIMIT over the finalised groups: order images of the first sort term, radix select of the keep-th image,
 // candidate indices (image <= threshold) and compaction of their records
 // high-cardinality GROUP BY: rows -> records (key + operands), [radix passes], per-bin LDS aggregation
@@ -137,12 +126,6 @@ hipError_t launch_finalize(const Program& P, const GlobalTable& G, OutValue* out
 hipError_t launch_finalize_small(const Program& P, const GlobalTable& G, OutValue* out_keys, OutValue* out_aggs, OutPartial* out_parts,
                                  uint64_t* out_rep, unsigned long long* counters, unsigned long long* host_counters, uint64_t max_out,
                                  uint32_t* err_flags, bool clear, hipStream_t st);
-hipError_t launch_filter_mask(const Program& P, uint64_t nrows, uint64_t* mask_words, uint32_t* tile_counts,
-                              uint32_t* err_flags, uint32_t grid, hipStream_t st);
-hipError_t launch_tile_scan(const uint32_t* counts, uint64_t* offsets, uint64_t ntiles, unsigned long long* total,
-                            hipStream_t st);
-hipError_t launch_filter_compact(const uint64_t* mask_words, const uint64_t* tile_offsets, uint64_t nrows,
-                                 uint64_t row_base, uint64_t* out_rows, uint32_t grid, hipStream_t st);
 // Filter alone in one pass: predicate + ordered compaction, tile offsets by a chained scan (tile_state: ntiles + 1 words, the
 // last one the tile counter; zeroed here)
 hipError_t launch_filter_stream(const Program& P, uint64_t nrows, uint64_t row_base, uint64_t* out_rows, unsigned long long* tile_state,

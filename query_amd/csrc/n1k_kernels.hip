@@ -7,7 +7,7 @@
 //                       workgroup's table into the global table (≙ IntermediateGroup,
 //                       execution/group_intermediate.go:56-104 + CumulateIntermediate).
 //   finalize_kernel     K5: FinalGroup (execution/group_final.go:55-98 + ComputeFinal).
-//   filter_* kernels    Filter alone (execution/filter.go:49-61): ballot bit mask, scan, ordered compaction.
+//   filter_stream_kernel  Filter alone (execution/filter.go:49-61): predicate and ordered compaction in one pass.
 //
 // All of it is HBM-bound integer/byte work (no MFMA): wave64, coalesced column loads, LDS atomics,
 // scalar (wave-uniform) interpretation of the plan program.
@@ -590,11 +590,9 @@ __global__ __launch_bounds__(BLOCK) void distinct_dedupe_kernel(const Program P,
         }
         if (lo != hi) {
             // (LDS-only barriers: __syncthreads() would also drain the loads of the next bin's words just issued)
-            if (!(D.pad1 & 2u)) {
             lds_barrier();
             for (uint32_t i = tid; i < D.set_slots; i += BLOCK) *(volatile lds_u64*)lds_word(set, i) = kEmptyKey;
             lds_barrier();
-            }
             for (uint64_t base = lo; base < hi; base += (uint64_t)BLOCK * U) {
                 if (base != lo) {
 #pragma unroll
@@ -614,7 +612,7 @@ __global__ __launch_bounds__(BLOCK) void distinct_dedupe_kernel(const Program P,
                     // bin differ in their value and key bits)
                     uint32_t h = ((uint32_t)w ^ ((uint32_t)(w >> 32) * 0x9E3779B1u)) * 0x85EBCA6Bu;
                     hh[u] = (h ^ (h >> 15)) & mask;
-                    state[u] = (w == kEmptyKey || (D.pad1 & 1u)) ? 2 : 0;  // (pad1: timing experiments only)
+                    state[u] = w == kEmptyKey ? 2 : 0;
                 }
                 if (!TOGETHER) {
 #pragma unroll
@@ -1433,15 +1431,8 @@ N1K_DEV uint64_t reduce_over_y(uint64_t (*red)[64], uint64_t v) {
     return out;
 }
 
-// (defined with finalize_small_kernel below: FinalGroup of a small table by ONE workgroup of 1024 threads)
-N1K_DEV void finalize_small_body(const Program& P, const GlobalTable& G, OutValue* out_keys, OutValue* out_aggs, OutPartial* out_parts,
-                                 uint64_t* out_rep, unsigned long long* counters, unsigned long long* host_counters, uint64_t max_out,
-                                 uint32_t* err_flags, uint32_t clear, uint32_t tid);
-
-// T.enabled: the workgroup that finishes LAST goes on to run the query's tail (finalize_small_body) — the merge and FinalGroup of a
-// small table are then one launch, without the ~ 6 us between two dependent kernels.
 __global__ __launch_bounds__(1024) void merge_slabs_kernel(const Program P, const FastArgs F, const GlobalTable G,
-                                                          uint32_t nblocks_total, unsigned long long* ngroups, const TailArgs T) {
+                                                          uint32_t nblocks_total, unsigned long long* ngroups) {
     // block = 64 slots (x) x 16 chunks (y); thread (x, y) folds workgroup slabs y', y' + Y, ... (y' = its global chunk,
     // Y = 16 * gridDim.y chunks) with unconditional, unrolled loads; the 16 chunks of a block meet through an LDS tree
     // and thread y == 0 applies the result to the global row (a handful of atomics per slot and block row).
@@ -1544,24 +1535,6 @@ __global__ __launch_bounds__(1024) void merge_slabs_kernel(const Program P, cons
                 break;
             }
         }
-    }
-    if (T.enabled) {
-        // every workgroup: its atomics are out (fence), then one ticket; the last one sees everybody's (fence) and runs the tail
-        __shared__ uint32_t s_last;
-        const uint32_t lt = threadIdx.y * 64 + threadIdx.x;
-        // (one release fence per workgroup, behind the barrier that has every wave's atomics out; a fence by every thread —
-        //  4096 L2 write-backs and invalidations per CU's worth of workgroups — made the kernel 50 us longer)
-        __syncthreads();
-        if (lt == 0) {
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-            s_last = atomicAdd(T.done, 1u) == gridDim.x * gridDim.y - 1u ? 1u : 0u;
-        }
-        __syncthreads();
-        if (!s_last) return;
-        if (lt == 0) *T.done = 0;  // (the next launch counts from zero)
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        finalize_small_body(P, G, T.out_keys, T.out_aggs, T.out_parts, T.out_rep, T.counters, T.host_counters, T.max_out, F.err_flags,
-                            T.clear, lt);
     }
 }
 
@@ -1917,11 +1890,12 @@ __global__ __launch_bounds__(256) void finalize_kernel(const Program P, const Gl
 // finalize_kernel + publish_counters_kernel (+ the next init_table_kernel): three dependent launches of a few microseconds
 // each, which is what a query over 10 M cached rows is made of.
 constexpr uint32_t kFinalizeSmallMax = 8192;
-N1K_DEV void finalize_small_body(const Program& P, const GlobalTable& G, OutValue* out_keys, OutValue* out_aggs, OutPartial* out_parts,
-                                 uint64_t* out_rep, unsigned long long* counters, unsigned long long* host_counters, uint64_t max_out,
-                                 uint32_t* err_flags, uint32_t clear, uint32_t tid) {
+__global__ __launch_bounds__(1024) void finalize_small_kernel(const Program P, const GlobalTable G, OutValue* out_keys, OutValue* out_aggs,
+                                                             OutPartial* out_parts, uint64_t* out_rep, unsigned long long* counters,
+                                                             unsigned long long* host_counters, uint64_t max_out, uint32_t* err_flags,
+                                                             uint32_t clear) {
     __shared__ uint32_t wave_cnt[16];
-    const uint32_t lane = tid & 63, wave = tid >> 6;
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     unsigned long long next = 0;
     for (uint64_t s0 = 0; s0 < G.capacity; s0 += 1024) {
         const uint64_t s = s0 + tid;
@@ -1966,13 +1940,6 @@ N1K_DEV void finalize_small_body(const Program& P, const GlobalTable& G, OutValu
         host_counters[tid] = __hip_atomic_load(&counters[tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (clear) counters[tid] = 0;
     }
-}
-
-__global__ __launch_bounds__(1024) void finalize_small_kernel(const Program P, const GlobalTable G, OutValue* out_keys, OutValue* out_aggs,
-                                                             OutPartial* out_parts, uint64_t* out_rep, unsigned long long* counters,
-                                                             unsigned long long* host_counters, uint64_t max_out, uint32_t* err_flags,
-                                                             uint32_t clear) {
-    finalize_small_body(P, G, out_keys, out_aggs, out_parts, out_rep, counters, host_counters, max_out, err_flags, clear, threadIdx.x);
 }
 
 hipError_t launch_finalize_small(const Program& P, const GlobalTable& G, OutValue* out_keys, OutValue* out_aggs, OutPartial* out_parts,
@@ -2629,44 +2596,11 @@ __global__ void topk_compact_kernel(const uint32_t* cand, uint64_t ncand, uint32
     orep[j] = rep[g];
 }
 
-// ------------------------------------------------------------------ Filter alone: mask, scan, compaction
+// ------------------------------------------------------------------ Filter alone
 //
-// Filter.processItem forwards the rows whose condition is TRUE, in input order (execution/filter.go:49-61).
-// K1: every wave evaluates 64 x R consecutive rows and stores one ballot word per 64 rows (1 bit/row) plus a
-//     survivor count per tile of kFilterTile rows.  K2 (after an exclusive scan of the tile counts): LDS-staged,
-//     ordered stream compaction of the set bits into row ordinals.
-template <int R, int BLOCK>
-__global__ __launch_bounds__(BLOCK) void filter_mask_kernel(const Program P, uint64_t nrows, uint64_t* mask_words,
-                                                           uint32_t* tile_counts, uint32_t* err_flags) {
-    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    uint32_t unsupported = 0;
-    const uint64_t chunk_rows = (uint64_t)BLOCK * R;
-    const uint64_t nchunks = (nrows + chunk_rows - 1) / chunk_rows;
-    for (uint64_t chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
-        const uint64_t wave_base = chunk * chunk_rows + (uint64_t)wave * 64 * R;
-        uint64_t row[R];
-        bool valid[R], pass[R];
-#pragma unroll
-        for (int j = 0; j < R; j++) {
-            row[j] = wave_base + (uint64_t)j * 64 + lane;
-            valid[j] = row[j] < nrows;
-        }
-        eval_predicate<R>(P, row, valid, pass, unsupported);
-        uint32_t cnt = 0;
-#pragma unroll
-        for (int j = 0; j < R; j++) {
-            unsigned long long b = __ballot(pass[j]);
-            cnt += (uint32_t)__popcll(b);
-            if (lane == 0 && wave_base + (uint64_t)j * 64 < nrows) mask_words[(wave_base >> 6) + j] = b;
-        }
-        if (lane == 0 && cnt) atomicAdd(&tile_counts[wave_base / kFilterTile], cnt);  // 64*R divides kFilterTile
-    }
-    if (unsupported) atomicOr(err_flags, (uint32_t)ERR_UNSUPPORTED_VALUE);
-}
-
-// K2 in ONE pass (execution/filter.go:49-61: the rows whose condition is TRUE, in input order): predicate, survivor count and
+// ONE pass (execution/filter.go:49-61: the rows whose condition is TRUE, in input order): predicate, survivor count and
 // ordered compaction of a tile by one workgroup, the tiles' output offsets by a chained scan with decoupled look-back — no
-// mask array, no single-workgroup scan between two kernels, no host round trip before the ordinals are written.
+// mask array, no separate scan kernel, no host round trip before the ordinals are written.
 //   * tiles (8192 rows) are handed out in order by one counter: a workgroup only ever waits for tiles that were handed out
 //     before its own;
 //   * tile t publishes ONE 64-bit word: [flag:2][count:62], flag 1 = the tile's own count (aggregate), 2 = the count of
@@ -2863,68 +2797,6 @@ hipError_t launch_filter_stream(const Program& P, uint64_t nrows, uint64_t row_b
     return hipGetLastError();
 }
 
-// exclusive scan of the tile counts (single workgroup, looping) -> tile offsets + total
-__global__ __launch_bounds__(1024) void tile_scan_kernel(const uint32_t* counts, uint64_t* offsets, uint64_t ntiles,
-                                                        unsigned long long* total) {
-    __shared__ uint64_t part[1024];
-    __shared__ uint64_t carry;
-    const uint32_t tid = threadIdx.x;
-    if (tid == 0) carry = 0;
-    __syncthreads();
-    for (uint64_t base = 0; base < ntiles; base += 1024) {
-        uint64_t i = base + tid;
-        uint64_t v = i < ntiles ? counts[i] : 0;
-        part[tid] = v;
-        __syncthreads();
-        for (uint32_t off = 1; off < 1024; off <<= 1) {
-            uint64_t add = tid >= off ? part[tid - off] : 0;
-            __syncthreads();
-            part[tid] += add;
-            __syncthreads();
-        }
-        if (i < ntiles) offsets[i] = carry + part[tid] - v;
-        __syncthreads();
-        if (tid == 1023) carry += part[1023];
-        __syncthreads();
-    }
-    if (tid == 0) *total = carry;
-}
-
-// K2: one workgroup per tile of kFilterTile rows (64 mask words): word offsets through LDS, then every lane
-// writes the ordinal of its set bit at its rank -> ascending, densely packed output
-__global__ __launch_bounds__(256) void filter_compact_kernel(const uint64_t* mask_words, const uint64_t* tile_offsets,
-                                                            uint64_t nrows, uint64_t row_base, uint64_t* out_rows) {
-    __shared__ uint32_t word_off[kFilterTile / 64];
-    __shared__ uint64_t words[kFilterTile / 64];
-    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const uint64_t ntiles = (nrows + kFilterTile - 1) / kFilterTile;
-    constexpr uint32_t kWords = kFilterTile / 64;
-    for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const uint64_t first_word = tile * kWords;
-        if (tid < kWords) {
-            uint64_t w = (first_word + tid) * 64 < nrows ? mask_words[first_word + tid] : 0ull;
-            words[tid] = w;
-            // exclusive scan of the 64 popcounts inside wave 0
-            uint32_t c = (uint32_t)__popcll(w), incl = c;
-            for (int off = 1; off < 64; off <<= 1) {
-                uint32_t t = __shfl_up(incl, off, 64);
-                if ((int)lane >= off) incl += t;
-            }
-            word_off[tid] = incl - c;
-        }
-        __syncthreads();
-        const uint64_t out_base = tile_offsets[tile];
-        for (uint32_t w = wave; w < kWords; w += 256 / 64) {
-            uint64_t m = words[w];
-            if ((m >> lane) & 1ull) {
-                uint32_t rank = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-                out_rows[out_base + word_off[w] + rank] = row_base + (first_word + w) * 64 + lane;
-            }
-        }
-        __syncthreads();
-    }
-}
-
 // ------------------------------------------------------------------ synthetic columns
 
 N1K_DEV uint64_t splitmix64(uint64_t x) {
@@ -3053,15 +2925,13 @@ hipError_t launch_scan_fast(const Program& P, const FastArgs& F, const GlobalTab
 }
 
 hipError_t launch_merge_slabs(const Program& P, const FastArgs& F, const GlobalTable& G, uint32_t nblocks,
-                              unsigned long long* ngroups, hipStream_t st, uint32_t ychunks_opt, const TailArgs* tail) {
-    TailArgs T{};
-    if (tail && G.capacity <= kFinalizeSmallMax) T = *tail;
+                              unsigned long long* ngroups, hipStream_t st, uint32_t ychunks_opt) {
     uint32_t blocks = (F.lds_slots + 63) / 64;
     // 16 * ychunks parallel chunks of workgroups; enough blocks for every CU (64 blocks read 25 MB of slabs at 1.25 TB/s)
     uint32_t ychunks = nblocks >= 512 ? 4 : (nblocks >= 128 ? 2 : 1);
     while (ychunks < 16 && blocks * ychunks < 256 && nblocks >= 32 * ychunks) ychunks *= 2;
     if (ychunks_opt) ychunks = ychunks_opt;
-    hipLaunchKernelGGL(merge_slabs_kernel, dim3(blocks, ychunks), dim3(64, 16), 0, st, P, F, G, nblocks, ngroups, T);
+    hipLaunchKernelGGL(merge_slabs_kernel, dim3(blocks, ychunks), dim3(64, 16), 0, st, P, F, G, nblocks, ngroups);
     return hipGetLastError();
 }
 
@@ -3377,26 +3247,6 @@ hipError_t launch_finalize(const Program& P, const GlobalTable& G, OutValue* out
     uint32_t blocks = (uint32_t)((G.capacity + chunk - 1) / chunk);
     hipLaunchKernelGGL(finalize_kernel, dim3(blocks), dim3(256), 0, st, P, G, out_keys, out_aggs, out_parts, out_rep,
                        out_count, max_out, err_flags, chunk);
-    return hipGetLastError();
-}
-
-hipError_t launch_filter_mask(const Program& P, uint64_t nrows, uint64_t* mask_words, uint32_t* tile_counts,
-                              uint32_t* err_flags, uint32_t grid, hipStream_t st) {
-    hipLaunchKernelGGL((filter_mask_kernel<4, 256>), dim3(grid), dim3(256), 0, st, P, nrows, mask_words, tile_counts,
-                       err_flags);
-    return hipGetLastError();
-}
-
-hipError_t launch_tile_scan(const uint32_t* counts, uint64_t* offsets, uint64_t ntiles, unsigned long long* total,
-                            hipStream_t st) {
-    hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(1024), 0, st, counts, offsets, ntiles, total);
-    return hipGetLastError();
-}
-
-hipError_t launch_filter_compact(const uint64_t* mask_words, const uint64_t* tile_offsets, uint64_t nrows,
-                                 uint64_t row_base, uint64_t* out_rows, uint32_t grid, hipStream_t st) {
-    hipLaunchKernelGGL(filter_compact_kernel, dim3(grid), dim3(256), 0, st, mask_words, tile_offsets, nrows, row_base,
-                       out_rows);
     return hipGetLastError();
 }
 

@@ -279,7 +279,6 @@ n1k_status run_group_records(n1k_handle* h, const n1k_batch* b, const PartitionP
     L.region_cursor[0] = h->d_rcursor.p;
     L.region_cap = cap;
     L.rec_overflow = d_flags;
-    L.pad = h->opt_spec_debug & 3u;  // (timing experiments only)
     if (spec) HIP_TRY(h, spec->launch_records(P, F, grid, wide, L, h->stream));
     else HIP_TRY(h, jit_launch_records(jit, P, F, grid, wide, L, h->stream));
     // (2) the second partition pass: the regions' 8 sub-regions into `bps` bins of fixed capacity per region
@@ -310,7 +309,6 @@ n1k_status run_group_records(n1k_handle* h, const n1k_batch* b, const PartitionP
     }
     // (3) one workgroup per bin: InitialGroup in an LDS table, the bin's groups into the compact region
     B.lds_slots = slots;
-    B.pad1 = h->opt_spec_debug >> 8;  // (timing experiments only)
     B.lds_max_fill = std::max(1u, slots * 5 / 8);
     for (uint32_t a = 0; a < kMaxAggs; a++) B.agg_src[a] = a < P.naggs ? pp.agg_src[a] : 0xFFFFFFFFu;
     B.err_flags = h->d_errp;

@@ -358,8 +358,7 @@ n1k_status run_group_batch(n1k_handle* h, const n1k_batch* b) {
             L.log_capacity = A.log_capacity;
             L.nw_key_bits = h->nw_key_bits;
             L.nw_val_bits = h->nw_val_bits;
-            L.dcache_slots = (h->opt_spec_debug & 4u) ? 0u : dcache_slots;
-            L.pad = h->opt_spec_debug;
+            L.dcache_slots = dcache_slots;
             h->wregion_used = true;
         }
         hipEvent_t e0 = get_event(h), e1 = get_event(h);
@@ -397,36 +396,7 @@ n1k_status run_group_batch(n1k_handle* h, const n1k_batch* b) {
                 }
                 if (spec) HIP_TRY(h, spec->launch(P, F, h->table, h->d_counters.p + 1, g, fblock, wide, L, h->stream));
                 else HIP_TRY(h, jit_launch(jit, P, F, h->table, h->d_counters.p + 1, g, wide, L, ndist, h->stream));
-                if (F.slabs) {
-                    // One-call execution of a small-table plan, and this merge is the query's last device work: its last
-                    // workgroup runs the tail too (FinalGroup into pinned memory, the counters, the next execution's reopen).
-                    TailArgs T{};
-                    SmallTail tl;
-                    const bool last_work = h->one_call && h->opt_tail_in_merge && n_main == n && off + n == b->nrows && !ndist &&
-                                           !h->has_array_agg && h->push_nseg <= 1 && !h->push_nrows_dev;
-                    if (last_work && small_tail_layout(h, tl) && tl.fused && ensure_pinned_counters(h) == N1K_OK &&
-                        small_tail_pinned(h, tl) == N1K_OK) {
-                        if (!h->d_merge_done.p) {
-                            HIP_TRY(h, h->d_merge_done.ensure(4));
-                            HIP_TRY(h, hipMemsetAsync(h->d_merge_done.p, 0, 16, h->stream));
-                        }
-                        char* d = h->pin_out;
-                        tl.clear = !h->prog.wide_int;
-                        T.out_keys = (OutValue*)d;
-                        T.out_aggs = (OutValue*)(d + tl.off_aggs);
-                        T.out_parts = (OutPartial*)(d + tl.off_parts);
-                        T.out_rep = (uint64_t*)(d + tl.off_rep);
-                        T.counters = h->d_counters.p;
-                        T.host_counters = (unsigned long long*)(h->pin_out + tl.total);
-                        T.max_out = tl.spec_groups;
-                        T.done = h->d_merge_done.p;
-                        T.clear = tl.clear ? 1u : 0u;
-                        T.enabled = 1;
-                        h->tail_done = tl;
-                        h->tail_in_merge = true;
-                    }
-                    HIP_TRY(h, launch_merge_slabs(P, F, h->table, g, h->d_counters.p + 1, h->stream, h->opt_merge_chunks, T.enabled ? &T : nullptr));
-                }
+                if (F.slabs) HIP_TRY(h, launch_merge_slabs(P, F, h->table, g, h->d_counters.p + 1, h->stream, h->opt_merge_chunks));
                 F.slabs = nullptr;
                 if (n_main < n) {
                     for (uint32_t c = 0; c < F.ncols; c++) {
@@ -516,61 +486,31 @@ n1k_status run_filter_batch(n1k_handle* h, const n1k_batch* b) {
     if (b->nrows == 0) return N1K_OK;
     hipEvent_t e0 = get_event(h), e1 = get_event(h);
     unsigned long long total = 0;
-    if (h->opt_filter_stream) {
-        // ONE pass (filter_stream_kernel): predicate, ordered compaction and the tiles' offsets by a chained scan; the ordinals
-        // land in a buffer sized for every row, the host reads the count and copies that many
-        const uint64_t ntiles = (b->nrows + kFilterStreamTile - 1) / kFilterStreamTile;
-        HIP_TRY(h, h->d_tile_off.ensure(ntiles + 1));
-        HIP_TRY(h, h->d_sel.ensure(b->nrows));
-        uint32_t grid = (uint32_t)std::min<uint64_t>(ntiles, (uint64_t)h->num_cus * 4);  // (124 VGPRs: four 256-thread workgroups per CU)
-        // one comparison of a TAGGED64 column with a NUMBER constant, arrays aligned for two rows per load: the wide variant
-        bool fast = h->opt_wide && P.nlogic == 1 && P.logic[0].op == LOGIC_PUSH;
-        if (fast) {
-            const Term& t = P.terms[P.logic[0].arg];
-            fast = t.op >= TERM_NUM_LT && t.op <= TERM_NUM_EQ && !t.a.is_const && t.a.col < (uint32_t)h->plan.paths.size() &&
-                   P.cols[t.a.col].kind == COLK_TAGGED64 && (uintptr_t)P.cols[t.a.col].payload % 16 == 0 && (uintptr_t)P.cols[t.a.col].tags % 2 == 0;
-        }
-        if (fast) grid = (uint32_t)std::min<uint64_t>(ntiles, (uint64_t)h->num_cus * (h->opt_grid_blocks ? h->opt_grid_blocks : 5));  // (84 VGPRs; measured 4: 0.43, 5: 0.39, 6: 0.40, 8: 0.40 ms per 100 M rows)
-        if (e0) (void)hipEventRecord(e0, h->stream);
-        HIP_TRY(h, launch_filter_stream(P, b->nrows, h->row_base, h->d_sel.p, (unsigned long long*)h->d_tile_off.p,
-                                        (unsigned long long*)h->d_tile_off.p + ntiles, h->d_counters.p + 3, h->d_errp, grid, h->stream, fast));
-        h->stats.spec_kernel = fast ? 1u : 0u;
-        if (e1) (void)hipEventRecord(e1, h->stream);  // device time excludes the PCIe copy of the ordinals
-        HIP_TRY(h, hipMemcpyAsync(&total, h->d_counters.p + 3, sizeof total, hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        if (total) {
-            size_t old = h->selected.size();
-            h->selected.resize(old + total);
-            HIP_TRY(h, hipMemcpyAsync(h->selected.data() + old, h->d_sel.p, total * 8, hipMemcpyDeviceToHost, h->stream));
-        }
-        h->events.emplace_back(e0, e1);
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        h->stats.rows_selected += total;
-        return N1K_OK;
+    // ONE pass (filter_stream_kernel): predicate, ordered compaction and the tiles' offsets by a chained scan; the ordinals
+    // land in a buffer sized for every row, the host reads the count and copies that many
+    const uint64_t ntiles = (b->nrows + kFilterStreamTile - 1) / kFilterStreamTile;
+    HIP_TRY(h, h->d_tile_off.ensure(ntiles + 1));
+    HIP_TRY(h, h->d_sel.ensure(b->nrows));
+    uint32_t grid = (uint32_t)std::min<uint64_t>(ntiles, (uint64_t)h->num_cus * 4);  // (124 VGPRs: four 256-thread workgroups per CU)
+    // one comparison of a TAGGED64 column with a NUMBER constant, arrays aligned for two rows per load: the wide variant
+    bool fast = h->opt_wide && P.nlogic == 1 && P.logic[0].op == LOGIC_PUSH;
+    if (fast) {
+        const Term& t = P.terms[P.logic[0].arg];
+        fast = t.op >= TERM_NUM_LT && t.op <= TERM_NUM_EQ && !t.a.is_const && t.a.col < (uint32_t)h->plan.paths.size() &&
+               P.cols[t.a.col].kind == COLK_TAGGED64 && (uintptr_t)P.cols[t.a.col].payload % 16 == 0 && (uintptr_t)P.cols[t.a.col].tags % 2 == 0;
     }
-    // three kernels (ablation, option filter_stream = 0): ballot mask + per-tile counts, single-workgroup scan, compaction
-    uint64_t ntiles = (b->nrows + kFilterTile - 1) / kFilterTile;
-    HIP_TRY(h, h->d_mask.ensure(ntiles * (kFilterTile / 64)));
-    HIP_TRY(h, h->d_tile_cnt.ensure(ntiles));
-    HIP_TRY(h, h->d_tile_off.ensure(ntiles));
-    uint64_t nchunks = (b->nrows + 1023) / 1024;
-    uint32_t grid = (uint32_t)std::min<uint64_t>(nchunks, (uint64_t)h->num_cus * 8);
+    if (fast) grid = (uint32_t)std::min<uint64_t>(ntiles, (uint64_t)h->num_cus * (h->opt_grid_blocks ? h->opt_grid_blocks : 5));  // (84 VGPRs; measured 4: 0.43, 5: 0.39, 6: 0.40, 8: 0.40 ms per 100 M rows)
     if (e0) (void)hipEventRecord(e0, h->stream);
-    HIP_TRY(h, hipMemsetAsync(h->d_tile_cnt.p, 0, ntiles * sizeof(uint32_t), h->stream));
-    HIP_TRY(h, launch_filter_mask(P, b->nrows, h->d_mask.p, h->d_tile_cnt.p, h->d_errp, grid, h->stream));
-    HIP_TRY(h, launch_tile_scan(h->d_tile_cnt.p, h->d_tile_off.p, ntiles, h->d_counters.p + 3, h->stream));
+    HIP_TRY(h, launch_filter_stream(P, b->nrows, h->row_base, h->d_sel.p, (unsigned long long*)h->d_tile_off.p,
+                                    (unsigned long long*)h->d_tile_off.p + ntiles, h->d_counters.p + 3, h->d_errp, grid, h->stream, fast));
+    h->stats.spec_kernel = fast ? 1u : 0u;
+    if (e1) (void)hipEventRecord(e1, h->stream);  // device time excludes the PCIe copy of the ordinals
     HIP_TRY(h, hipMemcpyAsync(&total, h->d_counters.p + 3, sizeof total, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     if (total) {
-        HIP_TRY(h, h->d_sel.ensure(total));
-        uint32_t cgrid = (uint32_t)std::min<uint64_t>(ntiles, (uint64_t)h->num_cus * 8);
-        HIP_TRY(h, launch_filter_compact(h->d_mask.p, h->d_tile_off.p, b->nrows, h->row_base, h->d_sel.p, cgrid, h->stream));
-        if (e1) (void)hipEventRecord(e1, h->stream);  // device time excludes the PCIe copy of the ordinals
         size_t old = h->selected.size();
         h->selected.resize(old + total);
         HIP_TRY(h, hipMemcpyAsync(h->selected.data() + old, h->d_sel.p, total * 8, hipMemcpyDeviceToHost, h->stream));
-    } else if (e1) {
-        (void)hipEventRecord(e1, h->stream);
     }
     h->events.emplace_back(e0, e1);
     HIP_TRY(h, hipStreamSynchronize(h->stream));

@@ -33,12 +33,6 @@ namespace n1k {
     }
 
 // flag bits: fire-and-forget ds_or (no LDS read, so the row loop never waits on lgkmcnt)
-// Two tiles in flight for every shape (0: only for those whose tiles end in barriers — the A/B switch).  With the tiles issued
-// unconditionally and decoded when they are processed (spec_issue_tile / spec_decode_tile) the second tile really is in flight
-// while the first is processed: config 2 at 100 M rows 0.270 -> 0.258 ms (scan + merge, three alternations on one box).
-#ifndef N1K_SPEC_PIPE_ALL
-#define N1K_SPEC_PIPE_ALL 1
-#endif
 #ifndef SPEC_FLAG
 #define SPEC_FLAG(ptr, bit) lds_or_u64((ptr), (bit))
 #endif
@@ -849,7 +843,6 @@ N1K_DEV void scan_spec_body(const Program& P, const FastArgs& F, const GlobalTab
         if constexpr (kND > 0) {
 #pragma unroll
             for (int d = 0; d < kND; d++) {
-                if (L.pad & 2u) continue;  // (timing experiments only: words dropped)
                 uint32_t* const ef = F.err_flags;
                 scatter_tile<BLOCK, kNW>(w_lds[d], w_par, mw[d], mb[d], L.region_cursor[d] + (size_t)w_sub * kCursorStride,
                                          kRecSubs * kCursorStride, L.region[d] + (size_t)w_sub * L.region_cap,
@@ -862,7 +855,7 @@ N1K_DEV void scan_spec_body(const Program& P, const FastArgs& F, const GlobalTab
     if constexpr (!SEG) {
         // plain batch: tiles at base = blockIdx.x * tile, + gridDim.x * tile, ...
         const uint32_t stride = gridDim.x * tile;
-        if constexpr (kND > 0 || (N1K_SPEC_PIPE_ALL && Spec::nderived == 0)) {  // (arithmetic nodes in registers: one tile, or the registers run out)
+        if constexpr (kND > 0 || Spec::nderived == 0) {  // (arithmetic nodes in registers: one tile, or the registers run out)
             // Two tiles in flight: the columns of tile t + 1 are requested before tile t's member words go through LDS (three
             // barriers and the stores to the regions), so the loads' latency hides behind that instead of adding to it.
             uint32_t ttA[R][kFastCols], ttB[R][kFastCols];
@@ -892,7 +885,7 @@ N1K_DEV void scan_spec_body(const Program& P, const FastArgs& F, const GlobalTab
     } else {
         // segmented batch: tiles numbered segment by segment (locate)
         const uint32_t gstride = gridDim.x;
-        if constexpr (kND > 0 || (N1K_SPEC_PIPE_ALL && Spec::nderived == 0)) {  // (arithmetic nodes in registers: one tile, or the registers run out)
+        if constexpr (kND > 0 || Spec::nderived == 0) {  // (arithmetic nodes in registers: one tile, or the registers run out)
             // Two tiles in flight: the columns of tile t + 1 are requested before tile t's member words go through LDS (three
             // barriers and the stores to the regions), so the loads' latency hides behind that instead of adding to it.
             uint32_t ttA[R][kFastCols], ttB[R][kFastCols];

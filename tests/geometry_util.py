@@ -23,8 +23,6 @@ GEOMETRY = {
     "slabs": (0, 1, 2),
     "merge_chunks": (0, 1, 3, 16),
     "lds_bytes": (1024, 4096, 65536, 163840),
-    "fused_tail": (0, 1),
-    "pinned_out": (0, 1),
     "jit_min_rows": (0, 1 << 40),
     "rep_row": (0, 1),
     # records / per-bin tables (agg_mode 4)
@@ -53,8 +51,6 @@ COVERED = {
     "lean_topk": "tests/test_gpu_parity.py::test_topk_over_the_partitioned_paths_kept_region",
     "topk_sample": "tests/test_gpu_parity.py::test_topk_threshold_from_a_sample",
     "topk_min_groups": "tests/test_gpu_parity.py::test_device_topk_filter_feeds_the_exact_order",
-    "filter_stream": "tests/test_gpu_parity.py::test_filter_only_selected_rows",
-    "tail_in_merge": "tests/test_gpu_parity.py::test_run_device_batch_is_reset_push_finish",
     "agg_spec": "tests/test_gpu_parity.py::test_per_bin_tables_over_16_byte_records",
     "records": "tests/test_gpu_fullsize.py::test_full_size_config5_own_query",
     "jit": "tests/test_gpu_parity.py::test_runtime_specialised_kernels_agree_with_the_oracle",
@@ -78,7 +74,6 @@ EXEMPT = {
     "device": "picks the GPU; every test runs on device 0",
     "stream": "the caller's stream; no kernel or geometry of its own",
     "inject_failure": "fault injection of the row exchange, covered by its failure tests in test_gpu_distributed.py",
-    "spec_debug": "timing switch that drops work on purpose: its results are wrong by design",
     "partition_sticky": "reuses the previous execution's probe decision; the path it picks is the partitioned one checked here",
 }
 

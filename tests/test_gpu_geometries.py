@@ -86,6 +86,8 @@ def _scan_cases():
         shape, "-".join("%s=%s" % kv for kv in opts.items()) or "default")))
     mode = {"direct": DIRECT, "direct-small": DIRECT, "hashed": HASH}
     for s in ("direct", "hashed"):
+        # default options reach both tails of the speculative FinalGroup (n1k_finish.cpp small_tail_layout): "direct" (2048
+        # table slots) finalize_small_kernel, "hashed" (262 144 slots) finalize_kernel + publish_counters_kernel
         add(s, {}, mode[s], 1)
         for b in G["block"]:  # the interpreter at every workgroup size (tile block x rows per lane; 4 below 1024)
             add(s, {"fast": 0, "block": b}, mode[s], 0)
@@ -99,9 +101,6 @@ def _scan_cases():
             add(s, {"fast": 0, "grid_blocks": g}, mode[s], 0)
         for rep in G["rep_row"]:  # representative rows: the interpreter only (n1k_scan.cpp:29)
             add(s, {"rep_row": rep}, mode[s], 0 if rep else 1)
-        for f in G["fused_tail"]:
-            for p in G["pinned_out"]:  # fused FinalGroup: both on and a table of <= 8192 slots (n1k_finish.cpp:28)
-                add(s if s == "hashed" else "direct-small", {"fused_tail": f, "pinned_out": p}, mode[s], 1)
     for r in G["rows_per_lane"]:  # the bounded-shape kernel (spec off): tile 512 threads x rows per lane
         add("direct", {"spec": 0, "rows_per_lane": r}, DIRECT, 0)
     for sl in G["slabs"]:  # 0 off, 1 from 4096 table bytes on, 2 always (n1k_scan.cpp:272)

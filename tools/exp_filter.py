@@ -1,4 +1,4 @@
-"""Filter-only path (execution/filter.go): mask + scan + compaction kernels and the copy of the survivors' ordinals."""
+"""Filter-only path (execution/filter.go): the one-pass filter_stream_kernel and the copy of the survivors' ordinals."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
