@@ -415,7 +415,10 @@ n1k_status n1k_merge_groups(n1k_handle *h, const void *blob, size_t len);
  * n1k_rows_step / n1k_partials_step run one whole step by these rules.  Not carried (the peers are left waiting; bound
  * such a wait with the host's own watchdog): a rank without a usable device, a rank that cannot allocate even one
  * region, and the first n1k_exchange_rows of a handle whose batch does not have the plan's column count / kinds (the
- * region size is a function of the column kinds; N1K_INVALID).
+ * region size is a function of the column kinds; N1K_INVALID).  Nor is an exchange whose regions would not lie inside the
+ * communicator's own buffers: every collective is handed the extents of its buffers and refuses such a call on the host
+ * (N1K_INVALID, the message names the extents) instead of touching memory outside them — an error of the library, not of the
+ * caller; over the loopback transport the peers' collective then fails with N1K_DEVICE_ERROR, over RCCL they are left waiting.
  *
  * n1k_exchange_partials: per-GPU partial groups (≙ the Initial -> Intermediate hand-over, algebra/aggregate.go:25-40):
  *   the sender's groups are exported (n1k_export_partials_async), moved by ONE collective — all-gather when `gathered`

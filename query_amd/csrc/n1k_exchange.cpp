@@ -120,7 +120,11 @@ n1k_status n1k_partition_device_batch(n1k_handle* h, const n1k_batch* batch, uin
     uint32_t err_flags = 0;
     HIP_TRY(h, hipMemcpyAsync(&err_flags, h->d_errp, 4, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    if (err_flags & ERR_TABLE_FULL) return fail(h, N1K_REGION_FULL, "partition region capacity (%llu rows) exceeded", (unsigned long long)capacity_rows);
+    if (err_flags & ERR_TABLE_FULL) {
+        // (the flag belongs to this call alone: the caller repeats it with larger regions, on the same handle)
+        HIP_TRY(h, hipMemsetAsync(h->d_errp, 0, 4, h->stream));
+        return fail(h, N1K_REGION_FULL, "partition region capacity (%llu rows) exceeded", (unsigned long long)capacity_rows);
+    }
     if (err_flags & ERR_UNPACKABLE_KEY) return fail(h, N1K_UNSUPPORTED_DATA, "a group key value does not fit the packed key");
     if (err_flags & ERR_UNSUPPORTED_VALUE) return fail(h, N1K_UNSUPPORTED_DATA, "a value outside the device subset was met");
     h->stats.rows_in += batch->nrows;
@@ -357,7 +361,27 @@ n1k_status loop_collective(n1k_comm* c, const void* send, hipStream_t st, Copy c
     return e == hipSuccess ? N1K_OK : cfail(c, N1K_DEVICE_ERROR, "loopback: collective failed: %s", hipGetErrorString(e));
 }
 
-n1k_status all_gather_bytes(n1k_comm* c, const char* send, char* recv, size_t bytes, hipStream_t st) {
+// The buffers a collective is handed come with their extents: a call whose regions do not lie inside them is refused on the
+// host, before any peer is given a pointer into them (`what` needs `need` bytes, the buffer holds `have`).
+bool outside_extent(n1k_comm* c, const char* what, size_t need, size_t have) {
+    if (need <= have) return false;
+    (void)cfail(c, N1K_INVALID, "collective refused: the %s regions of %d ranks end at byte %zu of a buffer of %zu bytes", what, c->world, need, have);
+    return true;
+}
+
+// loopback: a rank that refused its own call still keeps both rendezvous, publishing nothing — its peers' collective fails
+// (N1K_DEVICE_ERROR) instead of waiting for it
+n1k_status loop_refused(n1k_comm* c) {
+    c->hub->ptr[c->rank] = nullptr;
+    c->hub->barrier();
+    c->hub->barrier();
+    return N1K_INVALID;
+}
+
+// all-gather of `bytes` from every rank: send_extent / recv_extent are the sizes of the buffers behind `send` / `recv`
+n1k_status all_gather_bytes(n1k_comm* c, const char* send, size_t send_extent, char* recv, size_t recv_extent, size_t bytes, hipStream_t st) {
+    if (outside_extent(c, "send", bytes, send_extent) || outside_extent(c, "receive", bytes * (size_t)c->world, recv_extent))
+        return c->hub ? loop_refused(c) : N1K_INVALID;
     if (c->hub)
         return loop_collective(c, send, st, [&]() -> hipError_t {
             for (int p = 0; p < c->world; p++) {
@@ -373,12 +397,18 @@ n1k_status all_gather_bytes(n1k_comm* c, const char* send, char* recv, size_t by
 // All-to-all of equal regions: the region at send + p * send_stride goes to rank p, rank s's region lands at
 // recv + s * recv_stride.  This rank's own region is not copied: the caller reads it where it lies (`self`).  A stride of 0
 // is how a rank whose own part failed takes part (void_regions): one region for every peer, one sink for what arrives.
+// send_extent / recv_extent: the sizes of the buffers behind `send` / `recv`.  A call whose last region ((world - 1) * stride +
+// its length; stride 0: the longest region alone) ends outside either is refused before the group is opened.
 // Once the group is open it is always closed: no early return between ncclGroupStart and ncclGroupEnd.
-n1k_status all_to_all_regions(n1k_comm* c, const char* send, size_t send_stride, char* recv, size_t recv_stride, size_t region, hipStream_t st,
-                              const char** self, const size_t* send_bytes = nullptr) {
+n1k_status all_to_all_regions(n1k_comm* c, const char* send, size_t send_extent, size_t send_stride, char* recv, size_t recv_extent, size_t recv_stride,
+                              size_t region, hipStream_t st, const char** self, const size_t* send_bytes = nullptr) {
     // send_bytes: the region for rank p is send_bytes[p] long (regions of per-destination capacities: every rank sizes the regions
     // for destination p alike, so what this rank receives from everybody is `region` = send_bytes[its own rank] long)
     *self = send + (size_t)c->rank * send_stride;
+    size_t send_end = 0;
+    for (int p = 0; p < c->world; p++) send_end = std::max(send_end, (size_t)p * send_stride + (send_bytes ? send_bytes[p] : region));
+    if (outside_extent(c, "send", send_end, send_extent) || outside_extent(c, "receive", (size_t)(c->world - 1) * recv_stride + region, recv_extent))
+        return c->hub ? loop_refused(c) : N1K_INVALID;
     if (c->hub) {
         c->hub->stride[c->rank] = send_stride;  // (published with the pointer: read by the peers behind the first rendezvous)
         return loop_collective(c, send, st, [&]() -> hipError_t {
@@ -616,18 +646,23 @@ n1k_status mark_consumed(n1k_comm* c, n1k_handle* rcv) {
 // the regions of a rank whose local part failed: headers that hold nothing but the status.  Its usual buffers when they are
 // large enough (stride = region), else ONE scratch region that goes to every peer and one that every peer's region lands in.
 n1k_status void_regions(n1k_comm* c, n1k_handle* snd, size_t region, size_t header_bytes, uint32_t nsend, uint32_t nrecv, n1k_status status,
-                        const char** send, size_t* send_stride, char** recv, size_t* recv_stride, bool recv_contiguous) {
+                        const char** send, size_t* send_extent, size_t* send_stride, char** recv, size_t* recv_extent, size_t* recv_stride,
+                        bool recv_contiguous) {
     if (c->send.n >= region * nsend && c->recv.n >= region * nrecv) {
         *send = c->send.p;
+        *send_extent = c->send.n;
         *send_stride = region;
         *recv = c->recv.p;
+        *recv_extent = c->recv.n;
         *recv_stride = region;
     } else {
         CHIP_TRY(c, c->void_send.ensure(region));
         CHIP_TRY(c, c->void_recv.ensure(recv_contiguous ? region * nrecv : region));
         *send = c->void_send.p;
+        *send_extent = c->void_send.n;
         *send_stride = 0;
         *recv = c->void_recv.p;
+        *recv_extent = c->void_recv.n;
         *recv_stride = recv_contiguous ? region : 0;
         nsend = 1;
     }
@@ -671,14 +706,14 @@ n1k_status exchange_partials_impl(n1k_comm* c, n1k_handle* sender, n1k_handle* r
     // 2. the collective, always
     const char* send = c->send.p;
     char* recv = c->recv.p;
-    size_t sstride = region, rstride = region;
+    size_t sstride = region, rstride = region, sextent = c->send.n, rextent = c->recv.n;
     if (local != N1K_OK) {
-        st = void_regions(c, sender, region, 16, nsend, P, local, &send, &sstride, &recv, &rstride, gathered != 0);
+        st = void_regions(c, sender, region, 16, nsend, P, local, &send, &sextent, &sstride, &recv, &rextent, &rstride, gathered != 0);
         if (st != N1K_OK) return local;  // (not even one region: the peers are not told — see the comment above)
     }
     const char* self = nullptr;
-    if (gathered) st = all_gather_bytes(c, send, recv, region, sender->stream);
-    else st = all_to_all_regions(c, send, sstride, recv, rstride, region, sender->stream, &self);
+    if (gathered) st = all_gather_bytes(c, send, sextent, recv, rextent, region, sender->stream);
+    else st = all_to_all_regions(c, send, sextent, sstride, recv, rextent, rstride, region, sender->stream, &self);
     if (local != N1K_OK) {
         c->failure_broadcast = st == N1K_OK;
         sender->failure_global = st == N1K_OK;
@@ -804,19 +839,21 @@ n1k_status exchange_rows_impl(n1k_comm* c, n1k_handle* sender, const n1k_batch* 
     // 2. ONE all-to-all, always: counts, verdicts and rows of every column travel in the same region
     const char* send = c->send.p;
     char* recv = c->recv.p;
-    size_t sstride = stride, rstride = region;
+    size_t sstride = stride, rstride = region, sextent = c->send.n, rextent = c->recv.n;
     if (local != N1K_OK) {
         c->sent_cap.clear();
         if (c->send.n >= stride * P && c->recv.n >= region * P) {
             for (uint32_t d = 0; d < P; d++) (void)hipMemsetAsync(c->send.p + (size_t)d * stride, 0, header, sender->stream);
             (void)launch_stamp_verdict((unsigned long long*)c->send.p, P, stride / 8, nullptr, (uint32_t)local, sender->stream);
         } else {
-            st = void_regions(c, sender, stride, header, 1, 1, local, &send, &sstride, &recv, &rstride, false);
+            // the usual buffers do not hold P regions of this step's stride (they were sized by a step of smaller capacities, or
+            // not at all): asking void_regions for all P of them takes it to its scratch regions, whatever the buffers do hold
+            st = void_regions(c, sender, stride, header, P, P, local, &send, &sextent, &sstride, &recv, &rextent, &rstride, false);
             if (st != N1K_OK) return local;  // (not even one region: the peers are not told — see the comment above)
         }
     }
     const char* self = nullptr;
-    st = all_to_all_regions(c, send, sstride, recv, rstride, region, sender->stream, &self, wire.data());
+    st = all_to_all_regions(c, send, sextent, sstride, recv, rextent, rstride, region, sender->stream, &self, wire.data());
     if (local != N1K_OK) {
         c->failure_broadcast = st == N1K_OK;
         sender->failure_global = st == N1K_OK;
@@ -1033,7 +1070,7 @@ n1k_status n1k_gather_groups_status(n1k_comm* c, n1k_handle* h, const n1k_result
             HIP_TRY(h, c->gsend.ensure(slot));
             HIP_TRY(h, c->grecv.ensure(slot * (size_t)c->world));
             HIP_TRY(h, hipMemcpyAsync(c->gsend.p, stage.data(), slot, hipMemcpyHostToDevice, h->stream));
-            st = all_gather_bytes(c, c->gsend.p, c->grecv.p, slot, h->stream);
+            st = all_gather_bytes(c, c->gsend.p, c->gsend.n, c->grecv.p, c->grecv.n, slot, h->stream);
             if (st != N1K_OK) return fail(h, st, "%s", c->last_error.c_str());
             c->ghost.resize(slot * (size_t)c->world);
             HIP_TRY(h, hipMemcpyAsync(c->ghost.data(), c->grecv.p, c->ghost.size(), hipMemcpyDeviceToHost, h->stream));
