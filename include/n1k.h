@@ -332,6 +332,27 @@ n1k_status n1k_get_stats(const n1k_handle *h, n1k_stats *out);
  */
 n1k_status n1k_jit_check(n1k_handle *h, const uint32_t *col_kinds, uint32_t ncols, char *log, size_t loglen);
 
+/* ------------------------------------------------------------------- LIKE -- */
+
+/*
+ * `a LIKE "pattern"` (expression/comp_like.go) runs on the device as one match per DISTINCT dictionary string — a
+ * table of one byte per code, one bit per pattern of the plan — and one bit test per row.  The two entry points below
+ * run the matchers on their own (tests, diagnostics); n1k_like_stats says which route built a handle's table.
+ *
+ * n1k_like_match: the host matcher, no GPU needed.  String i is bytes[offsets[i] - offsets[0], offsets[i + 1] -
+ * offsets[0]); out_bits[i] = 1 when it matches.  N1K_INVALID for a pattern that is not valid UTF-8 (n1k_create
+ * answers N1K_UNSUPPORTED for a plan that holds one).
+ */
+n1k_status n1k_like_match(const char *pattern, size_t pattern_len, uint64_t n, const uint64_t *offsets, const char *bytes,
+                          uint8_t *out_bits);
+/* The same through like_match_kernel on `device`.  *out_left_to_host counts the strings the kernel left to the host
+ * matcher: longer than 128 bytes, or not valid UTF-8.  The results are those of n1k_like_match. */
+n1k_status n1k_like_match_device(int device, const char *pattern, size_t pattern_len, uint64_t n, const uint64_t *offsets,
+                                 const char *bytes, uint8_t *out_bits, uint64_t *out_left_to_host);
+/* out[0] dictionary strings matched on the device so far, out[1] on the host, out[2] distinct patterns of the plan,
+ * out[3] the number of new dictionary entries from which the device route is taken */
+n1k_status n1k_like_stats(const n1k_handle *h, uint64_t out[4]);
+
 /* ------------------------------------------------- multi-GPU (one per rank) -- */
 
 /*

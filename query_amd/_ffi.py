@@ -82,6 +82,7 @@ SYMBOLS = [
     "n1k_comm_max_u64", "n1k_exchange_partials", "n1k_exchange_rows", "n1k_gather_groups", "n1k_gather_groups_status", "n1k_rows_step", "n1k_partials_step", "n1k_failure_is_global",
     "n1k_exchange_rows_v", "n1k_exchange_sent_rows", "n1k_comm_max_u64_v", "n1k_rows_step_v",
     "n1k_synth_documents", "n1k_abi_version", "n1k_device_count",
+    "n1k_like_match", "n1k_like_match_device", "n1k_like_stats",
 ]
 
 _lib = None
@@ -217,6 +218,14 @@ def lib():
     L.n1k_synth_documents.restype = C.c_int
     L.n1k_synth_documents.argtypes = [C.c_uint64, C.c_uint64] + [C.c_void_p] * 5 + [C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p,
                                       C.POINTER(C.c_size_t)]
+    if hasattr(L, "n1k_like_match"):  # (absent from older builds loaded through N1K_LIB for A/B measurements)
+        L.n1k_like_match.restype = C.c_int
+        L.n1k_like_match.argtypes = [C.c_char_p, C.c_size_t, C.c_uint64, C.c_void_p, C.c_char_p, C.c_void_p]
+        L.n1k_like_match_device.restype = C.c_int
+        L.n1k_like_match_device.argtypes = [C.c_int, C.c_char_p, C.c_size_t, C.c_uint64, C.c_void_p, C.c_char_p, C.c_void_p,
+                                            C.POINTER(C.c_uint64)]
+        L.n1k_like_stats.restype = C.c_int
+        L.n1k_like_stats.argtypes = [H, C.POINTER(C.c_uint64 * 4)]
     L.n1k_abi_version.restype = C.c_int
     L.n1k_device_count.restype = C.c_int
     _lib = L

@@ -213,6 +213,38 @@ bool compile_cond(n1k_handle* h, const Expr* e, PlanError& err) {
         case EK::Between:
             h->need_rank = true;
             return push_term(TERM_BETWEEN, e->ch[0].get(), e->ch[1].get(), e->ch[2].get());
+        case EK::Like: {
+            // The pattern is compiled once per plan; the reference does the same for a constant (precompileLike) and
+            // compiles anything else per row, which stays with the reference operators.
+            const Expr* pat = e->ch[1].get();
+            if (pat->kind != EK::Const || pat->ctag != T_STRING) {
+                err.unsupported = true;
+                err.msg = "LIKE with a pattern that is not a STRING constant (the reference compiles such a pattern per row)";
+                return false;
+            }
+            size_t ix = 0;
+            while (ix < h->like_patterns.size() && h->like_patterns[ix].text != pat->cstr) ix++;
+            if (ix == h->like_patterns.size()) {
+                if (ix == kLikeMaxPatterns) {
+                    err.unsupported = true;
+                    err.msg = "more than " + std::to_string(kLikeMaxPatterns) + " distinct LIKE patterns in one plan";
+                    return false;
+                }
+                LikePattern lp;
+                if (!like_compile(pat->cstr.data(), pat->cstr.size(), lp)) {
+                    err.unsupported = true;
+                    err.msg = "LIKE pattern is not valid UTF-8 (the reference's regexp.Compile fails on it)";
+                    return false;
+                }
+                h->like_patterns.push_back(std::move(lp));
+            }
+            if (!push_term(TERM_LIKE, e->ch[0].get(), nullptr, nullptr)) return false;
+            Operand& b = P.terms[P.nterms - 1].b;
+            b.is_const = 1;
+            b.ctag = T_STRING;
+            b.cpayload = ix;  // (pad stays 0: not a dictionary string, bind_columns leaves it alone)
+            return true;
+        }
         case EK::IsNull: return push_term(TERM_IS_NULL, e->ch[0].get(), nullptr, nullptr);
         case EK::IsNotNull: return push_term(TERM_IS_NOT_NULL, e->ch[0].get(), nullptr, nullptr);
         case EK::IsMissing: return push_term(TERM_IS_MISSING, e->ch[0].get(), nullptr, nullptr);
@@ -228,6 +260,7 @@ bool compile_plan(n1k_handle* h, PlanError& err) {
     memset(&P, 0, sizeof P);
     h->derived.clear();
     h->const_strings.clear();
+    h->like_patterns.clear();
     const ParsedPlan& pl = h->plan;
     if (pl.paths.size() > (size_t)kMaxCols) { err.unsupported = true; err.msg = "more than 16 leaf paths"; return false; }
     if (pl.keys.size() > (size_t)kMaxKeys) { err.unsupported = true; err.msg = "more than 4 group keys"; return false; }
@@ -344,6 +377,76 @@ n1k_status ensure_rank(n1k_handle* h) {
     // groups that hold string MIN / MAX winners carry ranks of the old order: re-stamp them (n1k_kernels.hip)
     if (rebuilt && h->has_minmax && h->layout_fixed && h->table.capacity && (h->row_base || h->merged_groups_bound))
         HIP_TRY(h, launch_restamp_ranks(h->prog, h->table, h->stream));
+    return N1K_OK;
+}
+
+// LIKE match table: like_bits[code] bit p = pattern p matches dictionary string `code`.  Same rules as the rank table
+// above, except that a grown dictionary EXTENDS it: the entries of the old codes stay as they are (equal bytes, equal
+// code), only the new codes are matched — on the host below kLikeDeviceThreshold of them, by like_match_kernel from there
+// on (the strings the kernel leaves — too long, not valid UTF-8 — go through the host matcher either way).
+n1k_status ensure_like(n1k_handle* h) {
+    Program& P = h->prog;
+    if (h->like_patterns.empty()) {
+        P.like_bits = nullptr;
+        P.like_n = 0;
+        return N1K_OK;
+    }
+    const size_t n = h->dict.size(), first = h->like_built_for;
+    if (n > first) {
+        if (n + 4 > h->d_like.n) {  // (4 spare bytes: the kernels that stage the table in LDS copy whole words)
+            // the table moves: launches in flight may still read the old allocation
+            DevBuf<uint8_t> nb;
+            HIP_TRY(h, nb.ensure(std::max(n, h->d_like.n * 2) + 4));
+            hipError_t e = hipStreamSynchronize(h->stream);
+            if (e == hipSuccess && first) e = hipMemcpy(nb.p, h->d_like.p, first, hipMemcpyDeviceToDevice);
+            if (e != hipSuccess) nb.release();
+            HIP_TRY(h, e);
+            h->d_like.release();
+            h->d_like = nb;
+        }
+        const size_t cnt = n - first;
+        std::vector<uint64_t> off(cnt + 1);
+        off[0] = 0;
+        for (size_t i = 0; i < cnt; i++) off[i + 1] = off[i] + h->dict[first + i].size();
+        std::vector<uint8_t> bytes(off[cnt] + 1);
+        for (size_t i = 0; i < cnt; i++) memcpy(bytes.data() + off[i], h->dict[first + i].data(), h->dict[first + i].size());
+        std::vector<uint8_t> bits(cnt);
+        LikeKernelArgs A{};
+        if (cnt >= kLikeDeviceThreshold && like_dev_patterns(h->like_patterns, A.pat)) {
+            HIP_TRY(h, hipStreamSynchronize(h->stream));  // (the scratch buffers may still be read by the last extension)
+            HIP_TRY(h, h->d_like_bytes.ensure(off[cnt] + 16));
+            HIP_TRY(h, h->d_like_off.ensure(cnt + 1));
+            HIP_TRY(h, h->d_like_left.ensure(cnt));
+            if (off[cnt]) HIP_TRY(h, hipMemcpy(h->d_like_bytes.p, bytes.data(), off[cnt], hipMemcpyHostToDevice));
+            HIP_TRY(h, hipMemcpy(h->d_like_off.p, off.data(), (cnt + 1) * 8, hipMemcpyHostToDevice));
+            A.bytes = h->d_like_bytes.p;
+            A.offsets = h->d_like_off.p;
+            A.n = (uint32_t)cnt;
+            A.out_bits = h->d_like.p + first;  // (entries no launch has been told about yet: like_n grows below)
+            A.out_left = h->d_like_left.p;
+            HIP_TRY(h, launch_like_match(A, h->stream));
+            std::vector<uint8_t> left(cnt);
+            HIP_TRY(h, hipMemcpyAsync(left.data(), h->d_like_left.p, cnt, hipMemcpyDeviceToHost, h->stream));
+            HIP_TRY(h, hipStreamSynchronize(h->stream));
+            size_t nleft = 0;
+            for (size_t i = 0; i < cnt; i++) nleft += left[i];
+            if (nleft) {
+                HIP_TRY(h, hipMemcpy(bits.data(), h->d_like.p + first, cnt, hipMemcpyDeviceToHost));
+                for (size_t i = 0; i < cnt; i++)
+                    if (left[i]) like_match_block_host(h->like_patterns, 1, &off[i], bytes.data() + off[i], &bits[i]);
+                HIP_TRY(h, hipMemcpy(h->d_like.p + first, bits.data(), cnt, hipMemcpyHostToDevice));
+            }
+            h->like_on_device += cnt - nleft;
+            h->like_on_host += nleft;
+        } else {
+            like_match_block_host(h->like_patterns, cnt, off.data(), bytes.data(), bits.data());
+            HIP_TRY(h, hipMemcpy(h->d_like.p + first, bits.data(), cnt, hipMemcpyHostToDevice));
+            h->like_on_host += cnt;
+        }
+        h->like_built_for = n;
+    }
+    P.like_bits = h->d_like.p;
+    P.like_n = (uint32_t)h->like_built_for;
     return N1K_OK;
 }
 
@@ -654,6 +757,10 @@ static void destroy_handle(n1k_handle* h) {
         if (h->ev_q0) (void)hipEventDestroy(h->ev_q0);
         if (h->ev_q1) (void)hipEventDestroy(h->ev_q1);
         h->d_rank.release();
+        h->d_like.release();
+        h->d_like_bytes.release();
+        h->d_like_off.release();
+        h->d_like_left.release();
         h->d_keys.release();
         h->d_acc.release();
         h->d_rep.release();
@@ -1143,6 +1250,17 @@ n1k_status n1k_jit_check(n1k_handle* h, const uint32_t* col_kinds, uint32_t ncol
     }
     if (log && loglen) snprintf(log, loglen, "%s", l.c_str());
     return ok ? N1K_OK : fail(h, N1K_DEVICE_ERROR, "run-time compilation failed: %s", l.substr(0, 300).c_str());
+    });
+}
+
+n1k_status n1k_like_stats(const n1k_handle* h, uint64_t out[4]) {
+    return guarded(h, [&]() -> n1k_status {
+    if (!h || !out) return N1K_INVALID;
+    out[0] = h->like_on_device;
+    out[1] = h->like_on_host;
+    out[2] = h->like_patterns.size();
+    out[3] = kLikeDeviceThreshold;
+    return N1K_OK;
     });
 }
 

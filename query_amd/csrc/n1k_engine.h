@@ -24,6 +24,7 @@
 #include "n1k_jit.h"
 #include "n1k_json.h"
 #include "n1k_kernels.h"
+#include "n1k_like.h"
 #include "n1k_plan.h"
 
 
@@ -182,6 +183,16 @@ struct n1k_handle {
     size_t rank_built_for = (size_t)-1;
     DevBuf<uint32_t> d_rank;
 
+    // LIKE: the plan's distinct patterns and the match table — one byte per dictionary code, bit p = pattern p matches.
+    // Built before the first launch that needs it and EXTENDED when the dictionary has grown (ensure_like); kept across
+    // n1k_reset, freed with the handle.
+    std::vector<LikePattern> like_patterns;
+    DevBuf<uint8_t> d_like;
+    size_t like_built_for = 0;                // dictionary codes the table covers
+    uint64_t like_on_device = 0, like_on_host = 0;  // strings matched by like_match_kernel / by the host matcher
+    DevBuf<uint8_t> d_like_bytes, d_like_left;      // scratch of the device route: the new entries' bytes, the kernel's flags
+    DevBuf<uint64_t> d_like_off;
+
     // compiled program (column pointers are patched per batch)
     Program prog{};
     bool layout_fixed = false;
@@ -291,6 +302,7 @@ bool to_operand(n1k_handle* h, const Expr* e, Operand& o, PlanError& err);
 bool compile_plan(n1k_handle* h, PlanError& err);
 n1k_status ensure_device(n1k_handle* h);
 n1k_status ensure_rank(n1k_handle* h);
+n1k_status ensure_like(n1k_handle* h);
 n1k_status fix_layout(n1k_handle* h, const n1k_batch* b);
 n1k_status ensure_table(n1k_handle* h, uint64_t incoming_rows);
 n1k_status ensure_table_groups(n1k_handle* h, uint64_t groups);

@@ -125,6 +125,17 @@ N1K_DEV void eval_term(const Program& P, const Term& t, const uint64_t (&row)[R]
 #pragma unroll
             for (int j = 0; j < R; j++) out[j] = truth_l(ta[j], pa[j], P.empty_str_code, P.empty_arr_code, P.empty_obj_code);
             break;
+        case TERM_LIKE: {  // Like.Apply (expression/comp_like.go:68-88) with a STRING constant pattern: MISSING, NULL for a non-string,
+                           // else the pattern's bit of the string's entry in the match table
+            const uint32_t bit = 1u << (uint32_t)t.b.cpayload;
+#pragma unroll
+            for (int j = 0; j < R; j++) {
+                const uint32_t code = (uint32_t)pa[j];
+                const bool hit = ta[j] == T_STRING && code < P.like_n && (P.like_bits[code] & bit) != 0;
+                out[j] = ta[j] == T_MISSING ? L_MISSING : (ta[j] != T_STRING ? L_NULL : (hit ? L_TRUE : L_FALSE));
+            }
+            break;
+        }
         default: {  // TERM_NUM_*: a <op> NUMBER constant; same result as LT/LE/Eq.Apply with the operands in this order
             const uint32_t ct = t.b.ctag;
             const uint64_t cp = t.b.cpayload;
@@ -977,7 +988,8 @@ __global__ __launch_bounds__(BLOCK) void scan_group_kernel(const Program P, cons
 // interpreted per row.  Each column is loaded exactly once per row.
 
 // one cheap predicate term on a register-resident column value -> "is TRUE" (the only thing Filter needs)
-N1K_DEV bool fast_term_true(const FastTerm& t, uint32_t tg, uint64_t p) {
+// (like_lds: the match table staged in LDS by the caller, or null: read it from global memory)
+N1K_DEV bool fast_term_true(const FastTerm& t, uint32_t tg, uint64_t p, const uint8_t* like_lds) {
     switch (t.op) {
         case TERM_IS_NULL: return tg == T_NULL;
         case TERM_IS_NOT_NULL: return tg > T_NULL;
@@ -986,6 +998,11 @@ N1K_DEV bool fast_term_true(const FastTerm& t, uint32_t tg, uint64_t p) {
         case TERM_IS_VALUED: return tg > T_NULL;
         case TERM_IS_NOT_VALUED: return tg <= T_NULL;
         case TERM_STR_EQ: return tg == T_STRING && p == t.cpayload;
+        case TERM_LIKE: {
+            if (tg != T_STRING || (uint32_t)p >= t.like_n) return false;
+            const uint8_t b = like_lds ? like_lds[(uint32_t)p] : t.like_bits[(uint32_t)p];
+            return (b & t.like_bit) != 0;
+        }
         default: {
             if (tg <= T_NULL) return false;  // MISSING / NULL are never TRUE
             int c;
@@ -1025,6 +1042,17 @@ __global__ __launch_bounds__(BLOCK) void scan_fast_kernel(const Program P, const
     const uint32_t S = F.lds_slots;
     const uint32_t tid = threadIdx.x;
     lds_table_init<BLOCK>(P, lds, S, tid);
+    // LIKE: a match table of at most kLikeLdsBytes entries sits behind the workgroup's table (launch_scan_fast sized it)
+    const uint8_t* like_lds = nullptr;
+#pragma unroll
+    for (int t = 0; t < kFastTerms; t++) {
+        if (t < (int)F.nterms && F.terms[t].op == TERM_LIKE && F.terms[t].like_n <= kLikeLdsBytes && !like_lds) {
+            uint32_t* words = (uint32_t*)(lds + (size_t)S * P.lds_words);
+            const uint32_t* src = (const uint32_t*)F.terms[t].like_bits;
+            for (uint32_t k = tid; k < (F.terms[t].like_n + 3u) / 4u; k += BLOCK) words[k] = src[k];
+            like_lds = (const uint8_t*)words;
+        }
+    }
     __syncthreads();
 
     uint32_t unpackable = 0;
@@ -1076,7 +1104,7 @@ __global__ __launch_bounds__(BLOCK) void scan_fast_kernel(const Program P, const
                 uint64_t vp[R];
                 pick_col<R>(F.terms[t].col, ctag, cpay, vt, vp);
 #pragma unroll
-                for (int j = 0; j < R; j++) pass[j] = pass[j] && fast_term_true(F.terms[t], vt[j], vp[j]);
+                for (int j = 0; j < R; j++) pass[j] = pass[j] && fast_term_true(F.terms[t], vt[j], vp[j], like_lds);
             }
         }
         // group key: perfect-hash slot (execution/group_util.go:18-35); the packed key is rebuilt from the slot
@@ -2916,6 +2944,11 @@ static hipError_t launch_fast_variant(const Program& P, const FastArgs& F, const
 hipError_t launch_scan_fast(const Program& P, const FastArgs& F, const GlobalTable& G, unsigned long long* ngroups,
                             uint32_t grid, uint32_t block, uint32_t rows_per_lane, hipStream_t st) {
     size_t shmem = (size_t)F.lds_slots * P.lds_words * 8;
+    for (uint32_t t = 0; t < F.nterms; t++)
+        if (F.terms[t].op == TERM_LIKE && F.terms[t].like_n <= kLikeLdsBytes) {  // room for the staged match table
+            shmem += kLikeLdsBytes;
+            break;
+        }
     if (block == 512) {
         if (rows_per_lane == 2) return launch_fast_variant<2, 512>(P, F, G, ngroups, grid, shmem, st);
         return launch_fast_variant<4, 512>(P, F, G, ngroups, grid, shmem, st);

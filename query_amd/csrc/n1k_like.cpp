@@ -1,0 +1,208 @@
+// n1k_like.cpp — LIKE: pattern compiler, the host matcher, and the two matcher entry points of the C ABI.
+#include "n1k_like.h"
+
+#include "n1k_engine.h"
+
+namespace n1k {
+
+bool like_compile(const char* pattern, size_t len, LikePattern& out) {
+    const uint8_t* s = (const uint8_t*)pattern;
+    if (len > 0x7FFFFFFFu || !like_utf8_valid(s, (uint32_t)len)) return false;
+    out.text.assign(pattern, len);
+    out.prog.clear();
+    out.anchor_end = true;
+    std::string lit;
+    bool last_many = false;
+    auto flush = [&]() {
+        for (size_t i = 0, m; i < lit.size(); i += m) {
+            m = std::min<size_t>(255, lit.size() - i);
+            // (a chunk ends on a character boundary: the matcher over code points decodes every chunk on its own)
+            while (i + m < lit.size() && ((uint8_t)lit[i + m] & 0xC0) == 0x80) m--;
+            out.prog.push_back(LIKE_OP_LIT);
+            out.prog.push_back((uint8_t)m);
+            out.prog.insert(out.prog.end(), lit.begin() + i, lit.begin() + i + m);
+        }
+        lit.clear();
+    };
+    for (size_t i = 0; i < len; i++) {
+        const char c = pattern[i];
+        out.anchor_end = true;
+        if (c == '\\' && i + 1 < len && (pattern[i + 1] == '%' || pattern[i + 1] == '_')) {
+            lit.push_back(pattern[++i]);
+            last_many = false;
+            out.anchor_end = false;  // (holds only if this was the last token: reset by whatever follows)
+        } else if (c == '%') {
+            flush();
+            if (!last_many) out.prog.push_back(LIKE_OP_MANY);  // (a MANY right behind a MANY adds nothing)
+            last_many = true;
+        } else if (c == '_') {
+            flush();
+            out.prog.push_back(LIKE_OP_ONE);
+            last_many = false;
+        } else {
+            lit.push_back(c);
+            last_many = false;
+        }
+    }
+    flush();
+    return true;
+}
+
+namespace {
+
+// Go's view of a string that is not valid UTF-8: code points, every byte that begins no valid encoding one U+FFFD
+struct LikeRunes {
+    const uint32_t* s;
+    uint32_t n;
+    uint32_t next(uint32_t p) const { return p + 1; }
+    bool newline(uint32_t p) const { return s[p] == '\n'; }
+    uint32_t lit(uint32_t p, const uint8_t* b, uint32_t len) const {
+        for (uint32_t k = 0; k < len;) {  // (the literal is valid UTF-8 and holds whole characters)
+            const uint32_t l = like_utf8_len(b[k]);
+            uint32_t cp = l == 1 ? b[k] : (l == 2 ? b[k] & 0x1Fu : (l == 3 ? b[k] & 0x0Fu : b[k] & 0x07u));
+            for (uint32_t j = 1; j < l; j++) cp = (cp << 6) | (b[k + j] & 0x3Fu);
+            if (p >= n || s[p] != cp) return 0xFFFFFFFFu;
+            p++;
+            k += l;
+        }
+        return p;
+    }
+};
+
+void decode_runes(const uint8_t* s, uint32_t n, std::vector<uint32_t>& out) {
+    out.clear();
+    for (uint32_t i = 0; i < n;) {
+        const uint32_t l = like_utf8_valid_at(s, n, i);
+        if (!l) {
+            out.push_back(0xFFFDu);
+            i++;
+            continue;
+        }
+        uint32_t cp = l == 1 ? s[i] : (l == 2 ? s[i] & 0x1Fu : (l == 3 ? s[i] & 0x0Fu : s[i] & 0x07u));
+        for (uint32_t j = 1; j < l; j++) cp = (cp << 6) | (s[i + j] & 0x3Fu);
+        out.push_back(cp);
+        i += l;
+    }
+}
+
+}  // namespace
+
+bool like_match_host(const LikePattern& p, const uint8_t* s, size_t n) {
+    if (like_utf8_valid(s, (uint32_t)n))
+        return like_match(p.prog.data(), (uint32_t)p.prog.size(), p.anchor_end, LikeBytes{s, (uint32_t)n});
+    std::vector<uint32_t> r;
+    decode_runes(s, (uint32_t)n, r);
+    return like_match(p.prog.data(), (uint32_t)p.prog.size(), p.anchor_end, LikeRunes{r.data(), (uint32_t)r.size()});
+}
+
+void like_match_block_host(const std::vector<LikePattern>& pats, uint64_t n, const uint64_t* offsets, const uint8_t* bytes, uint8_t* bits) {
+    std::vector<uint32_t> r;
+    for (uint64_t i = 0; i < n; i++) {
+        const uint8_t* s = bytes + (offsets[i] - offsets[0]);
+        const uint32_t len = (uint32_t)(offsets[i + 1] - offsets[i]);
+        uint8_t b = 0;
+        if (like_utf8_valid(s, len)) {
+            for (size_t p = 0; p < pats.size(); p++)
+                b |= (uint8_t)(like_match(pats[p].prog.data(), (uint32_t)pats[p].prog.size(), pats[p].anchor_end, LikeBytes{s, len}) ? 1u << p : 0u);
+        } else {
+            decode_runes(s, len, r);
+            for (size_t p = 0; p < pats.size(); p++)
+                b |= (uint8_t)(like_match(pats[p].prog.data(), (uint32_t)pats[p].prog.size(), pats[p].anchor_end, LikeRunes{r.data(), (uint32_t)r.size()}) ? 1u << p : 0u);
+        }
+        bits[i] = b;
+    }
+}
+
+bool like_dev_patterns(const std::vector<LikePattern>& pats, LikeDevPatterns& out) {
+    memset(&out, 0, sizeof out);
+    if (pats.size() > kLikeMaxPatterns) return false;
+    out.npat = (uint32_t)pats.size();
+    for (size_t p = 0; p < pats.size(); p++) {
+        if (pats[p].prog.size() > kLikeDevProgBytes) return false;
+        out.plen[p] = (uint8_t)pats[p].prog.size();
+        out.anchor_end[p] = pats[p].anchor_end ? 1 : 0;
+        if (!pats[p].prog.empty()) memcpy(out.prog[p], pats[p].prog.data(), pats[p].prog.size());
+    }
+    return true;
+}
+
+}  // namespace n1k
+
+using namespace n1k;
+
+static bool offsets_ok(uint64_t n, const uint64_t* offsets) {
+    for (uint64_t i = 0; i < n; i++)
+        if (offsets[i + 1] < offsets[i] || offsets[i + 1] - offsets[i] > 0x7FFFFFFFull) return false;
+    return true;
+}
+
+extern "C" {
+
+n1k_status n1k_like_match(const char* pattern, size_t pattern_len, uint64_t n, const uint64_t* offsets, const char* bytes, uint8_t* out_bits) {
+    return guarded(nullptr, [&]() -> n1k_status {
+    if ((pattern_len && !pattern) || (n && (!offsets || !out_bits)) || !offsets_ok(n, offsets)) return N1K_INVALID;
+    if (n && offsets[n] > offsets[0] && !bytes) return N1K_INVALID;
+    std::vector<LikePattern> pats(1);
+    if (!like_compile(pattern ? pattern : "", pattern_len, pats[0])) return N1K_INVALID;
+    like_match_block_host(pats, n, offsets, (const uint8_t*)bytes, out_bits);
+    return N1K_OK;
+    });
+}
+
+n1k_status n1k_like_match_device(int device, const char* pattern, size_t pattern_len, uint64_t n, const uint64_t* offsets, const char* bytes,
+                                 uint8_t* out_bits, uint64_t* out_left_to_host) {
+    return guarded(nullptr, [&]() -> n1k_status {
+    if ((pattern_len && !pattern) || (n && (!offsets || !out_bits)) || n >= 0xFFFFFFF0ull || !offsets_ok(n, offsets)) return N1K_INVALID;
+    if (n && offsets[n] > offsets[0] && !bytes) return N1K_INVALID;
+    std::vector<LikePattern> pats(1);
+    if (!like_compile(pattern ? pattern : "", pattern_len, pats[0])) return N1K_INVALID;
+    if (out_left_to_host) *out_left_to_host = 0;
+    if (n == 0) return N1K_OK;
+    LikeKernelArgs A{};
+    if (!like_dev_patterns(pats, A.pat)) {  // a program the kernel does not take: every string is the host's
+        like_match_block_host(pats, n, offsets, (const uint8_t*)bytes, out_bits);
+        if (out_left_to_host) *out_left_to_host = n;
+        return N1K_OK;
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev || hipSetDevice(device) != hipSuccess) return N1K_DEVICE_ERROR;
+    const uint64_t nbytes = offsets[n] - offsets[0];
+    DevBuf<uint8_t> d_bytes, d_bits, d_left;
+    DevBuf<uint64_t> d_off;
+    std::vector<uint8_t> left(n);
+    auto run = [&]() -> hipError_t {
+        hipError_t e;
+        if ((e = d_bytes.ensure(nbytes + 16)) != hipSuccess) return e;
+        if ((e = d_off.ensure(n + 1)) != hipSuccess) return e;
+        if ((e = d_bits.ensure(n)) != hipSuccess) return e;
+        if ((e = d_left.ensure(n)) != hipSuccess) return e;
+        if (nbytes && (e = hipMemcpy(d_bytes.p, bytes, nbytes, hipMemcpyHostToDevice)) != hipSuccess) return e;
+        if ((e = hipMemcpy(d_off.p, offsets, (n + 1) * 8, hipMemcpyHostToDevice)) != hipSuccess) return e;
+        A.bytes = d_bytes.p;
+        A.offsets = d_off.p;
+        A.n = (uint32_t)n;
+        A.out_bits = d_bits.p;
+        A.out_left = d_left.p;
+        if ((e = launch_like_match(A, nullptr)) != hipSuccess) return e;
+        if ((e = hipDeviceSynchronize()) != hipSuccess) return e;
+        if ((e = hipMemcpy(out_bits, d_bits.p, n, hipMemcpyDeviceToHost)) != hipSuccess) return e;
+        return hipMemcpy(left.data(), d_left.p, n, hipMemcpyDeviceToHost);
+    };
+    const hipError_t e = run();
+    d_bytes.release();
+    d_off.release();
+    d_bits.release();
+    d_left.release();
+    if (e != hipSuccess) return N1K_DEVICE_ERROR;
+    uint64_t nleft = 0;
+    for (uint64_t i = 0; i < n; i++)
+        if (left[i]) {
+            nleft++;
+            out_bits[i] = like_match_host(pats[0], (const uint8_t*)bytes + (offsets[i] - offsets[0]), (size_t)(offsets[i + 1] - offsets[i])) ? 1 : 0;
+        }
+    if (out_left_to_host) *out_left_to_host = nleft;
+    return N1K_OK;
+    });
+}
+
+}  // extern "C"

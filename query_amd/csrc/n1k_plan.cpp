@@ -529,6 +529,15 @@ struct EParser {
                     e->ch.push_back(std::move(hi));
                     return close(std::move(e));
                 }
+                if (t.text == "like") {  // stringer.go VisitLike: (a like b)
+                    p++;
+                    auto o = primary();
+                    if (!o) return nullptr;
+                    auto e = mk(EK::Like);
+                    e->ch.push_back(std::move(first));
+                    e->ch.push_back(std::move(o));
+                    return close(std::move(e));
+                }
                 return unsupported("operator '" + t.text + "'");
             }
             default: return unsupported("operator at offset " + std::to_string(t.begin));

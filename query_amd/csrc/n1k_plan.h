@@ -22,6 +22,7 @@ struct PlanError {
 enum class EK {
     Const, Path, Add, Sub, Mult, Div, Mod, Neg, IDiv, IMod, Eq, LT, LE, Between, And, Or, Not,
     IsNull, IsNotNull, IsMissing, IsNotMissing, IsValued, IsNotValued,
+    Like,  // (a like b), expression/comp_like.go; NOT LIKE arrives as (not (a like b))
     Func  // numeric functions of one or two arguments (expression/func_num.go): fname
 };
 

@@ -60,8 +60,45 @@ constexpr bool spec_hashed() {
     return h;
 }
 
+// LIKE terms of a Spec: the match table (one byte per dictionary code, all terms of a plan share it) is staged in LDS before
+// the tile loop when it has at most kLikeLdsBytes entries — a per-row gather then costs an LDS read instead of a dependent
+// trip to L2 — and read from global memory otherwise.
 template <class Spec>
-N1K_DEV bool spec_term_true(int t, const FastArgs& F, uint32_t tg, uint64_t p) {
+constexpr bool spec_has_like() {
+    bool h = false;
+    for (int t = 0; t < Spec::nterms; t++) h = h || Spec::terms[t].op == TERM_LIKE;
+    return h;
+}
+template <class Spec>
+constexpr int spec_like_term() {
+    for (int t = 0; t < Spec::nterms; t++)
+        if (Spec::terms[t].op == TERM_LIKE) return t;
+    return 0;
+}
+struct SpecLike {
+    const uint8_t* lds;  // the staged copy
+    bool in_lds;         // wave-uniform: read the copy (else FastTerm::like_bits)
+};
+// Every thread of the workgroup calls this ahead of a __syncthreads() that precedes the tile loop.  `words`: the
+// workgroup's kLikeLdsBytes / 4 words of LDS (one word for a Spec without LIKE).  The table's allocation carries spare
+// bytes, so whole words may be read.
+template <class Spec, int BLOCK>
+N1K_DEV SpecLike spec_stage_like(const FastArgs& F, uint32_t* words, uint32_t tid) {
+    SpecLike K{(const uint8_t*)words, false};
+    if constexpr (spec_has_like<Spec>()) {
+        constexpr int t = spec_like_term<Spec>();
+        const uint32_t n = F.terms[t].like_n;
+        if (n <= kLikeLdsBytes) {
+            const uint32_t* src = (const uint32_t*)F.terms[t].like_bits;
+            for (uint32_t k = tid; k < (n + 3u) / 4u; k += BLOCK) words[k] = src[k];
+            K.in_lds = true;
+        }
+    }
+    return K;
+}
+
+template <class Spec>
+N1K_DEV bool spec_term_true(int t, const FastArgs& F, const SpecLike& K, uint32_t tg, uint64_t p) {
     constexpr int kT = kFastTerms;
     (void)kT;
     const uint32_t op = Spec::terms[t].op;
@@ -73,6 +110,11 @@ N1K_DEV bool spec_term_true(int t, const FastArgs& F, uint32_t tg, uint64_t p) {
         case TERM_IS_VALUED: return tg > T_NULL;
         case TERM_IS_NOT_VALUED: return tg <= T_NULL;
         case TERM_STR_EQ: return tg == T_STRING && p == F.terms[t].cpayload;
+        case TERM_LIKE: {  // one bit of the match table; a code the table does not cover is not read
+            if (tg != T_STRING || (uint32_t)p >= F.terms[t].like_n) return false;
+            const uint8_t b = K.in_lds ? K.lds[(uint32_t)p] : F.terms[t].like_bits[(uint32_t)p];
+            return (b & F.terms[t].like_bit) != 0;
+        }
         default: {
             // collation of the row value against the NUMBER constant (value/integer.go:100-118, float.go:106-121)
             int c;
@@ -177,11 +219,11 @@ template <class Spec>
 N1K_DEV void spec_row(const Program& P, const FastArgs& F, const GlobalTable& G, unsigned long long* ngroups,
                       uint64_t* lds, uint32_t S, uint32_t* lds_fill, const uint32_t (&tg)[kSpecCols],
                       const uint64_t (&pv)[kSpecCols], uint32_t& selected, uint32_t& unpackable, const WordLogArgs& L,
-                      uint64_t* dcache, uint64_t (&words)[kSpecDistinct], uint32_t (&bins)[kSpecDistinct]) {
+                      uint64_t* dcache, uint64_t (&words)[kSpecDistinct], uint32_t (&bins)[kSpecDistinct], const SpecLike& K) {
     constexpr int kND = spec_ndistinct<Spec>();
     bool pass = true;
 #pragma unroll
-    for (int t = 0; t < Spec::nterms; t++) pass = pass && spec_term_true<Spec>(t, F, tg[Spec::terms[t].col], pv[Spec::terms[t].col]);
+    for (int t = 0; t < Spec::nterms; t++) pass = pass && spec_term_true<Spec>(t, F, K, tg[Spec::terms[t].col], pv[Spec::terms[t].col]);
     if (!pass) return;
     uint32_t slot = 0;
     uint64_t key = 0;
@@ -423,10 +465,10 @@ N1K_DEV uint32_t rec16_region(const Rec16& r) { return part_hash(r.k & ~kRecIntF
 
 template <class Spec>
 N1K_DEV void spec_row_record(const Program& P, const FastArgs& F, const uint32_t (&tg)[kSpecCols], const uint64_t (&pv)[kSpecCols],
-                             uint32_t& selected, uint32_t& unpackable, Rec16& rec, uint32_t& bin) {
+                             uint32_t& selected, uint32_t& unpackable, Rec16& rec, uint32_t& bin, const SpecLike& K) {
     bool pass = true;
 #pragma unroll
-    for (int t = 0; t < Spec::nterms; t++) pass = pass && spec_term_true<Spec>(t, F, tg[Spec::terms[t].col], pv[Spec::terms[t].col]);
+    for (int t = 0; t < Spec::nterms; t++) pass = pass && spec_term_true<Spec>(t, F, K, tg[Spec::terms[t].col], pv[Spec::terms[t].col]);
     if (!pass) return;
     uint64_t key = 0;
 #pragma unroll
@@ -451,6 +493,8 @@ N1K_DEV void scan_spec_records_body(const Program& P, const FastArgs& F, const W
     extern __shared__ uint64_t lds[];
     ScatterLds<Rec16, BLOCK, kNW>& S = *(ScatterLds<Rec16, BLOCK, kNW>*)lds;
     const uint32_t tid = threadIdx.x;
+    __shared__ uint32_t like_words[spec_has_like<Spec>() ? kLikeLdsBytes / 4 : 1];
+    const SpecLike K = spec_stage_like<Spec, BLOCK>(F, like_words, tid);
     scatter_init<BLOCK>(S.cnt);
     __syncthreads();
     const uint32_t sub = blockIdx.x % kRecSubs;
@@ -477,7 +521,7 @@ N1K_DEV void scan_spec_records_body(const Program& P, const FastArgs& F, const W
                 recs[at].v = 0;
                 bins[at] = kScatterNone;
                 const bool row_ok = valid[j] && (!WIDE || h == 0 || 2u * (base + (uint32_t)j * BLOCK + tid) + 1u < nrows);
-                if (row_ok) spec_row_record<Spec>(P, F, tg[j][h], pv[j][h], selected, unpackable, recs[at], bins[at]);
+                if (row_ok) spec_row_record<Spec>(P, F, tg[j][h], pv[j][h], selected, unpackable, recs[at], bins[at], K);
             }
         }
         scatter_tile<BLOCK, kNW>(S, par, recs, bins, cursor, kRecSubs * kCursorStride, dst, (uint64_t)kRecSubs * L.region_cap,
@@ -565,7 +609,9 @@ N1K_DEV void scan_spec_partition_body(const Program& P, const FastArgs& F, const
     constexpr int kNW = R * (int)kRowsPerItem;
     constexpr int TILE = BLOCK * kNW;
     __shared__ PartLds<Spec, TILE> S;
+    __shared__ uint32_t like_words[spec_has_like<Spec>() ? kLikeLdsBytes / 4 : 1];
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    const SpecLike K = spec_stage_like<Spec, BLOCK>(F, like_words, tid);
     for (uint32_t i = tid; i < 128; i += BLOCK) (&S.cnt[0][0])[i] = 0;
     if (tid < 64 && A.per_dest) {
         const uint64_t capd = A.dest_cap[tid];
@@ -611,7 +657,7 @@ N1K_DEV void scan_spec_partition_body(const Program& P, const FastArgs& F, const
                 const int at = j * (int)kRowsPerItem + h;
                 bool ok = valid[j] && (!WIDE || h == 0 || 2u * (base + (uint32_t)j * BLOCK + tid) + 1u < nrows);
 #pragma unroll
-                for (int t = 0; t < Spec::nterms; t++) ok = ok && spec_term_true<Spec>(t, F, tg[j][h][Spec::terms[t].col], pv[j][h][Spec::terms[t].col]);
+                for (int t = 0; t < Spec::nterms; t++) ok = ok && spec_term_true<Spec>(t, F, K, tg[j][h][Spec::terms[t].col], pv[j][h][Spec::terms[t].col]);
                 // the destination is a function of the key VALUES (the same function as partition_kernel's)
                 uint64_t key = 0;
 #pragma unroll
@@ -771,6 +817,8 @@ N1K_DEV void scan_spec_body(const Program& P, const FastArgs& F, const GlobalTab
         for (int d = 0; d < kND; d++) scatter_init<BLOCK>(w_lds[d].cnt);
     }
     lds_table_init<BLOCK>(P, lds, S, tid);
+    __shared__ uint32_t like_words[spec_has_like<Spec>() ? kLikeLdsBytes / 4 : 1];
+    const SpecLike K = spec_stage_like<Spec, BLOCK>(F, like_words, tid);
     if (tid == 0) lds_fill = 0;
     __syncthreads();
 
@@ -835,7 +883,7 @@ N1K_DEV void scan_spec_body(const Program& P, const FastArgs& F, const GlobalTab
 #pragma unroll
                 for (int d = 0; d < (int)kSpecDistinct; d++) { words[d] = kEmptyKey; bins[d] = kScatterNone; }
                 const bool row_ok = valid[j] && (!WIDE || h == 0 || 2u * (base + (uint32_t)j * BLOCK + tid) + 1u < nr);
-                if (row_ok) spec_row<Spec>(P, F, G, ngroups, lds, S, &lds_fill, tg[j][h], pv[j][h], selected, unpackable, L, dcache, words, bins);
+                if (row_ok) spec_row<Spec>(P, F, G, ngroups, lds, S, &lds_fill, tg[j][h], pv[j][h], selected, unpackable, L, dcache, words, bins, K);
 #pragma unroll
                 for (int d = 0; d < (int)kSpecDistinct; d++) { mw[d][j * (int)kRowsPerItem + h] = words[d]; mb[d][j * (int)kRowsPerItem + h] = bins[d]; }
             }

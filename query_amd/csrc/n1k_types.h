@@ -78,7 +78,9 @@ enum : uint32_t {
     // fast forms of LT/LE/EQ when operand b is a NUMBER constant (same semantics, fewer instructions):
     // a <op> const with op in {<, <=, >, >=, =}   ("(50 < x)" is stored as x GT 50)
     TERM_NUM_LT, TERM_NUM_LE, TERM_NUM_GT, TERM_NUM_GE, TERM_NUM_EQ,
-    TERM_STR_EQ        // a = STRING constant (dictionary code compare)
+    TERM_STR_EQ,       // a = STRING constant (dictionary code compare)
+    TERM_LIKE          // a LIKE STRING constant (expression/comp_like.go:68-88): one bit of the match table per dictionary code;
+                       // b.cpayload = the pattern's index in the plan (its bit)
 };
 
 struct Term {
@@ -189,6 +191,10 @@ struct Program {
     uint64_t* wide_flt;
     unsigned long long* wide_count;  // distinct wide values met so far
     uint32_t wide_bits, pad1;
+    // LIKE: like_bits[code] bit p = pattern p of the plan matches dictionary string `code`; codes at or beyond like_n have
+    // no entry and are not read
+    const uint8_t* like_bits;
+    uint32_t like_n, pad2;
     DevCol cols[kMaxCols];
     Term terms[kMaxTerms];
     LogicOp logic[kMaxLogic];
@@ -370,12 +376,24 @@ constexpr int kFastCols = 3, kFastTerms = 2, kFastKeys = 2, kFastAggs = 5;
 constexpr int kFastDerived = 3, kSpecCols = kFastCols + kFastDerived;
 
 struct FastTerm {
-    uint32_t op;    // TERM_NUM_* / TERM_IS_* / TERM_STR_EQ
+    uint32_t op;    // TERM_NUM_* / TERM_IS_* / TERM_STR_EQ / TERM_LIKE
     uint32_t col;   // column slot of operand a
-    uint32_t ctag;
-    uint32_t pad;
-    uint64_t cpayload;
+    union {
+        uint32_t ctag;    // the constant's tag
+        uint32_t like_n;  // TERM_LIKE: entries of the match table (Program::like_n); codes at or beyond it are not read
+    };
+    union {
+        uint32_t pad;
+        uint32_t like_bit;  // TERM_LIKE: the pattern's bit in a table entry
+    };
+    union {
+        uint64_t cpayload;         // the constant's payload
+        const uint8_t* like_bits;  // TERM_LIKE: the match table (Program::like_bits)
+    };
 };
+// A match table of at most this many bytes (= dictionary codes) is copied into LDS by the bounded and the plan-specialised
+// kernels before their tile loop; a larger one is read from global memory ("LIKE").
+constexpr uint32_t kLikeLdsBytes = 4096;
 struct FastKey {
     uint32_t col, stride, radix, shift;
 };
@@ -467,7 +485,7 @@ inline uint64_t part_region_next(uint64_t off, uint64_t cap, uint32_t width) { r
 
 // compile-time shape of a plan handled by scan_spec_kernel (see n1k_spec.h)
 struct SpecTerm {
-    uint32_t op;         // TERM_NUM_* / TERM_IS_* / TERM_STR_EQ
+    uint32_t op;         // TERM_NUM_* / TERM_IS_* / TERM_STR_EQ / TERM_LIKE
     uint32_t col;        // column slot
     uint32_t const_int;  // TERM_NUM_*: 1 = the constant is an INT, 0 = FLOAT
 };

@@ -325,6 +325,13 @@ class GpuFilterGroup:
         return {f[0]: getattr(s, f[0]) for f in _ffi.Stats._fields_}
 
     # ----------------------------------------------------------------- life cycle
+    def like_stats(self) -> dict:
+        """How the LIKE match table of this operator was built: dictionary strings matched on the device / on the host,
+        distinct patterns of the plan, and the number of new dictionary entries from which the device route is taken."""
+        out = (C.c_uint64 * 4)()
+        self._check(self._lib.n1k_like_stats(self._h, C.byref(out)))
+        return {"device_strings": int(out[0]), "host_strings": int(out[1]), "patterns": int(out[2]), "device_threshold": int(out[3])}
+
     def reopen(self):
         self._check(self._lib.n1k_reset(self._h))
 
