@@ -353,6 +353,36 @@ n1k_status n1k_like_match_device(int device, const char *pattern, size_t pattern
  * out[3] the number of new dictionary entries from which the device route is taken */
 n1k_status n1k_like_stats(const n1k_handle *h, uint64_t out[4]);
 
+/* ----------------------------------------------------------- ANY / EVERY -- */
+
+/*
+ * `ANY v IN a SATISFIES P END`, `EVERY ...`, `ANY AND EVERY ...` (expression/coll_any.go:42-85, coll_every.go:42-85,
+ * coll_any_every.go:42-85 over collEval, coll_util.go:17-120) with `a` a leaf path of the row and P a tree of AND / OR /
+ * NOT over `<e> cmp constant`, `<e> between c and c`, `<e> like "pattern"`, `<e> is [not] null | missing | valued`, <e>
+ * the variable followed by at most two field names.  Such a term is a function of the ARRAY alone, so it runs as one
+ * evaluation per DISTINCT array — one bit of the byte LIKE keeps per dictionary code, for the entries that are the
+ * canonical text of an array — and one bit test per row: MISSING for MISSING, NULL for anything but an ARRAY.  LIKE
+ * patterns and collection predicates share the eight bits of an entry.  The two entry points below run the evaluators
+ * on their own (tests, diagnostics); n1k_coll_stats says which route built a handle's table.
+ *
+ * n1k_coll_eval: the host evaluator, no GPU needed.  predicate_text is one whole term as expression/stringer.go
+ * writes it (any `v` in (`d`.`tags`) satisfies (`v` = "x") end); the binding expression is parsed and otherwise unused.
+ * Entry i is the canonical JSON text (compact, names sorted) bytes[offsets[i] - offsets[0], offsets[i + 1] - offsets[0]);
+ * out_bits[i] = 1 when the term is TRUE for that array, 0 when it is FALSE or the text is no array.  N1K_UNSUPPORTED
+ * for a term n1k_create refuses in a plan, N1K_INVALID for text that is no such term.
+ */
+n1k_status n1k_coll_eval(const char *predicate_text, size_t len, uint64_t n, const uint64_t *offsets, const char *bytes,
+                         uint8_t *out_bits);
+/* The same through coll_match_kernel on `device`.  *out_left_to_host counts the arrays the kernel left to the host
+ * evaluator: text longer than 192 bytes, a compared or matched string (or a member name) with a backslash escape, a
+ * compared number beyond the exact conversions (over 18 digits; over 15 with a fraction), a string under LIKE that is not
+ * valid UTF-8.  The results are those of n1k_coll_eval. */
+n1k_status n1k_coll_eval_device(int device, const char *predicate_text, size_t len, uint64_t n, const uint64_t *offsets,
+                                const char *bytes, uint8_t *out_bits, uint64_t *out_left_to_host);
+/* out[0] arrays of the dictionary evaluated on the device so far, out[1] on the host, out[2] distinct collection
+ * predicates of the plan, out[3] the number of new dictionary entries from which the device route is taken */
+n1k_status n1k_coll_stats(const n1k_handle *h, uint64_t out[4]);
+
 /* ------------------------------------------------- multi-GPU (one per rank) -- */
 
 /*

@@ -225,9 +225,9 @@ bool compile_cond(n1k_handle* h, const Expr* e, PlanError& err) {
             size_t ix = 0;
             while (ix < h->like_patterns.size() && h->like_patterns[ix].text != pat->cstr) ix++;
             if (ix == h->like_patterns.size()) {
-                if (ix == kLikeMaxPatterns) {
+                if (ix + h->coll_preds.size() >= kLikeMaxPatterns) {  // (the bits of a table entry: LIKE patterns from bit 0 up, collection predicates from bit 7 down)
                     err.unsupported = true;
-                    err.msg = "more than " + std::to_string(kLikeMaxPatterns) + " distinct LIKE patterns in one plan";
+                    err.msg = "more than " + std::to_string(kLikeMaxPatterns) + " distinct LIKE patterns and ANY / EVERY predicates in one plan";
                     return false;
                 }
                 LikePattern lp;
@@ -243,6 +243,29 @@ bool compile_cond(n1k_handle* h, const Expr* e, PlanError& err) {
             b.is_const = 1;
             b.ctag = T_STRING;
             b.cpayload = ix;  // (pad stays 0: not a dictionary string, bind_columns leaves it alone)
+            return true;
+        }
+        case EK::Coll: {
+            // The predicate is compiled once per plan and evaluated once per distinct array (ensure_like); the row test reads
+            // its bit.  Two terms with the same text — the binding expression included — share a bit.
+            size_t ix = 0;
+            while (ix < h->coll_preds.size() && h->coll_preds[ix].text != e->text) ix++;
+            if (ix == h->coll_preds.size()) {
+                if (ix + h->like_patterns.size() >= kLikeMaxPatterns) {
+                    err.unsupported = true;
+                    err.msg = "more than " + std::to_string(kLikeMaxPatterns) + " distinct LIKE patterns and ANY / EVERY predicates in one plan";
+                    return false;
+                }
+                CollPred cp;
+                cp.text = e->text;
+                if (!coll_compile(e, cp.prog, err)) return false;
+                h->coll_preds.push_back(std::move(cp));
+            }
+            if (!push_term(TERM_COLL, e->ch[0].get(), nullptr, nullptr)) return false;
+            Operand& b = P.terms[P.nterms - 1].b;
+            b.is_const = 1;
+            b.ctag = T_ARRAY;
+            b.cpayload = kLikeMaxPatterns - 1 - ix;  // (pad stays 0: not a dictionary string)
             return true;
         }
         case EK::IsNull: return push_term(TERM_IS_NULL, e->ch[0].get(), nullptr, nullptr);
@@ -261,6 +284,7 @@ bool compile_plan(n1k_handle* h, PlanError& err) {
     h->derived.clear();
     h->const_strings.clear();
     h->like_patterns.clear();
+    h->coll_preds.clear();
     const ParsedPlan& pl = h->plan;
     if (pl.paths.size() > (size_t)kMaxCols) { err.unsupported = true; err.msg = "more than 16 leaf paths"; return false; }
     if (pl.keys.size() > (size_t)kMaxKeys) { err.unsupported = true; err.msg = "more than 4 group keys"; return false; }
@@ -386,7 +410,7 @@ n1k_status ensure_rank(n1k_handle* h) {
 // on (the strings the kernel leaves — too long, not valid UTF-8 — go through the host matcher either way).
 n1k_status ensure_like(n1k_handle* h) {
     Program& P = h->prog;
-    if (h->like_patterns.empty()) {
+    if (h->like_patterns.empty() && h->coll_preds.empty()) {
         P.like_bits = nullptr;
         P.like_n = 0;
         return N1K_OK;
@@ -412,7 +436,9 @@ n1k_status ensure_like(n1k_handle* h) {
         for (size_t i = 0; i < cnt; i++) memcpy(bytes.data() + off[i], h->dict[first + i].data(), h->dict[first + i].size());
         std::vector<uint8_t> bits(cnt);
         LikeKernelArgs A{};
-        if (cnt >= kLikeDeviceThreshold && like_dev_patterns(h->like_patterns, A.pat)) {
+        if (h->like_patterns.empty()) {
+            // (collection predicates alone: their bits are written below)
+        } else if (cnt >= kLikeDeviceThreshold && like_dev_patterns(h->like_patterns, A.pat)) {
             HIP_TRY(h, hipStreamSynchronize(h->stream));  // (the scratch buffers may still be read by the last extension)
             HIP_TRY(h, h->d_like_bytes.ensure(off[cnt] + 16));
             HIP_TRY(h, h->d_like_off.ensure(cnt + 1));
@@ -442,6 +468,58 @@ n1k_status ensure_like(n1k_handle* h) {
             like_match_block_host(h->like_patterns, cnt, off.data(), bytes.data(), bits.data());
             HIP_TRY(h, hipMemcpy(h->d_like.p + first, bits.data(), cnt, hipMemcpyHostToDevice));
             h->like_on_host += cnt;
+        }
+        if (!h->coll_preds.empty()) {
+            // ANY / EVERY: the predicates' bits of the new entries that are array text, OR-ed into what LIKE wrote.  Same two
+            // routes: coll_match_kernel from kCollDeviceThreshold new entries on (what it leaves — too long, an escape or a
+            // number only the host takes — goes through the host evaluator), the host evaluator below.
+            const uint32_t top = kLikeMaxPatterns - 1;
+            std::vector<uint8_t> cb(cnt, 0);
+            size_t narr = 0;
+            for (size_t i = 0; i < cnt; i++) narr += !h->dict[first + i].empty() && h->dict[first + i][0] == '[';
+            if (cnt >= kCollDeviceThreshold) {
+                HIP_TRY(h, hipStreamSynchronize(h->stream));
+                HIP_TRY(h, h->d_like_bytes.ensure(off[cnt] + 16));
+                HIP_TRY(h, h->d_like_off.ensure(cnt + 1));
+                HIP_TRY(h, h->d_like_left.ensure(cnt));
+                HIP_TRY(h, h->d_coll_bits.ensure(cnt));
+                HIP_TRY(h, h->d_coll_prog.ensure(h->coll_preds.size() * sizeof(CollProg)));
+                if (off[cnt]) HIP_TRY(h, hipMemcpy(h->d_like_bytes.p, bytes.data(), off[cnt], hipMemcpyHostToDevice));
+                HIP_TRY(h, hipMemcpy(h->d_like_off.p, off.data(), (cnt + 1) * 8, hipMemcpyHostToDevice));
+                for (size_t q = 0; q < h->coll_preds.size(); q++)
+                    HIP_TRY(h, hipMemcpy(h->d_coll_prog.p + q * sizeof(CollProg), &h->coll_preds[q].prog, sizeof(CollProg), hipMemcpyHostToDevice));
+                CollKernelArgs C{};
+                C.bytes = h->d_like_bytes.p;
+                C.offsets = h->d_like_off.p;
+                C.n = (uint32_t)cnt;
+                C.nprog = (uint32_t)h->coll_preds.size();
+                C.first_bit = top;
+                C.progs = (const CollProg*)h->d_coll_prog.p;
+                C.out_bits = h->d_coll_bits.p;
+                C.out_left = h->d_like_left.p;
+                HIP_TRY(h, launch_coll_match(C, h->stream));
+                std::vector<uint8_t> left(cnt);
+                HIP_TRY(h, hipMemcpyAsync(cb.data(), h->d_coll_bits.p, cnt, hipMemcpyDeviceToHost, h->stream));
+                HIP_TRY(h, hipMemcpyAsync(left.data(), h->d_like_left.p, cnt, hipMemcpyDeviceToHost, h->stream));
+                HIP_TRY(h, hipStreamSynchronize(h->stream));
+                size_t nleft = 0;
+                for (size_t i = 0; i < cnt; i++)
+                    if (left[i]) {
+                        nleft++;
+                        cb[i] = 0;
+                        coll_eval_block_host(h->coll_preds, top, 1, &off[i], bytes.data() + off[i], &cb[i]);
+                    }
+                h->coll_on_device += narr - nleft;
+                h->coll_on_host += nleft;
+            } else {
+                coll_eval_block_host(h->coll_preds, top, cnt, off.data(), bytes.data(), cb.data());
+                h->coll_on_host += narr;
+            }
+            if (!h->like_patterns.empty()) {
+                HIP_TRY(h, hipMemcpy(bits.data(), h->d_like.p + first, cnt, hipMemcpyDeviceToHost));
+                for (size_t i = 0; i < cnt; i++) cb[i] |= bits[i];
+            }
+            HIP_TRY(h, hipMemcpy(h->d_like.p + first, cb.data(), cnt, hipMemcpyHostToDevice));
         }
         h->like_built_for = n;
     }
@@ -761,6 +839,8 @@ static void destroy_handle(n1k_handle* h) {
         h->d_like_bytes.release();
         h->d_like_off.release();
         h->d_like_left.release();
+        h->d_coll_bits.release();
+        h->d_coll_prog.release();
         h->d_keys.release();
         h->d_acc.release();
         h->d_rep.release();
@@ -1260,6 +1340,17 @@ n1k_status n1k_like_stats(const n1k_handle* h, uint64_t out[4]) {
     out[1] = h->like_on_host;
     out[2] = h->like_patterns.size();
     out[3] = kLikeDeviceThreshold;
+    return N1K_OK;
+    });
+}
+
+n1k_status n1k_coll_stats(const n1k_handle* h, uint64_t out[4]) {
+    return guarded(h, [&]() -> n1k_status {
+    if (!h || !out) return N1K_INVALID;
+    out[0] = h->coll_on_device;
+    out[1] = h->coll_on_host;
+    out[2] = h->coll_preds.size();
+    out[3] = kCollDeviceThreshold;
     return N1K_OK;
     });
 }

@@ -24,6 +24,7 @@
 #include "n1k_jit.h"
 #include "n1k_json.h"
 #include "n1k_kernels.h"
+#include "n1k_coll.h"
 #include "n1k_like.h"
 #include "n1k_plan.h"
 
@@ -192,6 +193,11 @@ struct n1k_handle {
     uint64_t like_on_device = 0, like_on_host = 0;  // strings matched by like_match_kernel / by the host matcher
     DevBuf<uint8_t> d_like_bytes, d_like_left;      // scratch of the device route: the new entries' bytes, the kernel's flags
     DevBuf<uint64_t> d_like_off;
+    // ANY / EVERY: the plan's distinct collection predicates.  Predicate q owns bit 7 - q of the same table (LIKE pattern p
+    // owns bit p; together at most 8), evaluated for the entries that are array text by the same ensure_like.
+    std::vector<CollPred> coll_preds;
+    uint64_t coll_on_device = 0, coll_on_host = 0;  // arrays evaluated by coll_match_kernel / by the host evaluator
+    DevBuf<uint8_t> d_coll_bits, d_coll_prog;       // scratch of the device route: the kernel's bits, the programs
 
     // compiled program (column pointers are patched per batch)
     Program prog{};

@@ -29,7 +29,7 @@ static n1k_status run_partition(n1k_handle* h, const n1k_batch* b, PartArgs& A) 
         size_t lds = 2048 + 2048 + 4096;  // (+ the per-destination tables of PartLds)
         for (uint32_t c = 0; c < F.ncols; c++) lds += 2048u * (F.cols[c].kind == COLK_DICT32 ? 4u : 9u);
         for (uint32_t t = 0; t < F.nterms; t++)
-            if (F.terms[t].op == TERM_LIKE) { lds += kLikeLdsBytes; break; }  // (the staged match table, present by shape)
+            if (term_is_table_bit(F.terms[t].op)) { lds += kLikeLdsBytes; break; }  // (the staged match table, present by shape)
         if (lds <= 60 * 1024) {
             SpecSig sig = make_plan_sig(h, F);
             sig.mode = 1;
@@ -58,7 +58,7 @@ static n1k_status run_partition(n1k_handle* h, const n1k_batch* b, PartArgs& A) 
         const uint64_t tiles = (n + pblock * 4 - 1) / (pblock * 4);
         uint32_t part_per_cu = h->opt_part_per_cu ? h->opt_part_per_cu : (pblock == 256 ? 6u : 2u);
         for (uint32_t t = 0; t < F.nterms && !h->opt_part_per_cu; t++)
-            if (F.terms[t].op == TERM_LIKE) {  // with the staged match table beside a tile's staging: as many workgroups as still fit a CU
+            if (term_is_table_bit(F.terms[t].op)) {  // with the staged match table beside a tile's staging: as many workgroups as still fit a CU
                 size_t wg = 2048 + 2048 + 4096 + kLikeLdsBytes;
                 for (uint32_t c = 0; c < F.ncols; c++) wg += (size_t)pblock * 4u * (F.cols[c].kind == COLK_DICT32 ? 4u : 9u);
                 part_per_cu = std::max<uint32_t>(1u, std::min<uint32_t>(part_per_cu, (uint32_t)(160u * 1024u / wg)));

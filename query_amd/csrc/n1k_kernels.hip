@@ -125,14 +125,17 @@ N1K_DEV void eval_term(const Program& P, const Term& t, const uint64_t (&row)[R]
 #pragma unroll
             for (int j = 0; j < R; j++) out[j] = truth_l(ta[j], pa[j], P.empty_str_code, P.empty_arr_code, P.empty_obj_code);
             break;
-        case TERM_LIKE: {  // Like.Apply (expression/comp_like.go:68-88) with a STRING constant pattern: MISSING, NULL for a non-string,
+        case TERM_LIKE:    // Like.Apply (expression/comp_like.go:68-88) with a STRING constant pattern: MISSING, NULL for a non-string,
                            // else the pattern's bit of the string's entry in the match table
+        case TERM_COLL: {  // Any / Every / AnyEvery.Evaluate (expression/coll_any.go:42-85) over a column: MISSING, NULL for a
+                           // non-array (collEval, coll_util.go:27-35, 49-57), else the predicate's bit of the array's entry
             const uint32_t bit = 1u << (uint32_t)t.b.cpayload;
+            const uint32_t want = term_table_tag(t.op);
 #pragma unroll
             for (int j = 0; j < R; j++) {
                 const uint32_t code = (uint32_t)pa[j];
-                const bool hit = ta[j] == T_STRING && code < P.like_n && (P.like_bits[code] & bit) != 0;
-                out[j] = ta[j] == T_MISSING ? L_MISSING : (ta[j] != T_STRING ? L_NULL : (hit ? L_TRUE : L_FALSE));
+                const bool hit = ta[j] == want && code < P.like_n && (P.like_bits[code] & bit) != 0;
+                out[j] = ta[j] == T_MISSING ? L_MISSING : (ta[j] != want ? L_NULL : (hit ? L_TRUE : L_FALSE));
             }
             break;
         }
@@ -998,8 +1001,9 @@ N1K_DEV bool fast_term_true(const FastTerm& t, uint32_t tg, uint64_t p, const ui
         case TERM_IS_VALUED: return tg > T_NULL;
         case TERM_IS_NOT_VALUED: return tg <= T_NULL;
         case TERM_STR_EQ: return tg == T_STRING && p == t.cpayload;
-        case TERM_LIKE: {
-            if (tg != T_STRING || (uint32_t)p >= t.like_n) return false;
+        case TERM_LIKE:
+        case TERM_COLL: {
+            if (tg != term_table_tag(t.op) || (uint32_t)p >= t.like_n) return false;
             const uint8_t b = like_lds ? like_lds[(uint32_t)p] : t.like_bits[(uint32_t)p];
             return (b & t.like_bit) != 0;
         }
@@ -1042,11 +1046,11 @@ __global__ __launch_bounds__(BLOCK) void scan_fast_kernel(const Program P, const
     const uint32_t S = F.lds_slots;
     const uint32_t tid = threadIdx.x;
     lds_table_init<BLOCK>(P, lds, S, tid);
-    // LIKE: a match table of at most kLikeLdsBytes entries sits behind the workgroup's table (launch_scan_fast sized it)
+    // LIKE, ANY / EVERY: a match table of at most kLikeLdsBytes entries sits behind the workgroup's table (launch_scan_fast sized it)
     const uint8_t* like_lds = nullptr;
 #pragma unroll
     for (int t = 0; t < kFastTerms; t++) {
-        if (t < (int)F.nterms && F.terms[t].op == TERM_LIKE && F.terms[t].like_n <= kLikeLdsBytes && !like_lds) {
+        if (t < (int)F.nterms && term_is_table_bit(F.terms[t].op) && F.terms[t].like_n <= kLikeLdsBytes && !like_lds) {
             uint32_t* words = (uint32_t*)(lds + (size_t)S * P.lds_words);
             const uint32_t* src = (const uint32_t*)F.terms[t].like_bits;
             for (uint32_t k = tid; k < (F.terms[t].like_n + 3u) / 4u; k += BLOCK) words[k] = src[k];
@@ -2945,7 +2949,7 @@ hipError_t launch_scan_fast(const Program& P, const FastArgs& F, const GlobalTab
                             uint32_t grid, uint32_t block, uint32_t rows_per_lane, hipStream_t st) {
     size_t shmem = (size_t)F.lds_slots * P.lds_words * 8;
     for (uint32_t t = 0; t < F.nterms; t++)
-        if (F.terms[t].op == TERM_LIKE && F.terms[t].like_n <= kLikeLdsBytes) {  // room for the staged match table
+        if (term_is_table_bit(F.terms[t].op) && F.terms[t].like_n <= kLikeLdsBytes) {  // room for the staged match table
             shmem += kLikeLdsBytes;
             break;
         }

@@ -394,12 +394,58 @@ struct EParser {
                     if (e->ch.size() < 2) return bad(w + " takes at least 2 arguments");
                     return e;
                 }
+                if ((w == "any" || w == "every") && lx.toks[p + 1].kind != TK::LParen) return collection();
                 return unsupported("function or keyword '" + w + "'");
             }
             case TK::LBrack: return unsupported("array constructor");
             case TK::Other: return unsupported("token '" + t.text + "'");
             default: return bad("unexpected token at offset " + std::to_string(t.begin));
         }
+    }
+
+    // stringer.go VisitAny / VisitEvery / VisitAnyEvery + visitBindings (no parentheses of its own):
+    //   any|every|any and every [`name` : ]`var` in|within <expr>[, more bindings] satisfies <P> end
+    // Taken: one binding, `in`, no name variable, a binding expression that is a leaf path of the row.  What <P> may
+    // hold is decided where it is compiled (coll_compile, n1k_coll.cpp).
+    std::unique_ptr<Expr> collection() {
+        const size_t begin = cur().begin;
+        uint32_t mode = 1;  // every
+        if (is_word("any")) {
+            mode = 0;
+            if (lx.toks[p + 1].kind == TK::Word && lx.toks[p + 1].text == "and" && lx.toks[p + 2].kind == TK::Word && lx.toks[p + 2].text == "every") {
+                mode = 2;
+                p += 2;
+            }
+        }
+        p++;
+        if (cur().kind != TK::Ident) return unsupported("ANY / EVERY whose variable is not a back-quoted identifier");
+        const std::string var = cur().text;
+        p++;
+        if (cur().kind == TK::Other && cur().text == ":") return unsupported("ANY / EVERY with a name variable (`name` : `value`)");
+        if (is_word("within")) return unsupported("ANY / EVERY ... WITHIN (descendants)");
+        if (!is_word("in")) return bad("expected IN after the variable of ANY / EVERY");
+        p++;
+        if (cur().kind == TK::LBrack) return unsupported("ANY / EVERY over a constant array");
+        if (cur().kind == TK::Word && !is_word("cover") && !is_word("meta"))
+            return unsupported("ANY / EVERY over '" + cur().text + "' (a function or a comprehension, not a leaf path)");
+        auto over = primary();
+        if (!over) return nullptr;
+        if (over->kind != EK::Path) return unsupported("ANY / EVERY over an expression that is not a leaf path");
+        if (cur().kind == TK::Comma) return unsupported("ANY / EVERY with several bindings");
+        if (!is_word("satisfies")) return bad("expected SATISFIES in ANY / EVERY");
+        p++;
+        auto pred = primary();
+        if (!pred) return nullptr;
+        if (!is_word("end")) return bad("expected END after the SATISFIES condition");
+        const size_t stop = cur().end;
+        p++;
+        auto e = mk(EK::Coll);
+        e->text = src.substr(begin, stop - begin);
+        e->coll_mode = mode;
+        e->coll_var = var;
+        e->coll_pred = std::move(pred);
+        e->ch.push_back(std::move(over));
+        return e;
     }
 
     // everything expression.Stringer wraps in parentheses

@@ -23,6 +23,8 @@ enum class EK {
     Const, Path, Add, Sub, Mult, Div, Mod, Neg, IDiv, IMod, Eq, LT, LE, Between, And, Or, Not,
     IsNull, IsNotNull, IsMissing, IsNotMissing, IsValued, IsNotValued,
     Like,  // (a like b), expression/comp_like.go; NOT LIKE arrives as (not (a like b))
+    Coll,  // any | every | any and every `v` in <leaf path> satisfies <P> end (expression/coll_any.go, coll_every.go,
+           // coll_any_every.go): ch[0] the binding expression, coll_* the rest
     Func  // numeric functions of one or two arguments (expression/func_num.go): fname
 };
 
@@ -37,6 +39,11 @@ struct Expr {
     std::string text;        // exact stringer text, e.g. (`default`.`price`)
     // Func
     std::string fname;       // round | trunc | abs | ceil | floor | sign | sqrt
+    // Coll: `text` is the whole term as the stringer wrote it.  The SATISFIES tree is kept apart from ch: its paths name
+    // the bound variable, not the row, so collect_paths must not meet them.
+    uint32_t coll_mode = 0;  // COLL_ANY | COLL_EVERY | COLL_ANY_EVERY (n1k_coll.h)
+    std::string coll_var;    // the bound variable
+    std::unique_ptr<Expr> coll_pred;
 };
 
 struct AggDef {

@@ -44,9 +44,9 @@ bool build_fast_args(n1k_handle* h, uint32_t max_slots, FastArgs& F, bool fuse, 
         } else if (t.op >= TERM_IS_NULL && t.op <= TERM_IS_NOT_VALUED) {
             if (t.a.is_const) return false;
             ft.op = t.op; ft.col = t.a.col;
-        } else if (t.op == TERM_LIKE) {  // column LIKE "pattern": the table and its extent travel in the term
+        } else if (term_is_table_bit(t.op)) {  // column LIKE "pattern", ANY / EVERY over a column: the table and its extent travel in the term
             if (t.a.is_const) return false;
-            ft.op = TERM_LIKE; ft.col = t.a.col; ft.like_n = P.like_n; ft.like_bit = 1u << (uint32_t)t.b.cpayload;
+            ft.op = t.op; ft.col = t.a.col; ft.like_n = P.like_n; ft.like_bit = 1u << (uint32_t)t.b.cpayload;
             ft.like_bits = P.like_bits;
             // (the kernels stage a small table in LDS, kLikeLdsBytes beside the workgroup's table)
             max_slots = (uint32_t)std::min<uint64_t>(max_slots, (156u * 1024u - kLikeLdsBytes) / (P.lds_words * 8));
@@ -255,11 +255,11 @@ n1k_status run_group_batch(n1k_handle* h, const n1k_batch* b) {
         }
         const Program& P = ndist ? Pc : h->prog;  // (shadows the handle's program for the launches below)
         const uint32_t table_bytes = F.lds_slots * P.lds_words * 8;
-        // a shape with a LIKE term carries kLikeLdsBytes of static LDS for the staged match table (n1k_spec.h: present by
+        // a shape with a LIKE or an ANY / EVERY term carries kLikeLdsBytes of static LDS for the staged match table (n1k_spec.h: present by
         // shape, whatever the table's size) — part of every budget below
         uint32_t like_lds = 0;
         for (uint32_t t = 0; t < F.nterms; t++)
-            if (F.terms[t].op == TERM_LIKE) like_lds = kLikeLdsBytes;
+            if (term_is_table_bit(F.terms[t].op)) like_lds = kLikeLdsBytes;
         // the word scatter's LDS (per DISTINCT aggregate one ScatterLds<uint64_t, 512, 4>, n1k_scatter.h: 2048 staged words,
         // counters, run starts) and, in what is left of the workgroup's share of the CU, its "already logged" caches
         const uint32_t scatter_bytes = ndist * (2048u * 8u + 2u * 256u * 4u + 256u * 4u + 256u * 8u + 2048u) + (ndist ? 64u : 0u);

@@ -60,19 +60,19 @@ constexpr bool spec_hashed() {
     return h;
 }
 
-// LIKE terms of a Spec: the match table (one byte per dictionary code, all terms of a plan share it) is staged in LDS before
+// LIKE and ANY / EVERY terms of a Spec: the match table (one byte per dictionary code, all terms of a plan share it) is staged in LDS before
 // the tile loop when it has at most kLikeLdsBytes entries — a per-row gather then costs an LDS read instead of a dependent
 // trip to L2 — and read from global memory otherwise.
 template <class Spec>
 constexpr bool spec_has_like() {
     bool h = false;
-    for (int t = 0; t < Spec::nterms; t++) h = h || Spec::terms[t].op == TERM_LIKE;
+    for (int t = 0; t < Spec::nterms; t++) h = h || term_is_table_bit(Spec::terms[t].op);
     return h;
 }
 template <class Spec>
 constexpr int spec_like_term() {
     for (int t = 0; t < Spec::nterms; t++)
-        if (Spec::terms[t].op == TERM_LIKE) return t;
+        if (term_is_table_bit(Spec::terms[t].op)) return t;
     return 0;
 }
 struct SpecLike {
@@ -110,8 +110,9 @@ N1K_DEV bool spec_term_true(int t, const FastArgs& F, const SpecLike& K, uint32_
         case TERM_IS_VALUED: return tg > T_NULL;
         case TERM_IS_NOT_VALUED: return tg <= T_NULL;
         case TERM_STR_EQ: return tg == T_STRING && p == F.terms[t].cpayload;
-        case TERM_LIKE: {  // one bit of the match table; a code the table does not cover is not read
-            if (tg != T_STRING || (uint32_t)p >= F.terms[t].like_n) return false;
+        case TERM_LIKE:
+        case TERM_COLL: {  // one bit of the match table (a string's entry, an array's); a code the table does not cover is not read
+            if (tg != term_table_tag(op) || (uint32_t)p >= F.terms[t].like_n) return false;
             const uint8_t b = K.in_lds ? K.lds[(uint32_t)p] : F.terms[t].like_bits[(uint32_t)p];
             return (b & F.terms[t].like_bit) != 0;
         }

@@ -79,9 +79,15 @@ enum : uint32_t {
     // a <op> const with op in {<, <=, >, >=, =}   ("(50 < x)" is stored as x GT 50)
     TERM_NUM_LT, TERM_NUM_LE, TERM_NUM_GT, TERM_NUM_GE, TERM_NUM_EQ,
     TERM_STR_EQ,       // a = STRING constant (dictionary code compare)
-    TERM_LIKE          // a LIKE STRING constant (expression/comp_like.go:68-88): one bit of the match table per dictionary code;
+    TERM_LIKE,         // a LIKE STRING constant (expression/comp_like.go:68-88): one bit of the match table per dictionary code;
                        // b.cpayload = the pattern's index in the plan (its bit)
+    TERM_COLL          // ANY / EVERY / ANY AND EVERY v IN a SATISFIES ... END (expression/coll_any.go, coll_every.go,
+                       // coll_any_every.go): the same bit test over the same table, for an ARRAY's entry; b.cpayload = its bit
 };
+// TERM_LIKE and TERM_COLL are one row test: MISSING stays MISSING, a value whose tag is not the expected one is NULL, else
+// the term's bit of the value's dictionary entry in the match table.
+constexpr bool term_is_table_bit(uint32_t op) { return op == TERM_LIKE || op == TERM_COLL; }
+constexpr uint32_t term_table_tag(uint32_t op) { return op == TERM_COLL ? (uint32_t)T_ARRAY : (uint32_t)T_STRING; }
 
 struct Term {
     uint32_t op;
@@ -191,8 +197,8 @@ struct Program {
     uint64_t* wide_flt;
     unsigned long long* wide_count;  // distinct wide values met so far
     uint32_t wide_bits, pad1;
-    // LIKE: like_bits[code] bit p = pattern p of the plan matches dictionary string `code`; codes at or beyond like_n have
-    // no entry and are not read
+    // LIKE: like_bits[code] bit p = pattern p of the plan matches dictionary string `code`; ANY / EVERY: bit 7 - q = collection
+    // predicate q holds for the array whose canonical text is entry `code`; codes at or beyond like_n have no entry and are not read
     const uint8_t* like_bits;
     uint32_t like_n, pad2;
     DevCol cols[kMaxCols];
@@ -376,19 +382,19 @@ constexpr int kFastCols = 3, kFastTerms = 2, kFastKeys = 2, kFastAggs = 5;
 constexpr int kFastDerived = 3, kSpecCols = kFastCols + kFastDerived;
 
 struct FastTerm {
-    uint32_t op;    // TERM_NUM_* / TERM_IS_* / TERM_STR_EQ / TERM_LIKE
+    uint32_t op;    // TERM_NUM_* / TERM_IS_* / TERM_STR_EQ / TERM_LIKE / TERM_COLL
     uint32_t col;   // column slot of operand a
     union {
         uint32_t ctag;    // the constant's tag
-        uint32_t like_n;  // TERM_LIKE: entries of the match table (Program::like_n); codes at or beyond it are not read
+        uint32_t like_n;  // TERM_LIKE / TERM_COLL: entries of the match table (Program::like_n); codes at or beyond it are not read
     };
     union {
         uint32_t pad;
-        uint32_t like_bit;  // TERM_LIKE: the pattern's bit in a table entry
+        uint32_t like_bit;  // TERM_LIKE / TERM_COLL: the pattern's (predicate's) bit in a table entry
     };
     union {
         uint64_t cpayload;         // the constant's payload
-        const uint8_t* like_bits;  // TERM_LIKE: the match table (Program::like_bits)
+        const uint8_t* like_bits;  // TERM_LIKE / TERM_COLL: the match table (Program::like_bits)
     };
 };
 // A match table of at most this many bytes (= dictionary codes) is copied into LDS by the bounded and the plan-specialised
@@ -485,7 +491,7 @@ inline uint64_t part_region_next(uint64_t off, uint64_t cap, uint32_t width) { r
 
 // compile-time shape of a plan handled by scan_spec_kernel (see n1k_spec.h)
 struct SpecTerm {
-    uint32_t op;         // TERM_NUM_* / TERM_IS_* / TERM_STR_EQ / TERM_LIKE
+    uint32_t op;         // TERM_NUM_* / TERM_IS_* / TERM_STR_EQ / TERM_LIKE / TERM_COLL
     uint32_t col;        // column slot
     uint32_t const_int;  // TERM_NUM_*: 1 = the constant is an INT, 0 = FLOAT
 };

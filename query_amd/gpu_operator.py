@@ -332,6 +332,14 @@ class GpuFilterGroup:
         self._check(self._lib.n1k_like_stats(self._h, C.byref(out)))
         return {"device_strings": int(out[0]), "host_strings": int(out[1]), "patterns": int(out[2]), "device_threshold": int(out[3])}
 
+    def coll_stats(self) -> dict:
+        """How the ANY / EVERY bits of this operator's match table were built: arrays of the dictionary evaluated on the
+        device / on the host, distinct collection predicates of the plan, and the number of new dictionary entries from which
+        the device route is taken."""
+        out = (C.c_uint64 * 4)()
+        self._check(self._lib.n1k_coll_stats(self._h, C.byref(out)))
+        return {"device_arrays": int(out[0]), "host_arrays": int(out[1]), "predicates": int(out[2]), "device_threshold": int(out[3])}
+
     def reopen(self):
         self._check(self._lib.n1k_reset(self._h))
 
