@@ -9,10 +9,19 @@
 // One lane per document.  A wave stages the bytes of its (up to 64, consecutive) documents in LDS with coalesced 16-byte
 // loads and every lane then scans its own document there: an iterative descent along the wanted field chains (first field
 // of a name wins, as FirstFind), a validating skip of everything else.  The kernel takes the common shapes itself and hands
-// the rest to the host's scalar extractor by marking the document (status 1): escapes in a wanted string or in a name that
-// is compared, array / object values of a wanted path, numbers beyond the exactly convertible range (> 18 digits; > 15
-// digits or |exponent| > 22 with a fraction or exponent), documents that are not objects, documents larger than the wave's
-// LDS share, anything that does not parse — the host then produces the value or names the malformed document, exactly as
+// the rest to the host's scalar extractor by marking the document (status 1):
+//   * escapes in a wanted string, or in a member name of an object in which a path still looks for its field (names in
+//     skipped values, and names behind the point where every path of the level has found its field, are not compared);
+//   * array / object values of a wanted path;
+//   * wanted numbers beyond the exactly convertible range — with `digits` counted from the first non-zero digit to the
+//     last one written (trailing zeros too) and e10 = exponent - fraction digits: > 18 digits; or, with a fraction or an
+//     exponent, > 15 digits or |e10| > 22 (numbers that are only skipped are validated, never handed over);
+//   * a skipped value that nests more than 64 non-empty arrays / objects;
+//   * documents that are not objects, documents that do not fit the wave's LDS share staged from the 16-byte boundary
+//     below their start (length + offset % 16 > kJsonWaveBytes - 16, offset counted from the batch's first byte);
+//   * a string whose 64-bit hash collides with another string's, or that finds no slot within 128 probes;
+//   * anything that does not parse
+// — the host then produces the value or names the malformed document, exactly as
 // n1k_extract_json does (n1k_json.cpp).  Strings become provisional ids: slots of a per-batch open-addressed table keyed by
 // a 64-bit hash of the bytes and verified against the first occurrence; only the DISTINCT strings travel to the host, whose
 // dictionary gives them their codes, and a second small kernel rewrites the ids.
