@@ -12,7 +12,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libn1k.so")
-SOURCES = ["n1k_kernels.hip", "n1k_bins.hip", "n1k_jsondev.hip", "n1k_like.hip", "n1k_like.cpp", "n1k_coll.hip", "n1k_coll.cpp", "n1k_jsonpush.cpp", "n1k_plan.cpp", "n1k_engine.cpp", "n1k_scan.cpp", "n1k_partitioned.cpp", "n1k_distinct.cpp",
+SOURCES = ["n1k_kernels.hip", "n1k_bins.hip", "n1k_jsondev.hip", "n1k_matchtable.hip", "n1k_matchtable.cpp", "n1k_like.cpp", "n1k_coll.cpp", "n1k_jsonpush.cpp", "n1k_plan.cpp", "n1k_engine.cpp", "n1k_scan.cpp", "n1k_partitioned.cpp", "n1k_distinct.cpp",
            "n1k_finish.cpp", "n1k_tail.cpp", "n1k_exchange.cpp", "n1k_jit.cpp", "n1k_json.cpp"]
 HEADERS = ["n1k_types.h", "n1k_device.h", "n1k_tables.h", "n1k_scatter.h", "n1k_spec.h", "n1k_like.h", "n1k_coll.h", "n1k_jit.h", "n1k_kernels.h", "n1k_plan.h", os.path.join("..", "..", "include", "n1k.h")]
 HOST_HEADERS = ["n1k_engine.h"]  # host-only: not part of source_hash()
@@ -62,7 +62,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     headers = [os.path.join(CSRC, f) for f in HEADERS + HOST_HEADERS] + [os.path.abspath(__file__)]
 
     def compile_one(src: str) -> str:
-        obj = os.path.join(OBJDIR, src + ".o")  # (n1k_like.hip and n1k_like.cpp are two objects)
+        obj = os.path.join(OBJDIR, src + ".o")  # (n1k_matchtable.hip and n1k_matchtable.cpp are two objects)
         path = os.path.join(CSRC, src)
         deps = headers if not src.endswith(".hip") else [os.path.join(CSRC, f) for f in HEADERS]  # (kernels see no host header)
         if force or _stale(obj, [path] + deps):

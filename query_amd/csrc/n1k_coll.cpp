@@ -1,5 +1,5 @@
-// n1k_coll.cpp — ANY / EVERY: the predicate compiler, what only the host evaluator does, and the two evaluator entry
-// points of the C ABI.
+// n1k_coll.cpp — ANY / EVERY: the predicate compiler and what only the host evaluator does.  (The device route and the
+// entry points of the C ABI: n1k_matchtable.cpp.)
 #include "n1k_coll.h"
 
 #include <cerrno>
@@ -263,7 +263,7 @@ void coll_eval_block_host(const std::vector<CollPred>& preds, uint32_t first_bit
     for (uint64_t i = 0; i < n; i++) {
         const uint8_t* s = bytes + (offsets[i] - offsets[0]);
         const uint32_t len = (uint32_t)(offsets[i + 1] - offsets[i]);
-        if (!len || s[0] != '[') continue;
+        if (!coll_array_text(s, len)) continue;
         for (size_t q = 0; q < preds.size(); q++) {
             bool left = false;
             if (coll_eval<true>(preds[q].prog, s, len, left)) bits[i] |= (uint8_t)(1u << (first_bit - q));
@@ -272,101 +272,3 @@ void coll_eval_block_host(const std::vector<CollPred>& preds, uint32_t first_bit
 }
 
 }  // namespace n1k
-
-using namespace n1k;
-
-static bool coll_offsets_ok(uint64_t n, const uint64_t* offsets) {
-    for (uint64_t i = 0; i < n; i++)
-        if (offsets[i + 1] < offsets[i] || offsets[i + 1] - offsets[i] > 0x7FFFFFFFull) return false;
-    return true;
-}
-
-// one whole `any ... end` term -> program; N1K_UNSUPPORTED for what n1k_create refuses in a plan, N1K_INVALID for text
-// that is no such term
-static n1k_status coll_parse(const char* text, size_t len, std::vector<CollPred>& preds) {
-    PlanError err;
-    const std::string src(text ? text : "", len);
-    auto e = parse_expression(src, err);
-    if (!e) return err.unsupported ? N1K_UNSUPPORTED : N1K_INVALID;
-    if (e->kind != EK::Coll) return N1K_INVALID;
-    preds.resize(1);
-    preds[0].text = src;
-    if (!coll_compile(e.get(), preds[0].prog, err)) return err.unsupported ? N1K_UNSUPPORTED : N1K_INVALID;
-    return N1K_OK;
-}
-
-extern "C" {
-
-n1k_status n1k_coll_eval(const char* predicate_text, size_t len, uint64_t n, const uint64_t* offsets, const char* bytes, uint8_t* out_bits) {
-    return guarded(nullptr, [&]() -> n1k_status {
-    if ((len && !predicate_text) || (n && (!offsets || !out_bits)) || !coll_offsets_ok(n, offsets)) return N1K_INVALID;
-    if (n && offsets[n] > offsets[0] && !bytes) return N1K_INVALID;
-    std::vector<CollPred> preds;
-    const n1k_status st = coll_parse(predicate_text, len, preds);
-    if (st != N1K_OK) return st;
-    if (n) memset(out_bits, 0, n);
-    coll_eval_block_host(preds, 0, n, offsets, (const uint8_t*)bytes, out_bits);
-    return N1K_OK;
-    });
-}
-
-n1k_status n1k_coll_eval_device(int device, const char* predicate_text, size_t len, uint64_t n, const uint64_t* offsets, const char* bytes,
-                                uint8_t* out_bits, uint64_t* out_left_to_host) {
-    return guarded(nullptr, [&]() -> n1k_status {
-    if ((len && !predicate_text) || (n && (!offsets || !out_bits)) || n >= 0xFFFFFFF0ull || !coll_offsets_ok(n, offsets)) return N1K_INVALID;
-    if (n && offsets[n] > offsets[0] && !bytes) return N1K_INVALID;
-    std::vector<CollPred> preds;
-    const n1k_status st = coll_parse(predicate_text, len, preds);
-    if (st != N1K_OK) return st;
-    if (out_left_to_host) *out_left_to_host = 0;
-    if (n == 0) return N1K_OK;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev || hipSetDevice(device) != hipSuccess) return N1K_DEVICE_ERROR;
-    const uint64_t nbytes = offsets[n] - offsets[0];
-    DevBuf<uint8_t> d_bytes, d_bits, d_left, d_prog;
-    DevBuf<uint64_t> d_off;
-    std::vector<uint8_t> left(n);
-    auto run = [&]() -> hipError_t {
-        hipError_t e;
-        if ((e = d_bytes.ensure(nbytes + 16)) != hipSuccess) return e;
-        if ((e = d_off.ensure(n + 1)) != hipSuccess) return e;
-        if ((e = d_bits.ensure(n)) != hipSuccess) return e;
-        if ((e = d_left.ensure(n)) != hipSuccess) return e;
-        if ((e = d_prog.ensure(sizeof(CollProg))) != hipSuccess) return e;
-        if (nbytes && (e = hipMemcpy(d_bytes.p, bytes, nbytes, hipMemcpyHostToDevice)) != hipSuccess) return e;
-        if ((e = hipMemcpy(d_off.p, offsets, (n + 1) * 8, hipMemcpyHostToDevice)) != hipSuccess) return e;
-        if ((e = hipMemcpy(d_prog.p, &preds[0].prog, sizeof(CollProg), hipMemcpyHostToDevice)) != hipSuccess) return e;
-        CollKernelArgs A{};
-        A.bytes = d_bytes.p;
-        A.offsets = d_off.p;
-        A.n = (uint32_t)n;
-        A.nprog = 1;
-        A.first_bit = 0;
-        A.progs = (const CollProg*)d_prog.p;
-        A.out_bits = d_bits.p;
-        A.out_left = d_left.p;
-        if ((e = launch_coll_match(A, nullptr)) != hipSuccess) return e;
-        if ((e = hipDeviceSynchronize()) != hipSuccess) return e;
-        if ((e = hipMemcpy(out_bits, d_bits.p, n, hipMemcpyDeviceToHost)) != hipSuccess) return e;
-        return hipMemcpy(left.data(), d_left.p, n, hipMemcpyDeviceToHost);
-    };
-    const hipError_t e = run();
-    d_bytes.release();
-    d_off.release();
-    d_bits.release();
-    d_left.release();
-    d_prog.release();
-    if (e != hipSuccess) return N1K_DEVICE_ERROR;
-    uint64_t nleft = 0;
-    for (uint64_t i = 0; i < n; i++)
-        if (left[i]) {
-            nleft++;
-            out_bits[i] = 0;
-            coll_eval_block_host(preds, 0, 1, &offsets[i], (const uint8_t*)bytes + (offsets[i] - offsets[0]), &out_bits[i]);
-        }
-    if (out_left_to_host) *out_left_to_host = nleft;
-    return N1K_OK;
-    });
-}
-
-}  // extern "C"

@@ -65,14 +65,14 @@ struct CollProg {
 };
 
 struct CollKernelArgs {
-    const uint8_t* bytes;     // the entries' bytes back to back (+ 16 spare bytes)
-    const uint64_t* offsets;  // n + 1; entry i = bytes[offsets[i] - offsets[0], offsets[i + 1] - offsets[0])
-    uint32_t n, nprog;
-    uint32_t first_bit, pad;  // program q writes bit first_bit - q
-    const CollProg* progs;    // nprog programs (device memory)
-    uint8_t* out_bits;        // n bytes (0 for an entry that is no array, and for one left to the host)
-    uint8_t* out_left;        // n bytes: 1 = left to the host evaluator
+    EntryBlockArgs blk;          // out_bits: 0 for an entry that is no array text, and for one left to the host evaluator
+    uint32_t nprog, first_bit;   // program q writes bit first_bit - q
+    const CollProg* progs;       // nprog programs (device memory)
 };
+
+// Is this dictionary entry array text?  The dictionary does not record tags: canonical text of an array begins with '['
+// and has its ']', so at least 2 bytes.  (A STRING that begins with '[' passes too; no row with tag STRING reads its bits.)
+N1K_HD bool coll_array_text(const uint8_t* s, uint64_t len) { return len >= 2 && s[0] == '['; }
 
 // ---- the cursor
 

@@ -404,130 +404,6 @@ n1k_status ensure_rank(n1k_handle* h) {
     return N1K_OK;
 }
 
-// LIKE match table: like_bits[code] bit p = pattern p matches dictionary string `code`.  Same rules as the rank table
-// above, except that a grown dictionary EXTENDS it: the entries of the old codes stay as they are (equal bytes, equal
-// code), only the new codes are matched — on the host below kLikeDeviceThreshold of them, by like_match_kernel from there
-// on (the strings the kernel leaves — too long, not valid UTF-8 — go through the host matcher either way).
-n1k_status ensure_like(n1k_handle* h) {
-    Program& P = h->prog;
-    if (h->like_patterns.empty() && h->coll_preds.empty()) {
-        P.like_bits = nullptr;
-        P.like_n = 0;
-        return N1K_OK;
-    }
-    const size_t n = h->dict.size(), first = h->like_built_for;
-    if (n > first) {
-        if (n + 4 > h->d_like.n) {  // (4 spare bytes: the kernels that stage the table in LDS copy whole words)
-            // the table moves: launches in flight may still read the old allocation
-            DevBuf<uint8_t> nb;
-            HIP_TRY(h, nb.ensure(std::max(n, h->d_like.n * 2) + 4));
-            hipError_t e = hipStreamSynchronize(h->stream);
-            if (e == hipSuccess && first) e = hipMemcpy(nb.p, h->d_like.p, first, hipMemcpyDeviceToDevice);
-            if (e != hipSuccess) nb.release();
-            HIP_TRY(h, e);
-            h->d_like.release();
-            h->d_like = nb;
-        }
-        const size_t cnt = n - first;
-        std::vector<uint64_t> off(cnt + 1);
-        off[0] = 0;
-        for (size_t i = 0; i < cnt; i++) off[i + 1] = off[i] + h->dict[first + i].size();
-        std::vector<uint8_t> bytes(off[cnt] + 1);
-        for (size_t i = 0; i < cnt; i++) memcpy(bytes.data() + off[i], h->dict[first + i].data(), h->dict[first + i].size());
-        std::vector<uint8_t> bits(cnt);
-        LikeKernelArgs A{};
-        if (h->like_patterns.empty()) {
-            // (collection predicates alone: their bits are written below)
-        } else if (cnt >= kLikeDeviceThreshold && like_dev_patterns(h->like_patterns, A.pat)) {
-            HIP_TRY(h, hipStreamSynchronize(h->stream));  // (the scratch buffers may still be read by the last extension)
-            HIP_TRY(h, h->d_like_bytes.ensure(off[cnt] + 16));
-            HIP_TRY(h, h->d_like_off.ensure(cnt + 1));
-            HIP_TRY(h, h->d_like_left.ensure(cnt));
-            if (off[cnt]) HIP_TRY(h, hipMemcpy(h->d_like_bytes.p, bytes.data(), off[cnt], hipMemcpyHostToDevice));
-            HIP_TRY(h, hipMemcpy(h->d_like_off.p, off.data(), (cnt + 1) * 8, hipMemcpyHostToDevice));
-            A.bytes = h->d_like_bytes.p;
-            A.offsets = h->d_like_off.p;
-            A.n = (uint32_t)cnt;
-            A.out_bits = h->d_like.p + first;  // (entries no launch has been told about yet: like_n grows below)
-            A.out_left = h->d_like_left.p;
-            HIP_TRY(h, launch_like_match(A, h->stream));
-            std::vector<uint8_t> left(cnt);
-            HIP_TRY(h, hipMemcpyAsync(left.data(), h->d_like_left.p, cnt, hipMemcpyDeviceToHost, h->stream));
-            HIP_TRY(h, hipStreamSynchronize(h->stream));
-            size_t nleft = 0;
-            for (size_t i = 0; i < cnt; i++) nleft += left[i];
-            if (nleft) {
-                HIP_TRY(h, hipMemcpy(bits.data(), h->d_like.p + first, cnt, hipMemcpyDeviceToHost));
-                for (size_t i = 0; i < cnt; i++)
-                    if (left[i]) like_match_block_host(h->like_patterns, 1, &off[i], bytes.data() + off[i], &bits[i]);
-                HIP_TRY(h, hipMemcpy(h->d_like.p + first, bits.data(), cnt, hipMemcpyHostToDevice));
-            }
-            h->like_on_device += cnt - nleft;
-            h->like_on_host += nleft;
-        } else {
-            like_match_block_host(h->like_patterns, cnt, off.data(), bytes.data(), bits.data());
-            HIP_TRY(h, hipMemcpy(h->d_like.p + first, bits.data(), cnt, hipMemcpyHostToDevice));
-            h->like_on_host += cnt;
-        }
-        if (!h->coll_preds.empty()) {
-            // ANY / EVERY: the predicates' bits of the new entries that are array text, OR-ed into what LIKE wrote.  Same two
-            // routes: coll_match_kernel from kCollDeviceThreshold new entries on (what it leaves — too long, an escape or a
-            // number only the host takes — goes through the host evaluator), the host evaluator below.
-            const uint32_t top = kLikeMaxPatterns - 1;
-            std::vector<uint8_t> cb(cnt, 0);
-            size_t narr = 0;
-            for (size_t i = 0; i < cnt; i++) narr += !h->dict[first + i].empty() && h->dict[first + i][0] == '[';
-            if (cnt >= kCollDeviceThreshold) {
-                HIP_TRY(h, hipStreamSynchronize(h->stream));
-                HIP_TRY(h, h->d_like_bytes.ensure(off[cnt] + 16));
-                HIP_TRY(h, h->d_like_off.ensure(cnt + 1));
-                HIP_TRY(h, h->d_like_left.ensure(cnt));
-                HIP_TRY(h, h->d_coll_bits.ensure(cnt));
-                HIP_TRY(h, h->d_coll_prog.ensure(h->coll_preds.size() * sizeof(CollProg)));
-                if (off[cnt]) HIP_TRY(h, hipMemcpy(h->d_like_bytes.p, bytes.data(), off[cnt], hipMemcpyHostToDevice));
-                HIP_TRY(h, hipMemcpy(h->d_like_off.p, off.data(), (cnt + 1) * 8, hipMemcpyHostToDevice));
-                for (size_t q = 0; q < h->coll_preds.size(); q++)
-                    HIP_TRY(h, hipMemcpy(h->d_coll_prog.p + q * sizeof(CollProg), &h->coll_preds[q].prog, sizeof(CollProg), hipMemcpyHostToDevice));
-                CollKernelArgs C{};
-                C.bytes = h->d_like_bytes.p;
-                C.offsets = h->d_like_off.p;
-                C.n = (uint32_t)cnt;
-                C.nprog = (uint32_t)h->coll_preds.size();
-                C.first_bit = top;
-                C.progs = (const CollProg*)h->d_coll_prog.p;
-                C.out_bits = h->d_coll_bits.p;
-                C.out_left = h->d_like_left.p;
-                HIP_TRY(h, launch_coll_match(C, h->stream));
-                std::vector<uint8_t> left(cnt);
-                HIP_TRY(h, hipMemcpyAsync(cb.data(), h->d_coll_bits.p, cnt, hipMemcpyDeviceToHost, h->stream));
-                HIP_TRY(h, hipMemcpyAsync(left.data(), h->d_like_left.p, cnt, hipMemcpyDeviceToHost, h->stream));
-                HIP_TRY(h, hipStreamSynchronize(h->stream));
-                size_t nleft = 0;
-                for (size_t i = 0; i < cnt; i++)
-                    if (left[i]) {
-                        nleft++;
-                        cb[i] = 0;
-                        coll_eval_block_host(h->coll_preds, top, 1, &off[i], bytes.data() + off[i], &cb[i]);
-                    }
-                h->coll_on_device += narr - nleft;
-                h->coll_on_host += nleft;
-            } else {
-                coll_eval_block_host(h->coll_preds, top, cnt, off.data(), bytes.data(), cb.data());
-                h->coll_on_host += narr;
-            }
-            if (!h->like_patterns.empty()) {
-                HIP_TRY(h, hipMemcpy(bits.data(), h->d_like.p + first, cnt, hipMemcpyDeviceToHost));
-                for (size_t i = 0; i < cnt; i++) cb[i] |= bits[i];
-            }
-            HIP_TRY(h, hipMemcpy(h->d_like.p + first, cb.data(), cnt, hipMemcpyHostToDevice));
-        }
-        h->like_built_for = n;
-    }
-    P.like_bits = h->d_like.p;
-    P.like_n = (uint32_t)h->like_built_for;
-    return N1K_OK;
-}
-
 // Decide the key bit fields once the column kinds are known (first batch).
 n1k_status fix_layout(n1k_handle* h, const n1k_batch* b) {
     Program& P = h->prog;
@@ -836,11 +712,7 @@ static void destroy_handle(n1k_handle* h) {
         if (h->ev_q1) (void)hipEventDestroy(h->ev_q1);
         h->d_rank.release();
         h->d_like.release();
-        h->d_like_bytes.release();
-        h->d_like_off.release();
-        h->d_like_left.release();
-        h->d_coll_bits.release();
-        h->d_coll_prog.release();
+        h->match_scratch.release();
         h->d_keys.release();
         h->d_acc.release();
         h->d_rep.release();

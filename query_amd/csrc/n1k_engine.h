@@ -60,6 +60,22 @@ struct DevBuf {
     }
 };
 
+// device scratch of the match table's device route (n1k_matchtable.cpp)
+struct MatchScratch {
+    DevBuf<uint8_t> bytes;   // the block's bytes
+    DevBuf<uint64_t> off;    // its n + 1 offsets
+    DevBuf<uint8_t> left;    // 2n: the LIKE kernel's left-to-host flags, then the ANY / EVERY kernel's
+    DevBuf<uint8_t> bits;    // 2n: the LIKE kernel's bits where they do not go straight into the table, then the ANY / EVERY kernel's
+    DevBuf<uint8_t> progs;   // CollProg[]
+    void release() {
+        bytes.release();
+        off.release();
+        left.release();
+        bits.release();
+        progs.release();
+    }
+};
+
 inline uint64_t next_pow2(uint64_t x) {
     uint64_t p = 1;
     while (p < x) p <<= 1;
@@ -191,13 +207,11 @@ struct n1k_handle {
     DevBuf<uint8_t> d_like;
     size_t like_built_for = 0;                // dictionary codes the table covers
     uint64_t like_on_device = 0, like_on_host = 0;  // strings matched by like_match_kernel / by the host matcher
-    DevBuf<uint8_t> d_like_bytes, d_like_left;      // scratch of the device route: the new entries' bytes, the kernel's flags
-    DevBuf<uint64_t> d_like_off;
     // ANY / EVERY: the plan's distinct collection predicates.  Predicate q owns bit 7 - q of the same table (LIKE pattern p
     // owns bit p; together at most 8), evaluated for the entries that are array text by the same ensure_like.
     std::vector<CollPred> coll_preds;
     uint64_t coll_on_device = 0, coll_on_host = 0;  // arrays evaluated by coll_match_kernel / by the host evaluator
-    DevBuf<uint8_t> d_coll_bits, d_coll_prog;       // scratch of the device route: the kernel's bits, the programs
+    MatchScratch match_scratch;                     // kept from one extension of the table to the next
 
     // compiled program (column pointers are patched per batch)
     Program prog{};
@@ -308,7 +322,6 @@ bool to_operand(n1k_handle* h, const Expr* e, Operand& o, PlanError& err);
 bool compile_plan(n1k_handle* h, PlanError& err);
 n1k_status ensure_device(n1k_handle* h);
 n1k_status ensure_rank(n1k_handle* h);
-n1k_status ensure_like(n1k_handle* h);
 n1k_status fix_layout(n1k_handle* h, const n1k_batch* b);
 n1k_status ensure_table(n1k_handle* h, uint64_t incoming_rows);
 n1k_status ensure_table_groups(n1k_handle* h, uint64_t groups);
@@ -318,6 +331,9 @@ void drain_events(n1k_handle* h);
 n1k_status validate_batch(n1k_handle* h, const n1k_batch* b);
 uint64_t batch_bytes_per_row(const n1k_handle* h);
 void default_value(const AggDef& d, n1k_value& v, n1k_partial& p);
+
+// n1k_matchtable.cpp: the LIKE / ANY / EVERY match table, built and extended before the launches that read it
+n1k_status ensure_like(n1k_handle* h);
 
 // n1k_scan.cpp: one batch through Filter + InitialGroup (kernel choice), Filter-only batches, staging of host batches
 bool build_fast_args(n1k_handle* h, uint32_t max_slots, FastArgs& F, bool fuse = false, bool partition_only = false);

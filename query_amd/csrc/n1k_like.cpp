@@ -1,4 +1,5 @@
-// n1k_like.cpp — LIKE: pattern compiler, the host matcher, and the two matcher entry points of the C ABI.
+// n1k_like.cpp — LIKE: pattern compiler and the host matcher.  (The device route and the entry points of the C ABI:
+// n1k_matchtable.cpp.)
 #include "n1k_like.h"
 
 #include "n1k_engine.h"
@@ -127,82 +128,3 @@ bool like_dev_patterns(const std::vector<LikePattern>& pats, LikeDevPatterns& ou
 }
 
 }  // namespace n1k
-
-using namespace n1k;
-
-static bool offsets_ok(uint64_t n, const uint64_t* offsets) {
-    for (uint64_t i = 0; i < n; i++)
-        if (offsets[i + 1] < offsets[i] || offsets[i + 1] - offsets[i] > 0x7FFFFFFFull) return false;
-    return true;
-}
-
-extern "C" {
-
-n1k_status n1k_like_match(const char* pattern, size_t pattern_len, uint64_t n, const uint64_t* offsets, const char* bytes, uint8_t* out_bits) {
-    return guarded(nullptr, [&]() -> n1k_status {
-    if ((pattern_len && !pattern) || (n && (!offsets || !out_bits)) || !offsets_ok(n, offsets)) return N1K_INVALID;
-    if (n && offsets[n] > offsets[0] && !bytes) return N1K_INVALID;
-    std::vector<LikePattern> pats(1);
-    if (!like_compile(pattern ? pattern : "", pattern_len, pats[0])) return N1K_INVALID;
-    like_match_block_host(pats, n, offsets, (const uint8_t*)bytes, out_bits);
-    return N1K_OK;
-    });
-}
-
-n1k_status n1k_like_match_device(int device, const char* pattern, size_t pattern_len, uint64_t n, const uint64_t* offsets, const char* bytes,
-                                 uint8_t* out_bits, uint64_t* out_left_to_host) {
-    return guarded(nullptr, [&]() -> n1k_status {
-    if ((pattern_len && !pattern) || (n && (!offsets || !out_bits)) || n >= 0xFFFFFFF0ull || !offsets_ok(n, offsets)) return N1K_INVALID;
-    if (n && offsets[n] > offsets[0] && !bytes) return N1K_INVALID;
-    std::vector<LikePattern> pats(1);
-    if (!like_compile(pattern ? pattern : "", pattern_len, pats[0])) return N1K_INVALID;
-    if (out_left_to_host) *out_left_to_host = 0;
-    if (n == 0) return N1K_OK;
-    LikeKernelArgs A{};
-    if (!like_dev_patterns(pats, A.pat)) {  // a program the kernel does not take: every string is the host's
-        like_match_block_host(pats, n, offsets, (const uint8_t*)bytes, out_bits);
-        if (out_left_to_host) *out_left_to_host = n;
-        return N1K_OK;
-    }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev || hipSetDevice(device) != hipSuccess) return N1K_DEVICE_ERROR;
-    const uint64_t nbytes = offsets[n] - offsets[0];
-    DevBuf<uint8_t> d_bytes, d_bits, d_left;
-    DevBuf<uint64_t> d_off;
-    std::vector<uint8_t> left(n);
-    auto run = [&]() -> hipError_t {
-        hipError_t e;
-        if ((e = d_bytes.ensure(nbytes + 16)) != hipSuccess) return e;
-        if ((e = d_off.ensure(n + 1)) != hipSuccess) return e;
-        if ((e = d_bits.ensure(n)) != hipSuccess) return e;
-        if ((e = d_left.ensure(n)) != hipSuccess) return e;
-        if (nbytes && (e = hipMemcpy(d_bytes.p, bytes, nbytes, hipMemcpyHostToDevice)) != hipSuccess) return e;
-        if ((e = hipMemcpy(d_off.p, offsets, (n + 1) * 8, hipMemcpyHostToDevice)) != hipSuccess) return e;
-        A.bytes = d_bytes.p;
-        A.offsets = d_off.p;
-        A.n = (uint32_t)n;
-        A.out_bits = d_bits.p;
-        A.out_left = d_left.p;
-        if ((e = launch_like_match(A, nullptr)) != hipSuccess) return e;
-        if ((e = hipDeviceSynchronize()) != hipSuccess) return e;
-        if ((e = hipMemcpy(out_bits, d_bits.p, n, hipMemcpyDeviceToHost)) != hipSuccess) return e;
-        return hipMemcpy(left.data(), d_left.p, n, hipMemcpyDeviceToHost);
-    };
-    const hipError_t e = run();
-    d_bytes.release();
-    d_off.release();
-    d_bits.release();
-    d_left.release();
-    if (e != hipSuccess) return N1K_DEVICE_ERROR;
-    uint64_t nleft = 0;
-    for (uint64_t i = 0; i < n; i++)
-        if (left[i]) {
-            nleft++;
-            out_bits[i] = like_match_host(pats[0], (const uint8_t*)bytes + (offsets[i] - offsets[0]), (size_t)(offsets[i + 1] - offsets[i])) ? 1 : 0;
-        }
-    if (out_left_to_host) *out_left_to_host = nleft;
-    return N1K_OK;
-    });
-}
-
-}  // extern "C"

@@ -155,12 +155,17 @@ struct LikeDevPatterns {
     uint8_t prog[kLikeMaxPatterns][kLikeDevProgBytes];
 };
 
-struct LikeKernelArgs {
-    const uint8_t* bytes;     // the strings of this block of dictionary entries, back to back (+ 16 spare bytes)
-    const uint64_t* offsets;  // n + 1; string i = bytes[offsets[i] - offsets[0], offsets[i + 1] - offsets[0])
+// a block of dictionary entries as the match table's kernels take it (n1k_matchtable.hip), whatever they evaluate
+struct EntryBlockArgs {
+    const uint8_t* bytes;     // the entries' bytes back to back (+ 16 spare bytes)
+    const uint64_t* offsets;  // n + 1; entry i = bytes[offsets[i] - offsets[0], offsets[i + 1] - offsets[0])
     uint32_t n, pad;
-    uint8_t* out_bits;        // n bytes: bit p = pattern p matches string i (0 for a string left to the host)
-    uint8_t* out_left;        // n bytes: 1 = left to the host matcher (longer than kLikeDevMaxLen, or not valid UTF-8)
+    uint8_t* out_bits;        // n bytes: the matcher's bits of entry i (0 for an entry that is not its business or left to the host)
+    uint8_t* out_left;        // n bytes: 1 = left to the host (longer than the matcher's limit, or what only the host does)
+};
+
+struct LikeKernelArgs {
+    EntryBlockArgs blk;   // out_bits: bit p = pattern p matches; left: longer than kLikeDevMaxLen, or not valid UTF-8
     LikeDevPatterns pat;
 };
 

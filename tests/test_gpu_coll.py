@@ -145,6 +145,36 @@ def test_device_evaluator_when_a_waves_entries_span_more_than_its_slab():
         assert left == excluded and np.array_equal(dev, host) and np.array_equal(dev, want), term
 
 
+BLOCK_EDGES = [1, 63, 64, 65, 255, 256, 257]  # the last lane's clamp, a full wave, a wave of one lane, a second workgroup of one entry
+
+
+def test_device_evaluator_at_the_edges_of_a_block():
+    """Blocks that end inside a wave, on a wave and one entry into the next workgroup; entries of 0 to 40 bytes, some of them
+    no array text.  Once more with a last array of 15 KB: the final wave then spans more than its slab and reads what it
+    takes from global memory."""
+    rng = random.Random(11)
+    mode, cond = cu.ANY, ("cmp", "=", [], "t_1", False)
+    term = cu.term_text(mode, cond)
+    pool = []
+    for i in range(max(BLOCK_EDGES)):
+        if i % 7 == 3:
+            pool.append(rng.choice([b"", b"[", b"plain", b"]["]))
+            continue
+        text = cu.texts_of([[rng.choice(["a", "t_1", "ab", 1, None, {"f": 2}]) for _ in range(rng.randint(0, 5))]])[0]
+        pool.append(text if len(text) <= 40 else b"[]")
+    assert min(len(e) for e in pool) == 0 and max(len(e) for e in pool) > 30
+    huge = cu.texts_of([["ab"] * 3000 + ["t_1"]])[0]
+    assert len(huge) > SLAB
+    for n in BLOCK_EDGES:
+        for last in (None, huge):
+            entries = pool[:n] if last is None else pool[:n - 1] + [last]
+            dev, left = cu.device_eval(term, entries)
+            host = cu.host_eval(term, entries)
+            assert np.array_equal(dev, host), (n, last is None, np.nonzero(dev != host))
+            assert left == sum(1 for e in entries if len(e) >= 2 and e[:1] == b"[" and len(e) > DEV_MAX_LEN), (n, left)
+            assert n < 64 or 0 < int(host.sum()) < n
+
+
 # ------------------------------------------------------------------ differential by substitution
 
 # dictionary: strings, then the canonical texts of arrays (and one object) that the terms below split in many ways
@@ -540,6 +570,90 @@ def test_a_large_dictionary_takes_the_device_route_and_a_small_one_the_host_rout
         else:
             assert stats["device_arrays"] == 0 and stats["host_arrays"] == narr, stats
         assert stats["predicates"] == 2
+
+
+LIKE_MAX_LEN = 128  # bytes of a string like_match_kernel takes (tests/test_gpu_like.py)
+MIXED_PATTERNS = ["%7", "%b_c%"]
+MIXED_PREDS = [(cu.ANY, ("cmp", "=", [], "t_1", False)), (cu.EVERY, ("like", [], "%w%4"))]
+
+
+def mixed_dictionary(n, tag, with_bracket):
+    """n distinct entries, strings then arrays, every one marked with `tag`; among them what each kernel leaves to the host
+    and what only looks like an array.  Returns (entries, texts of the strings as Go reads them, array values)."""
+    ns = n // 2
+    strings = [("%s%d" % (tag, i)).encode() for i in range(ns)]
+    strings[1] = (tag + "x" * 300 + "7").encode()     # over 128 B: the host matcher's (and matches "%7")
+    strings[2] = b"ab\xffc" + tag.encode()            # not valid UTF-8: idem (the byte is one U+FFFD, which `_` takes)
+    strings[3] = ("[looks like one " + tag).encode()  # a STRING that begins with '[': evaluated as array text, read by no ARRAY row
+    if with_bracket:
+        strings[4] = b"["                             # one byte: no array text
+    arrays = [[tag + "w%d" % i] + (["t_1"] if i % 3 == 0 else []) + ([i] if i % 2 else []) for i in range(n - ns)]
+    arrays[1] = [tag + "w1"] * 60 + ["t_1"]           # over 192 B: the host evaluator's
+    arrays[2] = ['x"y', tag, "t_1"]                   # an escaped string FIRST, under both predicates: idem
+    return strings + cu.texts_of(arrays), [s.decode("utf-8", errors="replace") for s in strings], arrays
+
+
+def valid_utf8(b):
+    try:
+        b.decode("utf-8")
+        return True
+    except UnicodeDecodeError:
+        return False
+
+
+def mixed_counts(entries, on_device):
+    """(device strings, host strings, device arrays, host arrays) of one extension of the table by `entries`, by the rules
+    DESIGN.md §4 states: LIKE is evaluated for every entry, and the kernel leaves a string over 128 B or not valid UTF-8;
+    ANY / EVERY for an entry of at least 2 bytes that begins with '[', and the kernel leaves one over 192 B or one with an
+    escaped string where these predicates compare (mixed_dictionary puts the escape first: no early exit hides it)."""
+    like_left = sum(1 for e in entries if len(e) > LIKE_MAX_LEN or not valid_utf8(e))
+    arr = [e for e in entries if len(e) >= 2 and e[:1] == b"["]
+    coll_left = sum(1 for e in arr if len(e) > DEV_MAX_LEN or b"\\" in e)
+    if not on_device:
+        return 0, len(entries), 0, len(arr)
+    return len(entries) - like_left, like_left, len(arr) - coll_left, coll_left
+
+
+@pytest.mark.parametrize("below", [1, 0], ids=["host-route-then-device", "device-route-twice"])
+def test_a_plan_with_like_and_collection_terms_builds_one_table_on_both_routes(below):
+    """Two LIKE patterns over a string column and an ANY and an EVERY over an array column in one Filter: a dictionary of
+    T - 1 entries goes through the host matchers for both kinds, one of T through both kernels (one upload, merged once).
+    A second batch then interns T more: the table is extended — from an odd entry when the first held T - 1 — by both
+    kernels, and the old entries keep their bits."""
+    cond = "(%s or %s or %s or %s)" % tuple(["(%s like %s)" % (D("s"), json.dumps(p)) for p in MIXED_PATTERNS] +
+                                            [cu.term_text(m, c, over=D("a")) for m, c in MIXED_PREDS])
+    op = query_amd.GpuFilterGroup(plan.filter_group_plan(cond, [], ["count(*)"]))
+    T = op.like_stats()["device_threshold"]
+    assert T == op.coll_stats()["device_threshold"] and T % 2 == 0
+    rng = np.random.default_rng(below)
+    dictionary, str_hit, arr_hit, str_codes, arr_codes = [], [], [], [], []
+    want_stats = np.zeros(4, np.int64)
+    for tag, n in (("s", T - below), ("u", T)):
+        entries, texts, arrays = mixed_dictionary(n, tag, with_bracket=tag == "s")
+        base, ns = len(dictionary), len(texts)
+        dictionary += entries
+        str_codes += range(base, base + ns)
+        arr_codes += range(base + ns, base + n)
+        str_hit += [any(lu.like4(t, p) is True for p in MIXED_PATTERNS) for t in texts]
+        arr_hit += [any(cu.coll_mirror(m, c, a) is True for m, c in MIXED_PREDS) for a in arrays]
+        # rows over every entry interned so far (the old ones too), each special entry among them
+        rows = 20_000
+        si = np.concatenate([np.arange(len(str_codes)), rng.integers(0, len(str_codes), rows - len(str_codes))])
+        ai = np.concatenate([rng.integers(0, len(arr_codes), rows - len(arr_codes)), np.arange(len(arr_codes))])
+        cols = {D("s"): n1o.Column(D("s"), n1o.COL_DICT32, codes=np.array(str_codes, np.uint32)[si]),
+                D("a"): n1o.Column(D("a"), n1o.COL_TAGGED64, tags=np.full(rows, n1o.T_ARRAY, np.uint8), payload=np.array(arr_codes, np.uint64)[ai])}
+        op.process_items([cols[p] for p in op.column_paths], dictionary)
+        got = op.after_items().aggs[0][0][1]
+        assert int(_ffi.lib().n1k_dict_size(op._h)) == len(dictionary)  # (the handle interned nothing of its own: n new entries)
+        want = int((np.array(str_hit)[si] | np.array(arr_hit)[ai]).sum())
+        assert 0 < want < rows and got == want, (tag, got, want)
+        want_stats += mixed_counts(entries, on_device=n >= T)
+        ls, cs = op.like_stats(), op.coll_stats()
+        assert (ls["device_strings"], ls["host_strings"], cs["device_arrays"], cs["host_arrays"]) == tuple(want_stats), (tag, ls, cs, want_stats)
+        assert ls["patterns"] == 2 and cs["predicates"] == 2
+        op.reopen()  # (keeps the table)
+    assert want_stats[0] > 0 and want_stats[2] > 0 and want_stats[1] >= 3 and want_stats[3] >= 2
+    op.done()
 
 
 def test_having_any_over_an_array_valued_group_key():

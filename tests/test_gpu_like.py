@@ -110,6 +110,38 @@ def test_device_matcher_when_a_waves_strings_span_more_than_its_slab():
         assert left == excluded and np.array_equal(dev, host) and np.array_equal(dev, want), pattern
 
 
+BLOCK_EDGES = [1, 63, 64, 65, 255, 256, 257]  # the last lane's clamp, a full wave, a wave of one lane, a second workgroup of one string
+
+
+def test_device_matcher_at_the_edges_of_a_block():
+    """Blocks that end inside a wave, on a wave and one string into the next workgroup; strings of 0 to 40 bytes.  Once more
+    with a last string of 10 KB: the final wave then spans more than its slab and reads what it takes from global memory."""
+    rng = np.random.default_rng(11)
+    pool = ["".join(rng.choice(list("aabbc_%\né"), int(rng.integers(0, 41)))).encode()[:40] for _ in range(max(BLOCK_EDGES))]
+    pool[5] = pool[5][:3] + b"\xff"  # not valid UTF-8 (as is a string the cut at 40 bytes splits a character of): the host matcher's
+
+    def valid(b):
+        try:
+            b.decode("utf-8")
+            return True
+        except UnicodeDecodeError:
+            return False
+
+    assert min(len(s) for s in pool) == 0 and max(len(s) for s in pool) == 40 and 0 < sum(not valid(s) for s in pool[:63]) < 10
+    huge = b"ab" * 5000
+    assert len(huge) > 64 * DEV_MAX_LEN
+    for n in BLOCK_EDGES:
+        for last in (None, huge):
+            strings = pool[:n] if last is None else pool[:n - 1] + [last]
+            excluded = sum(1 for s in strings if len(s) > DEV_MAX_LEN or not valid(s))
+            for pattern in (b"%ab%", b"a%"):
+                dev, left = lu.device_match(pattern, strings)
+                host = lu.host_match(pattern, strings)
+                assert np.array_equal(dev, host), (n, last is None, pattern, np.nonzero(dev != host))
+                assert left == excluded, (n, last is None, left, excluded)
+            assert n < 64 or 0 < int(host.sum()) < n
+
+
 def test_like_term_on_both_sides_of_the_lds_switch():
     """The bounded and the run-time-built kernels stage a match table of at most 4096 entries in LDS and read a larger one
     from global memory: dictionaries of 3000 and of 6000 strings, DICT32 and TAGGED64 string column, against the oracle by

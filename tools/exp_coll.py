@@ -11,8 +11,11 @@
              end (upload + kernel + results back), arrays per second each, for several block sizes.
   route      the handle's own route (ensure_like): a plan with two collection predicates, N new dictionary entries interned,
              then the first push of a one-row batch timed against a second push that brings no new entry.
+  mixed      route, with exp_like.py's three LIKE patterns over a string column in the same Filter: both kinds of term
+             evaluated for every new entry, one table.
 
-usage: exp_coll.py [scan|evaluator|route|all] [rows] [arrays]   — prints one JSON line per measurement."""
+usage: exp_coll.py [scan|evaluator|route|mixed|all] [rows] [arrays] [route sizes, comma separated]   — prints one JSON line per
+measurement."""
 import ctypes as C
 import json
 import os
@@ -135,9 +138,11 @@ def evaluator(n):
             break
 
 
-def route():
+def route(sizes=None, mixed=False):
     D = bench.D
     cond = "(any `g` in %s satisfies (`g` = \"t_1\") end or every `g` in %s satisfies (`g` like \"%%zz%%\") end)" % (D("a"), D("a"))
+    if mixed:
+        cond = "(%s or (%s like \"%%1_3%%\") or (%s like \"item\\\\_0%%7\") or (%s like \"%%-b_x%%\"))" % (cond, D("s"), D("s"), D("s"))
     pj = query_amd.plan.filter_group_plan(cond, [], ["count(*)"])
     probe = query_amd.GpuFilterGroup(pj)
     thr = probe.coll_stats()["device_threshold"]
@@ -149,29 +154,35 @@ def route():
         tags = np.full(1, T_ARRAY, dtype=np.uint8)
         payload = np.zeros(1, dtype=np.uint64)
 
-    for n in (thr // 4, thr // 2, thr - 1, thr, 2 * thr, 4 * thr, 16 * thr):
+    class StrCol:
+        kind = _ffi.COL_DICT32
+        codes = np.zeros(1, dtype=np.uint32)
+
+    by_path = {D("a"): Col, D("s"): StrCol}
+    for n in sizes or (thr // 4, thr // 2, thr - 1, thr, 2 * thr, 4 * thr, 16 * thr):
         best_first, best_again, stats = 1e9, 1e9, None
         for rep in range(4):
             arrays = make_arrays(n, rng)
             op = query_amd.GpuFilterGroup(pj)
+            cols = [by_path[p] for p in op.column_paths]
             op.intern([b"[]"])
-            op.process_items([Col], None)  # device, stream, staging buffers: not what is measured
+            op.process_items(cols, None)  # device, stream, staging buffers: not what is measured
             op.sync()
             op.intern(arrays)
             t0 = time.perf_counter()
-            op.process_items([Col], None)
+            op.process_items(cols, None)
             op.sync()
             t1 = time.perf_counter()
-            op.process_items([Col], None)
+            op.process_items(cols, None)
             op.sync()
             t2 = time.perf_counter()
-            stats = op.coll_stats()
+            stats, like = op.coll_stats(), op.like_stats()
             op.done()
             if rep:
                 best_first, best_again = min(best_first, t1 - t0), min(best_again, t2 - t1)
-        print(json.dumps({"exp": "coll_route", "new_entries": n, "route": "device" if stats["device_arrays"] else "host",
+        print(json.dumps({"exp": "coll_route_mixed" if mixed else "coll_route", "new_entries": n, "route": "device" if stats["device_arrays"] else "host",
                           "first_push_ms": round(best_first * 1e3, 3), "push_without_new_entries_ms": round(best_again * 1e3, 3),
-                          "table_ms": round((best_first - best_again) * 1e3, 3), "coll": stats}), flush=True)
+                          "table_ms": round((best_first - best_again) * 1e3, 3), "coll": stats, **({"like": like} if mixed else {})}), flush=True)
 
 
 if __name__ == "__main__":
@@ -182,5 +193,8 @@ if __name__ == "__main__":
         scan(rows)
     if what in ("evaluator", "all"):
         evaluator(narr)
+    sizes = [int(x) for x in sys.argv[4].split(",")] if len(sys.argv) > 4 else None
     if what in ("route", "all"):
-        route()
+        route(sizes)
+    if what in ("mixed", "all"):
+        route(sizes, mixed=True)

@@ -14,7 +14,8 @@
            against a second push that brings no new string.  N just below kLikeDeviceThreshold goes through the host
            matcher, N at it through the kernel: both routes measured where they are meant to cross.
 
-usage: exp_like.py [scan|matcher|route|all] [rows] [strings]   — prints one JSON line per measurement."""
+usage: exp_like.py [scan|matcher|route|all] [rows] [strings] [route sizes, comma separated]   — prints one JSON line per
+measurement."""
 import ctypes as C
 import json
 import os
@@ -117,7 +118,7 @@ def matcher(n):
             break
 
 
-def route():
+def route(sizes=None):
     D = bench.D
     cond = "((%s like \"%%1_3%%\") or (%s like \"item\\\\_0%%7\") or (%s like \"%%-b_x%%\"))" % (D("s"), D("s"), D("s"))
     pj = query_amd.plan.filter_group_plan(cond, [], ["count(*)"])
@@ -130,7 +131,7 @@ def route():
         kind = _ffi.COL_DICT32
         codes = np.zeros(1, dtype=np.uint32)
 
-    for n in (thr // 4, thr // 2, thr - 1, thr, 2 * thr, 4 * thr, 16 * thr):
+    for n in sizes or (thr // 4, thr // 2, thr - 1, thr, 2 * thr, 4 * thr, 16 * thr):
         best_first, best_again, stats = 1e9, 1e9, None
         for rep in range(5):
             strings = [b"item_%09d-%s" % (i, bytes(rng.integers(97, 123, 14).astype(np.uint8))) for i in range(n)]
@@ -163,4 +164,4 @@ if __name__ == "__main__":
     if what in ("matcher", "all"):
         matcher(nstr)
     if what in ("route", "all"):
-        route()
+        route([int(x) for x in sys.argv[4].split(",")] if len(sys.argv) > 4 else None)
