@@ -383,6 +383,33 @@ n1k_status n1k_coll_eval_device(int device, const char *predicate_text, size_t l
  * predicates of the plan, out[3] the number of new dictionary entries from which the device route is taken */
 n1k_status n1k_coll_stats(const n1k_handle *h, uint64_t out[4]);
 
+/* --------------------------------------------------------------------- IN -- */
+
+/*
+ * `a IN [c, c, ...]` over a list of constants (expression/coll_in.go:61-91) runs on the device.  The list falls apart by
+ * type class, since Equals is FALSE across classes: its numbers are searched per row in a sorted array the handle keeps
+ * in device memory (at most 1024 distinct numbers in the lists of one plan, each within +-2^53), its booleans and its
+ * `null` are flags, and its STRINGS are one more predicate of the match table — "is this dictionary entry one of the
+ * list's strings", one hash lookup per DISTINCT entry, one bit test per row.  A list that holds strings takes one of the
+ * eight bits LIKE patterns and collection predicates share; at most 4096 distinct strings in one list.  The two entry
+ * points below run the string matchers on their own (tests, diagnostics); n1k_in_stats says which route built a handle's table.
+ *
+ * n1k_in_match: the host matcher, no GPU needed.  list_text is the bracketed list alone, as expression/stringer.go writes
+ * it (["a", "b"]) or as the JSON of a folded constant (["a","b"]); its elements that are not strings are parsed and
+ * otherwise unused.  String i is bytes[offsets[i] - offsets[0], offsets[i + 1] - offsets[0]); out_bits[i] = 1 when the list
+ * holds it, bytes compared as bytes.  N1K_UNSUPPORTED for a list n1k_create refuses in a plan, N1K_INVALID for text that
+ * is no list.
+ */
+n1k_status n1k_in_match(const char *list_text, size_t len, uint64_t n, const uint64_t *offsets, const char *bytes,
+                        uint8_t *out_bits);
+/* The same through in_match_kernel on `device`.  *out_left_to_host counts the strings the kernel left to the host
+ * matcher: exactly those longer than 128 bytes.  The results are those of n1k_in_match. */
+n1k_status n1k_in_match_device(int device, const char *list_text, size_t len, uint64_t n, const uint64_t *offsets,
+                               const char *bytes, uint8_t *out_bits, uint64_t *out_left_to_host);
+/* out[0] distinct IN lists of the plan, out[1] dictionary strings looked up on the device so far, out[2] on the host,
+ * out[3] the number of new dictionary entries from which the device route is taken */
+n1k_status n1k_in_stats(const n1k_handle *h, uint64_t out[4]);
+
 /* ------------------------------------------------- multi-GPU (one per rank) -- */
 
 /*

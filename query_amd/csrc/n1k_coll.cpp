@@ -147,6 +147,7 @@ struct Compiler {
                         : e->kind == EK::IsNotMissing ? CN_IS_NOT_MISSING : e->kind == EK::IsValued ? CN_IS_VALUED : CN_IS_NOT_VALUED;
                 return node(nd);
             case EK::Coll: refuse("a nested ANY / EVERY"); return -1;
+            case EK::In: refuse("IN inside SATISFIES"); return -1;
             case EK::Func: refuse("function '" + e->fname + "' inside SATISFIES"); return -1;
             case EK::Path:
             case EK::Const: refuse("a bare value used for its truth inside SATISFIES"); return -1;

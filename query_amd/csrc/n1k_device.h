@@ -103,6 +103,37 @@ N1K_DEV uint32_t equals_l(uint32_t ta, uint64_t pa, uint32_t tb, uint64_t pb, ui
     return L_FALSE;
 }
 
+// TERM_IN, the numeric half: does the NUMBER (tg, p) equal one of nums[0, n)?  The constants are distinct, ascending and
+// within +-2^53, so an INT constant is exactly its double and a FLOAT constant is never integral: a binary search in
+// float64 finds the one candidate, and two INTs then have to agree exactly (value/integer.go:68-87 — 2^53 + 1 is not
+// 2^53 although their doubles are equal).  NaN equals nothing; -0.0 equals 0.
+N1K_DEV bool in_num_hit(const double* nums, uint32_t n, uint32_t tg, uint64_t p) {
+    const double x = num_actual(tg, p);
+    uint32_t lo = 0, hi = n;  // -> the first constant that is not below x
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (nums[mid] < x) lo = mid + 1;
+        else hi = mid;
+    }
+    if (lo >= n) return false;
+    const double c = nums[lo];
+    if (!(c == x)) return false;
+    return tg != T_INT || (int64_t)c == (int64_t)p;
+}
+
+// In.Apply (expression/coll_in.go:61-91) over a constant list, without the STRING case's table read: `str_hit` is the
+// list's bit of the value's match-table entry (read by the caller for a STRING value only).  flags: the term's mask | IN_*.
+N1K_DEV uint32_t in_term_l(uint32_t flags, const double* nums, uint32_t n, uint32_t tg, uint64_t p, bool str_hit) {
+    if (tg == T_MISSING) return L_MISSING;
+    if (flags & IN_EMPTY) return L_FALSE;
+    if (tg == T_NULL) return L_NULL;
+    bool hit;
+    if (tg == T_STRING) hit = str_hit;
+    else if (tg == T_INT || tg == T_FLOAT) hit = in_num_hit(nums, n, tg, p);
+    else hit = tg == T_TRUE ? (flags & IN_HAS_TRUE) != 0 : (tg == T_FALSE && (flags & IN_HAS_FALSE) != 0);  // (an ARRAY or OBJECT equals no scalar)
+    return hit ? L_TRUE : ((flags & IN_HAS_NULL) ? L_NULL : L_FALSE);
+}
+
 // type + Truth() of a value used as a condition
 // (value/integer.go:136-138, float.go:190-192, string.go:148, boolean.go:125, null.go:106, missing.go:113)
 N1K_DEV uint32_t truth_l(uint32_t tag, uint64_t p, uint32_t empty_str, uint32_t empty_arr, uint32_t empty_obj) {

@@ -25,6 +25,7 @@
 #include "n1k_json.h"
 #include "n1k_kernels.h"
 #include "n1k_coll.h"
+#include "n1k_in.h"
 #include "n1k_like.h"
 #include "n1k_plan.h"
 
@@ -64,8 +65,8 @@ struct DevBuf {
 struct MatchScratch {
     DevBuf<uint8_t> bytes;   // the block's bytes
     DevBuf<uint64_t> off;    // its n + 1 offsets
-    DevBuf<uint8_t> left;    // 2n: the LIKE kernel's left-to-host flags, then the ANY / EVERY kernel's
-    DevBuf<uint8_t> bits;    // 2n: the LIKE kernel's bits where they do not go straight into the table, then the ANY / EVERY kernel's
+    DevBuf<uint8_t> left;    // 3n: the LIKE kernel's left-to-host flags, then the ANY / EVERY kernel's, then the IN kernel's
+    DevBuf<uint8_t> bits;    // 3n: the LIKE kernel's bits where they do not go straight into the table, then the ANY / EVERY kernel's, then the IN kernel's
     DevBuf<uint8_t> progs;   // CollProg[]
     void release() {
         bytes.release();
@@ -212,6 +213,18 @@ struct n1k_handle {
     std::vector<CollPred> coll_preds;
     uint64_t coll_on_device = 0, coll_on_host = 0;  // arrays evaluated by coll_match_kernel / by the host evaluator
     MatchScratch match_scratch;                     // kept from one extension of the table to the next
+    // IN: the plan's distinct constant lists.  A list that holds strings owns one more bit of the same table (above the LIKE
+    // patterns' bits: pattern count + its index among such lists; all three kinds together at most 8); the strings of all
+    // lists lie in one open-addressed table (host copy and device copy), the numbers of all lists in one array.  Both
+    // device copies are made by the first ensure_like and freed with the handle.
+    std::vector<InList> in_lists;
+    std::vector<double> in_numbers;
+    uint32_t in_string_lists = 0;
+    InTableHost in_table;
+    DevBuf<uint8_t> d_in_table;
+    DevBuf<double> d_in_nums;
+    bool in_uploaded = false;
+    uint64_t in_on_device = 0, in_on_host = 0;  // strings matched by in_match_kernel / by the host matcher
 
     // compiled program (column pointers are patched per batch)
     Program prog{};

@@ -139,6 +139,18 @@ N1K_DEV void eval_term(const Program& P, const Term& t, const uint64_t (&row)[R]
             }
             break;
         }
+        case TERM_IN: {  // In.Apply (expression/coll_in.go:61-91) with a constant list: a STRING reads the list's bit of its
+                         // entry in the match table, a NUMBER searches the list's sorted constants, a BOOLEAN reads a flag
+            const uint32_t flags = (uint32_t)t.b.cpayload, mask = flags & 0xFFu;
+            const uint32_t begin = (uint32_t)t.c.cpayload, end = (uint32_t)(t.c.cpayload >> 32);
+#pragma unroll
+            for (int j = 0; j < R; j++) {
+                const uint32_t code = (uint32_t)pa[j];
+                const bool str_hit = ta[j] == T_STRING && mask && code < P.like_n && (P.like_bits[code] & mask) != 0;
+                out[j] = in_term_l(flags, P.in_nums + begin, end - begin, ta[j], pa[j], str_hit);
+            }
+            break;
+        }
         default: {  // TERM_NUM_*: a <op> NUMBER constant; same result as LT/LE/Eq.Apply with the operands in this order
             const uint32_t ct = t.b.ctag;
             const uint64_t cp = t.b.cpayload;
@@ -1006,6 +1018,13 @@ N1K_DEV bool fast_term_true(const FastTerm& t, uint32_t tg, uint64_t p, const ui
             if (tg != term_table_tag(t.op) || (uint32_t)p >= t.like_n) return false;
             const uint8_t b = like_lds ? like_lds[(uint32_t)p] : t.like_bits[(uint32_t)p];
             return (b & t.like_bit) != 0;
+        }
+        case TERM_IN: {  // TRUE exactly when the value equals a constant of the list
+            if (tg == T_INT || tg == T_FLOAT) return in_num_hit(t.in_nums, t.in_n, tg, p);
+            if (tg != T_STRING) return tg == T_TRUE ? (t.like_bit & IN_HAS_TRUE) != 0 : (tg == T_FALSE && (t.like_bit & IN_HAS_FALSE) != 0);
+            if (!(t.like_bit & 0xFFu) || (uint32_t)p >= t.like_n) return false;
+            const uint8_t b = like_lds ? like_lds[(uint32_t)p] : t.like_bits[(uint32_t)p];
+            return (b & t.like_bit & 0xFFu) != 0;
         }
         default: {
             if (tg <= T_NULL) return false;  // MISSING / NULL are never TRUE

@@ -13,8 +13,12 @@
 //     that is no array text (coll_array_text) gets no bit and is not the host's either: no row with tag ARRAY reads it.  An
 //     array on which the evaluator met what only the host does (an escaped string under a comparison, a number beyond the
 //     exact conversions, a string under LIKE that is not valid UTF-8) is flagged for the host.
+//   InMatcher (in_match_kernel): in_lookup (n1k_in.h) — hash the entry's bytes, probe the plan's table of IN-list string
+//     constants, compare the candidate's bytes — gives the mask of the lists that hold the entry.  Every entry is its
+//     business; bytes are bytes, so only an entry beyond the limit is the host's.
 #include <hip/hip_runtime.h>
 #include "n1k_coll.h"
+#include "n1k_in.h"
 
 namespace n1k {
 
@@ -60,6 +64,15 @@ struct CollMatcher {
     }
 };
 
+struct InMatcher {
+    using Args = InKernelArgs;
+    struct Params { uint32_t none; };  // (the table is probed where it lies: a few dependent reads per entry, L2-resident)
+    static constexpr uint32_t kMaxLen = kInDevMaxLen;
+    static __device__ void stage(Params&, const Args&, uint32_t) {}
+    static __device__ bool wants(const uint8_t*, uint64_t) { return true; }
+    static __device__ uint8_t match(const Params&, const Args& A, const uint8_t* s, uint32_t len, bool&) { return in_lookup(A.tab, s, len); }
+};
+
 template <class Matcher>
 __global__ __launch_bounds__(256) void match_table_kernel(const typename Matcher::Args A) {
     constexpr uint32_t kSlab = 64 * Matcher::kMaxLen;  // bytes 64 entries within the limit span at most
@@ -102,6 +115,7 @@ __global__ __launch_bounds__(256) void match_table_kernel(const typename Matcher
 
 constexpr auto like_match_kernel = match_table_kernel<LikeMatcher>;
 constexpr auto coll_match_kernel = match_table_kernel<CollMatcher>;
+constexpr auto in_match_kernel = match_table_kernel<InMatcher>;
 
 hipError_t launch_like_match(const LikeKernelArgs& A, hipStream_t st) {
     if (A.blk.n == 0) return hipSuccess;
@@ -115,6 +129,14 @@ hipError_t launch_coll_match(const CollKernelArgs& A, hipStream_t st) {
     if (A.nprog > kLikeMaxPatterns) return hipErrorInvalidValue;
     const uint32_t grid = (A.blk.n + kMatchBlock - 1) / kMatchBlock;
     hipLaunchKernelGGL(coll_match_kernel, dim3(grid), dim3(kMatchBlock), 0, st, A);
+    return hipGetLastError();
+}
+
+hipError_t launch_in_match(const InKernelArgs& A, hipStream_t st) {
+    if (A.blk.n == 0) return hipSuccess;
+    if (A.tab.nconst == 0 || !A.tab.slots) return hipErrorInvalidValue;
+    const uint32_t grid = (A.blk.n + kMatchBlock - 1) / kMatchBlock;
+    hipLaunchKernelGGL(in_match_kernel, dim3(grid), dim3(kMatchBlock), 0, st, A);
     return hipGetLastError();
 }
 

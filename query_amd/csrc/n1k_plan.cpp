@@ -448,6 +448,49 @@ struct EParser {
         return e;
     }
 
+    // The right side of IN: a list of constants, `["a", "b"]` as the ArrayConstruct stringer writes it or `["a","b"]`, the
+    // JSON of a folded constant.  Elements: STRING, NUMBER (a negative one plain or in parentheses), true, false, null.
+    // Returns an EK::In whose ch holds the elements only (the caller puts the left operand in front).
+    std::unique_ptr<Expr> in_list() {
+        if (cur().kind != TK::LBrack) {
+            const char* what = cur().kind == TK::Ident || (cur().kind == TK::LParen && lx.toks[p + 1].kind == TK::Ident) ? "a path"
+                               : (cur().kind == TK::LParen && lx.toks[p + 1].kind == TK::Word && lx.toks[p + 1].text == "select") ? "a subquery"
+                               : "an expression";
+            return unsupported(std::string("IN whose right side is not a constant list (") + what + ")");
+        }
+        const size_t begin = cur().begin;
+        p++;
+        auto e = mk(EK::In);
+        while (cur().kind != TK::RBrack) {
+            if (!e->ch.empty()) {
+                if (cur().kind != TK::Comma) return bad("expected , or ] in the list of IN");
+                p++;
+            }
+            const Tok& t = cur();
+            if (t.kind == TK::Str || t.kind == TK::Num ||
+                (t.kind == TK::Word && (t.text == "true" || t.text == "false" || t.text == "null"))) {
+                e->ch.push_back(primary());
+            } else if (t.kind == TK::LParen && lx.toks[p + 1].kind == TK::Num && lx.toks[p + 2].kind == TK::RParen) {  // (-5)
+                e->ch.push_back(number(lx.toks[p + 1].text));
+                p += 3;
+            } else if (t.kind == TK::LParen && lx.toks[p + 1].kind == TK::Minus && lx.toks[p + 2].kind == TK::Num && lx.toks[p + 3].kind == TK::RParen) {
+                e->ch.push_back(number("-" + lx.toks[p + 2].text));
+                p += 4;
+            } else if (t.kind == TK::Word && t.text == "missing") {
+                return unsupported("IN list with the element `missing`");
+            } else if (t.kind == TK::LBrack || (t.kind == TK::Other && t.text == "{")) {
+                return unsupported("IN list with a nested array or object");
+            } else if (t.kind == TK::End) {
+                return bad("unterminated list of IN");
+            } else {
+                return unsupported("IN list with an element that is not a constant (a path or an expression)");
+            }
+        }
+        e->text = src.substr(begin, cur().end - begin);
+        p++;
+        return e;
+    }
+
     // everything expression.Stringer wraps in parentheses
     std::unique_ptr<Expr> paren() {
         size_t open = cur().begin;
@@ -582,6 +625,13 @@ struct EParser {
                     auto e = mk(EK::Like);
                     e->ch.push_back(std::move(first));
                     e->ch.push_back(std::move(o));
+                    return close(std::move(e));
+                }
+                if (t.text == "in") {  // stringer.go VisitIn: (a in b)
+                    p++;
+                    auto e = in_list();
+                    if (!e) return nullptr;
+                    e->ch.insert(e->ch.begin(), std::move(first));
                     return close(std::move(e));
                 }
                 return unsupported("operator '" + t.text + "'");

@@ -25,6 +25,8 @@ enum class EK {
     Like,  // (a like b), expression/comp_like.go; NOT LIKE arrives as (not (a like b))
     Coll,  // any | every | any and every `v` in <leaf path> satisfies <P> end (expression/coll_any.go, coll_every.go,
            // coll_any_every.go): ch[0] the binding expression, coll_* the rest
+    In,    // (a in [c, c, ...]), expression/coll_in.go, over a constant list: ch[0] the left operand, ch[1..] the elements
+           // (Const), `text` the bracketed list as the stringer wrote it; NOT IN arrives as (not (a in [...]))
     Func  // numeric functions of one or two arguments (expression/func_num.go): fname
 };
 

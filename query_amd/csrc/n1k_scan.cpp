@@ -44,10 +44,16 @@ bool build_fast_args(n1k_handle* h, uint32_t max_slots, FastArgs& F, bool fuse, 
         } else if (t.op >= TERM_IS_NULL && t.op <= TERM_IS_NOT_VALUED) {
             if (t.a.is_const) return false;
             ft.op = t.op; ft.col = t.a.col;
-        } else if (term_is_table_bit(t.op)) {  // column LIKE "pattern", ANY / EVERY over a column: the table and its extent travel in the term
+        } else if (term_is_table_bit(t.op)) {  // column LIKE "pattern", ANY / EVERY over a column, column IN [constants]: the table and its extent travel in the term
             if (t.a.is_const) return false;
             ft.op = t.op; ft.col = t.a.col; ft.like_n = P.like_n; ft.like_bit = 1u << (uint32_t)t.b.cpayload;
             ft.like_bits = P.like_bits;
+            if (t.op == TERM_IN) {  // its mask and flags as the term holds them, and its range of the plan's number constants
+                const uint32_t begin = (uint32_t)t.c.cpayload, end = (uint32_t)(t.c.cpayload >> 32);
+                ft.like_bit = (uint32_t)t.b.cpayload;
+                ft.in_nums = P.in_nums + begin;
+                ft.in_n = end - begin;
+            }
             // (the kernels stage a small table in LDS, kLikeLdsBytes beside the workgroup's table)
             max_slots = (uint32_t)std::min<uint64_t>(max_slots, (156u * 1024u - kLikeLdsBytes) / (P.lds_words * 8));
         } else if (t.op == TERM_EQ) {  // column = "string constant" (either side)

@@ -116,6 +116,14 @@ N1K_DEV bool spec_term_true(int t, const FastArgs& F, const SpecLike& K, uint32_
             const uint8_t b = K.in_lds ? K.lds[(uint32_t)p] : F.terms[t].like_bits[(uint32_t)p];
             return (b & F.terms[t].like_bit) != 0;
         }
+        case TERM_IN: {  // TRUE exactly when the value equals a constant of the list (In.Apply, expression/coll_in.go:61-91)
+            const uint32_t flags = F.terms[t].like_bit;
+            if (tg == T_INT || tg == T_FLOAT) return in_num_hit(F.terms[t].in_nums, F.terms[t].in_n, tg, p);
+            if (tg != T_STRING) return tg == T_TRUE ? (flags & IN_HAS_TRUE) != 0 : (tg == T_FALSE && (flags & IN_HAS_FALSE) != 0);
+            if (!(flags & 0xFFu) || (uint32_t)p >= F.terms[t].like_n) return false;
+            const uint8_t b = K.in_lds ? K.lds[(uint32_t)p] : F.terms[t].like_bits[(uint32_t)p];
+            return (b & flags & 0xFFu) != 0;
+        }
         default: {
             // collation of the row value against the NUMBER constant (value/integer.go:100-118, float.go:106-121)
             int c;

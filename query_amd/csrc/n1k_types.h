@@ -81,13 +81,23 @@ enum : uint32_t {
     TERM_STR_EQ,       // a = STRING constant (dictionary code compare)
     TERM_LIKE,         // a LIKE STRING constant (expression/comp_like.go:68-88): one bit of the match table per dictionary code;
                        // b.cpayload = the pattern's index in the plan (its bit)
-    TERM_COLL          // ANY / EVERY / ANY AND EVERY v IN a SATISFIES ... END (expression/coll_any.go, coll_every.go,
+    TERM_COLL,         // ANY / EVERY / ANY AND EVERY v IN a SATISFIES ... END (expression/coll_any.go, coll_every.go,
                        // coll_any_every.go): the same bit test over the same table, for an ARRAY's entry; b.cpayload = its bit
+    TERM_IN            // a IN [constants] (expression/coll_in.go:61-91).  b.cpayload = the list's mask in a match-table entry
+                       // (bits 0..7; 0: the list holds no string) | IN_* flags; c.cpayload = begin | end << 32, the list's
+                       // range of Program::in_nums
 };
 // TERM_LIKE and TERM_COLL are one row test: MISSING stays MISSING, a value whose tag is not the expected one is NULL, else
-// the term's bit of the value's dictionary entry in the match table.
-constexpr bool term_is_table_bit(uint32_t op) { return op == TERM_LIKE || op == TERM_COLL; }
+// the term's bit of the value's dictionary entry in the match table.  TERM_IN reads the same table for a STRING value (the
+// kernels that stage the table in LDS do so for all three) and answers the other tags from its numbers and flags.
+constexpr bool term_is_table_bit(uint32_t op) { return op == TERM_LIKE || op == TERM_COLL || op == TERM_IN; }
 constexpr uint32_t term_table_tag(uint32_t op) { return op == TERM_COLL ? (uint32_t)T_ARRAY : (uint32_t)T_STRING; }
+
+// TERM_IN: what the list holds besides strings and numbers (b.cpayload, FastTerm::like_bit)
+enum : uint32_t { IN_HAS_TRUE = 1u << 8, IN_HAS_FALSE = 1u << 9, IN_HAS_NULL = 1u << 10, IN_EMPTY = 1u << 11 };
+// Distinct number constants of all IN lists of one plan.  A choice, not a measurement: 10 probe steps per row and 8 KiB
+// that stay in L2.
+constexpr uint32_t kInMaxNumbers = 1024;
 
 struct Term {
     uint32_t op;
@@ -201,6 +211,10 @@ struct Program {
     // predicate q holds for the array whose canonical text is entry `code`; codes at or beyond like_n have no entry and are not read
     const uint8_t* like_bits;
     uint32_t like_n, pad2;
+    // IN: the number constants of the plan's lists as float64 (each within +-2^53, so an INT constant is exactly its
+    // double); every list's distinct numbers ascending, the lists back to back (device memory owned by the handle)
+    const double* in_nums;
+    uint32_t in_n, pad3;
     DevCol cols[kMaxCols];
     Term terms[kMaxTerms];
     LogicOp logic[kMaxLogic];
@@ -382,7 +396,7 @@ constexpr int kFastCols = 3, kFastTerms = 2, kFastKeys = 2, kFastAggs = 5;
 constexpr int kFastDerived = 3, kSpecCols = kFastCols + kFastDerived;
 
 struct FastTerm {
-    uint32_t op;    // TERM_NUM_* / TERM_IS_* / TERM_STR_EQ / TERM_LIKE / TERM_COLL
+    uint32_t op;    // TERM_NUM_* / TERM_IS_* / TERM_STR_EQ / TERM_LIKE / TERM_COLL / TERM_IN
     uint32_t col;   // column slot of operand a
     union {
         uint32_t ctag;    // the constant's tag
@@ -390,12 +404,15 @@ struct FastTerm {
     };
     union {
         uint32_t pad;
-        uint32_t like_bit;  // TERM_LIKE / TERM_COLL: the pattern's (predicate's) bit in a table entry
+        uint32_t like_bit;  // TERM_LIKE / TERM_COLL: the pattern's (predicate's) bit in a table entry; TERM_IN: the list's
+                            // mask (0: no string in the list) | IN_* flags
     };
     union {
         uint64_t cpayload;         // the constant's payload
-        const uint8_t* like_bits;  // TERM_LIKE / TERM_COLL: the match table (Program::like_bits)
+        const uint8_t* like_bits;  // TERM_LIKE / TERM_COLL / TERM_IN: the match table (Program::like_bits)
     };
+    const double* in_nums;  // TERM_IN: the list's number constants, ascending (its range of Program::in_nums), in_n of them
+    uint32_t in_n, pad2;
 };
 // A match table of at most this many bytes (= dictionary codes) is copied into LDS by the bounded and the plan-specialised
 // kernels before their tile loop; a larger one is read from global memory ("LIKE").

@@ -340,6 +340,14 @@ class GpuFilterGroup:
         self._check(self._lib.n1k_coll_stats(self._h, C.byref(out)))
         return {"device_arrays": int(out[0]), "host_arrays": int(out[1]), "predicates": int(out[2]), "device_threshold": int(out[3])}
 
+    def in_stats(self) -> dict:
+        """How the IN bits of this operator's match table were built: distinct constant lists of the plan, dictionary
+        strings looked up on the device / on the host, and the number of new dictionary entries from which the device route
+        is taken."""
+        out = (C.c_uint64 * 4)()
+        self._check(self._lib.n1k_in_stats(self._h, C.byref(out)))
+        return {"lists": int(out[0]), "device_strings": int(out[1]), "host_strings": int(out[2]), "device_threshold": int(out[3])}
+
     def reopen(self):
         self._check(self._lib.n1k_reset(self._h))
 

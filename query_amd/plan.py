@@ -21,6 +21,20 @@ def field_path(alias: str, *names: str) -> str:
     return s
 
 
+def in_list(path: str, values: Sequence) -> str:
+    """Stringer text of `path IN [values]` over constants (stringer.go VisitIn, VisitArrayConstruct):
+    in_list(field_path("d", "cat"), ["a", 3, None]) -> ((`d`.`cat`) in ["a", 3, null]).  Values: str, int, float, bool,
+    None (null).  Negative numbers come out in parentheses, as the reference writes a negation."""
+    def const(v):
+        if isinstance(v, (str, bool)) or v is None:
+            return json.dumps(v, ensure_ascii=False)
+        if isinstance(v, (int, float)):
+            t = json.dumps(v)
+            return "(%s)" % t if t.startswith("-") else t
+        raise TypeError("in_list takes str, int, float, bool and None, not %r" % (v,))
+    return "(%s in [%s])" % (path, ", ".join(const(v) for v in values))
+
+
 @dataclass
 class Filter:
     condition: str
