@@ -213,91 +213,47 @@ bool compile_cond(n1k_handle* h, const Expr* e, PlanError& err) {
         case EK::Between:
             h->need_rank = true;
             return push_term(TERM_BETWEEN, e->ch[0].get(), e->ch[1].get(), e->ch[2].get());
+        // The three kinds of the match table: the predicate is compiled once per plan and evaluated once per
+        // distinct dictionary entry (ensure_match_table); the row test reads its bit.  Two terms with the same text share
+        // everything.  b.cpayload holds the predicate's index until MatchTable::finalize_bits puts its bit there (pad
+        // stays 0: not a dictionary string, bind_columns leaves it alone).
         case EK::Like: {
-            // The pattern is compiled once per plan; the reference does the same for a constant (precompileLike) and
-            // compiles anything else per row, which stays with the reference operators.
+            // (the reference compiles a constant pattern once, precompileLike, and anything else per row, which stays with
+            //  the reference operators)
             const Expr* pat = e->ch[1].get();
             if (pat->kind != EK::Const || pat->ctag != T_STRING) {
                 err.unsupported = true;
                 err.msg = "LIKE with a pattern that is not a STRING constant (the reference compiles such a pattern per row)";
                 return false;
             }
-            size_t ix = 0;
-            while (ix < h->like_patterns.size() && h->like_patterns[ix].text != pat->cstr) ix++;
-            if (ix == h->like_patterns.size()) {
-                if (ix + h->coll_preds.size() + h->in_string_lists >= kLikeMaxPatterns) {  // (the bits of a table entry: LIKE patterns from bit 0 up, IN lists above them, collection predicates from bit 7 down)
-                    err.unsupported = true;
-                    err.msg = "more than " + std::to_string(kLikeMaxPatterns) + " distinct LIKE patterns, ANY / EVERY predicates and IN lists of strings in one plan";
-                    return false;
-                }
-                LikePattern lp;
-                if (!like_compile(pat->cstr.data(), pat->cstr.size(), lp)) {
-                    err.unsupported = true;
-                    err.msg = "LIKE pattern is not valid UTF-8 (the reference's regexp.Compile fails on it)";
-                    return false;
-                }
-                h->like_patterns.push_back(std::move(lp));
-            }
-            if (!push_term(TERM_LIKE, e->ch[0].get(), nullptr, nullptr)) return false;
+            const int ix = h->match.add_like(pat->cstr, err);
+            if (ix < 0 || !push_term(TERM_LIKE, e->ch[0].get(), nullptr, nullptr)) return false;
             Operand& b = P.terms[P.nterms - 1].b;
             b.is_const = 1;
             b.ctag = T_STRING;
-            b.cpayload = ix;  // (pad stays 0: not a dictionary string, bind_columns leaves it alone)
+            b.cpayload = (uint64_t)ix;
             return true;
         }
         case EK::Coll: {
-            // The predicate is compiled once per plan and evaluated once per distinct array (ensure_like); the row test reads
-            // its bit.  Two terms with the same text — the binding expression included — share a bit.
-            size_t ix = 0;
-            while (ix < h->coll_preds.size() && h->coll_preds[ix].text != e->text) ix++;
-            if (ix == h->coll_preds.size()) {
-                if (ix + h->like_patterns.size() + h->in_string_lists >= kLikeMaxPatterns) {
-                    err.unsupported = true;
-                    err.msg = "more than " + std::to_string(kLikeMaxPatterns) + " distinct LIKE patterns, ANY / EVERY predicates and IN lists of strings in one plan";
-                    return false;
-                }
-                CollPred cp;
-                cp.text = e->text;
-                if (!coll_compile(e, cp.prog, err)) return false;
-                h->coll_preds.push_back(std::move(cp));
-            }
-            if (!push_term(TERM_COLL, e->ch[0].get(), nullptr, nullptr)) return false;
+            const int ix = h->match.add_coll(e, err);
+            if (ix < 0 || !push_term(TERM_COLL, e->ch[0].get(), nullptr, nullptr)) return false;
             Operand& b = P.terms[P.nterms - 1].b;
             b.is_const = 1;
             b.ctag = T_ARRAY;
-            b.cpayload = kLikeMaxPatterns - 1 - ix;  // (pad stays 0: not a dictionary string)
+            b.cpayload = (uint64_t)ix;
             return true;
         }
         case EK::In: {
-            // The list is taken apart once per plan (in_compile): its strings become one more predicate of the match table,
-            // its numbers a range of the plan's sorted constants, the rest flags.  Two terms with the same list text share all of it.
-            size_t ix = 0;
-            while (ix < h->in_lists.size() && h->in_lists[ix].text != e->text) ix++;
-            if (ix == h->in_lists.size()) {
-                InList il;
-                if (!in_compile(e, il, err)) return false;
-                if (!il.strings.empty() && h->like_patterns.size() + h->coll_preds.size() + h->in_string_lists >= kLikeMaxPatterns) {
-                    err.unsupported = true;
-                    err.msg = "more than " + std::to_string(kLikeMaxPatterns) + " distinct LIKE patterns, ANY / EVERY predicates and IN lists of strings in one plan";
-                    return false;
-                }
-                if (h->in_numbers.size() + il.numbers.size() > kInMaxNumbers) {
-                    err.unsupported = true;
-                    err.msg = "more than " + std::to_string(kInMaxNumbers) + " distinct number constants in the IN lists of one plan";
-                    return false;
-                }
-                il.num_begin = (uint32_t)h->in_numbers.size();
-                h->in_numbers.insert(h->in_numbers.end(), il.numbers.begin(), il.numbers.end());
-                il.num_end = (uint32_t)h->in_numbers.size();
-                if (!il.strings.empty()) h->in_string_lists++;
-                h->in_lists.push_back(std::move(il));
-            }
-            if (!push_term(TERM_IN, e->ch[0].get(), nullptr, nullptr)) return false;
+            // (in_compile takes the list apart: its strings are a predicate of the match table, its numbers a range of the
+            //  plan's sorted constants — c.cpayload —, the rest flags)
+            const int ix = h->match.add_in(e, err);
+            if (ix < 0 || !push_term(TERM_IN, e->ch[0].get(), nullptr, nullptr)) return false;
+            const InList& l = h->match.lists[(size_t)ix];
             Term& t = P.terms[P.nterms - 1];
             t.b.is_const = t.c.is_const = 1;
-            t.b.ctag = t.c.ctag = T_ARRAY;  // (pad stays 0: not dictionary strings)
-            t.b.cpayload = ix;              // the list's index; compile_plan puts its mask and flags here once every bit is known
-            t.c.cpayload = (uint64_t)h->in_lists[ix].num_begin | (uint64_t)h->in_lists[ix].num_end << 32;
+            t.b.ctag = t.c.ctag = T_ARRAY;
+            t.b.cpayload = (uint64_t)ix;
+            t.c.cpayload = (uint64_t)l.num_begin | (uint64_t)l.num_end << 32;
             return true;
         }
         case EK::IsNull: return push_term(TERM_IS_NULL, e->ch[0].get(), nullptr, nullptr);
@@ -315,29 +271,14 @@ bool compile_plan(n1k_handle* h, PlanError& err) {
     memset(&P, 0, sizeof P);
     h->derived.clear();
     h->const_strings.clear();
-    h->like_patterns.clear();
-    h->coll_preds.clear();
-    h->in_lists.clear();
-    h->in_numbers.clear();
-    h->in_string_lists = 0;
+    h->match.clear_plan();
     const ParsedPlan& pl = h->plan;
     if (pl.paths.size() > (size_t)kMaxCols) { err.unsupported = true; err.msg = "more than 16 leaf paths"; return false; }
     if (pl.keys.size() > (size_t)kMaxKeys) { err.unsupported = true; err.msg = "more than 4 group keys"; return false; }
     if (pl.aggs.size() > (size_t)kMaxAggs) { err.unsupported = true; err.msg = "more than 8 aggregates"; return false; }
     P.ncols = (uint32_t)pl.paths.size();
     if (pl.condition && !compile_cond(h, pl.condition.get(), err)) return false;
-    // IN lists that hold strings take the bits above the LIKE patterns', in the order of their first use
-    uint32_t in_bit = (uint32_t)h->like_patterns.size();
-    for (InList& l : h->in_lists)
-        if (!l.strings.empty()) l.mask = (uint8_t)(1u << in_bit++);
-    for (uint32_t t = 0; t < P.nterms; t++)
-        if (P.terms[t].op == TERM_IN) {
-            const InList& l = h->in_lists[(size_t)P.terms[t].b.cpayload];
-            P.terms[t].b.cpayload = l.mask | (l.has_true ? IN_HAS_TRUE : 0u) | (l.has_false ? IN_HAS_FALSE : 0u) | (l.has_null ? IN_HAS_NULL : 0u) |
-                                    (l.empty ? IN_EMPTY : 0u);
-        }
-    in_build_table(h->in_lists, h->in_table);
-    h->in_uploaded = false;
+    h->match.finalize_bits(P);
     P.nkeys = (uint32_t)pl.keys.size();
     for (uint32_t k = 0; k < P.nkeys; k++)
         if (!to_operand(h, pl.keys[k].get(), P.keys[k].src, err)) return false;
@@ -758,10 +699,7 @@ static void destroy_handle(n1k_handle* h) {
         if (h->ev_q0) (void)hipEventDestroy(h->ev_q0);
         if (h->ev_q1) (void)hipEventDestroy(h->ev_q1);
         h->d_rank.release();
-        h->d_like.release();
-        h->match_scratch.release();
-        h->d_in_table.release();
-        h->d_in_nums.release();
+        h->match.release();
         h->d_keys.release();
         h->d_acc.release();
         h->d_rep.release();
@@ -1257,9 +1195,9 @@ n1k_status n1k_jit_check(n1k_handle* h, const uint32_t* col_kinds, uint32_t ncol
 n1k_status n1k_like_stats(const n1k_handle* h, uint64_t out[4]) {
     return guarded(h, [&]() -> n1k_status {
     if (!h || !out) return N1K_INVALID;
-    out[0] = h->like_on_device;
-    out[1] = h->like_on_host;
-    out[2] = h->like_patterns.size();
+    out[0] = h->match.counts[MK_LIKE].dev;
+    out[1] = h->match.counts[MK_LIKE].host;
+    out[2] = h->match.patterns.size();
     out[3] = kLikeDeviceThreshold;
     return N1K_OK;
     });
@@ -1268,9 +1206,9 @@ n1k_status n1k_like_stats(const n1k_handle* h, uint64_t out[4]) {
 n1k_status n1k_coll_stats(const n1k_handle* h, uint64_t out[4]) {
     return guarded(h, [&]() -> n1k_status {
     if (!h || !out) return N1K_INVALID;
-    out[0] = h->coll_on_device;
-    out[1] = h->coll_on_host;
-    out[2] = h->coll_preds.size();
+    out[0] = h->match.counts[MK_COLL].dev;
+    out[1] = h->match.counts[MK_COLL].host;
+    out[2] = h->match.preds.size();
     out[3] = kCollDeviceThreshold;
     return N1K_OK;
     });
@@ -1279,9 +1217,9 @@ n1k_status n1k_coll_stats(const n1k_handle* h, uint64_t out[4]) {
 n1k_status n1k_in_stats(const n1k_handle* h, uint64_t out[4]) {
     return guarded(h, [&]() -> n1k_status {
     if (!h || !out) return N1K_INVALID;
-    out[0] = h->in_lists.size();
-    out[1] = h->in_on_device;
-    out[2] = h->in_on_host;
+    out[0] = h->match.lists.size();
+    out[1] = h->match.counts[MK_IN].dev;
+    out[2] = h->match.counts[MK_IN].host;
     out[3] = kInDeviceThreshold;
     return N1K_OK;
     });

@@ -61,12 +61,12 @@ struct DevBuf {
     }
 };
 
-// device scratch of the match table's device route (n1k_matchtable.cpp)
+// device scratch of the match table's device route (n1k_matchtable.cpp), kept from one extension of the table to the next
 struct MatchScratch {
     DevBuf<uint8_t> bytes;   // the block's bytes
     DevBuf<uint64_t> off;    // its n + 1 offsets
-    DevBuf<uint8_t> left;    // 3n: the LIKE kernel's left-to-host flags, then the ANY / EVERY kernel's, then the IN kernel's
-    DevBuf<uint8_t> bits;    // 3n: the LIKE kernel's bits where they do not go straight into the table, then the ANY / EVERY kernel's, then the IN kernel's
+    DevBuf<uint8_t> left;    // MK_COUNT * n: the kernels' left-to-host flags, kind k at k * n
+    DevBuf<uint8_t> bits;    // MK_COUNT * n: the kernels' bits where they do not go straight into the table, kind k at k * n
     DevBuf<uint8_t> progs;   // CollProg[]
     void release() {
         bytes.release();
@@ -76,6 +76,57 @@ struct MatchScratch {
         progs.release();
     }
 };
+
+// the kinds of predicate that own bits of a match-table entry
+enum MatchKind { MK_LIKE, MK_COLL, MK_IN, MK_COUNT };
+
+// The match table ("The match table"): one byte per dictionary code, a predicate evaluated once per distinct
+// entry, one bit per row in the scan.  The plan's compiled predicates of the three kinds, the constants of its IN lists and
+// the table in device memory: built before the first launch that needs it and EXTENDED when the dictionary has grown
+// (ensure_match_table), kept across n1k_reset, freed with the handle.
+struct MatchTable {
+    std::vector<LikePattern> patterns;  // distinct LIKE patterns: pattern p owns bit p
+    std::vector<CollPred> preds;        // distinct ANY / EVERY predicates: predicate q owns bit coll_top - q
+    std::vector<InList> lists;          // distinct IN lists; those that hold strings own the bits above the patterns', in order of first use
+    uint32_t string_lists = 0;          // lists that hold strings
+    uint32_t coll_top = kMatchBits - 1; // (the diagnostic entry points evaluate one predicate into bit 0)
+    std::vector<double> in_numbers;     // the numbers of all lists, list by list (Program::in_nums)
+    InTableHost in_table;               // the strings of all lists in one open-addressed table
+    DevBuf<uint8_t> d_in_table;         // both device copies are made before the first launch (upload_in_constants)
+    DevBuf<double> d_in_nums;
+    bool in_uploaded = false;
+    DevBuf<uint8_t> d_bits;             // the table (+ 4 spare bytes: the kernels that stage it in LDS copy whole words)
+    size_t built_for = 0;               // dictionary codes it covers
+    MatchScratch scratch;
+    struct { uint64_t dev = 0, host = 0; } counts[MK_COUNT];  // entries evaluated by the kind's kernel / by its host matcher
+
+    // plan side (n1k_matchtable.cpp): find the predicate by its text or compile and append it; the index, or -1 and err
+    int add_like(const std::string& pattern, PlanError& err);
+    int add_coll(const Expr* e, PlanError& err);
+    int add_in(const Expr* e, PlanError& err);
+    void finalize_bits(Program& P);  // once the condition is compiled: the bit of every predicate, into the terms that read them
+    void clear_plan() {
+        patterns.clear();
+        preds.clear();
+        lists.clear();
+        in_numbers.clear();
+        string_lists = 0;
+    }
+    void release() {
+        d_bits.release();
+        scratch.release();
+        d_in_table.release();
+        d_in_nums.release();
+    }
+};
+
+// LDS the kernels of a bounded shape carry for the staged match table: kMatchLdsBytes when some term reads the table (n1k_spec.h:
+// present by shape, whatever the table's size), else none
+inline uint32_t match_lds_bytes(const FastArgs& F) {
+    for (uint32_t t = 0; t < F.nterms; t++)
+        if (term_is_table_bit(F.terms[t].op)) return kMatchLdsBytes;
+    return 0;
+}
 
 inline uint64_t next_pow2(uint64_t x) {
     uint64_t p = 1;
@@ -201,30 +252,7 @@ struct n1k_handle {
     size_t rank_built_for = (size_t)-1;
     DevBuf<uint32_t> d_rank;
 
-    // LIKE: the plan's distinct patterns and the match table — one byte per dictionary code, bit p = pattern p matches.
-    // Built before the first launch that needs it and EXTENDED when the dictionary has grown (ensure_like); kept across
-    // n1k_reset, freed with the handle.
-    std::vector<LikePattern> like_patterns;
-    DevBuf<uint8_t> d_like;
-    size_t like_built_for = 0;                // dictionary codes the table covers
-    uint64_t like_on_device = 0, like_on_host = 0;  // strings matched by like_match_kernel / by the host matcher
-    // ANY / EVERY: the plan's distinct collection predicates.  Predicate q owns bit 7 - q of the same table (LIKE pattern p
-    // owns bit p; together at most 8), evaluated for the entries that are array text by the same ensure_like.
-    std::vector<CollPred> coll_preds;
-    uint64_t coll_on_device = 0, coll_on_host = 0;  // arrays evaluated by coll_match_kernel / by the host evaluator
-    MatchScratch match_scratch;                     // kept from one extension of the table to the next
-    // IN: the plan's distinct constant lists.  A list that holds strings owns one more bit of the same table (above the LIKE
-    // patterns' bits: pattern count + its index among such lists; all three kinds together at most 8); the strings of all
-    // lists lie in one open-addressed table (host copy and device copy), the numbers of all lists in one array.  Both
-    // device copies are made by the first ensure_like and freed with the handle.
-    std::vector<InList> in_lists;
-    std::vector<double> in_numbers;
-    uint32_t in_string_lists = 0;
-    InTableHost in_table;
-    DevBuf<uint8_t> d_in_table;
-    DevBuf<double> d_in_nums;
-    bool in_uploaded = false;
-    uint64_t in_on_device = 0, in_on_host = 0;  // strings matched by in_match_kernel / by the host matcher
+    MatchTable match;  // LIKE, ANY / EVERY, IN: the plan's predicates over dictionary entries and their table
 
     // compiled program (column pointers are patched per batch)
     Program prog{};
@@ -345,8 +373,8 @@ n1k_status validate_batch(n1k_handle* h, const n1k_batch* b);
 uint64_t batch_bytes_per_row(const n1k_handle* h);
 void default_value(const AggDef& d, n1k_value& v, n1k_partial& p);
 
-// n1k_matchtable.cpp: the LIKE / ANY / EVERY match table, built and extended before the launches that read it
-n1k_status ensure_like(n1k_handle* h);
+// n1k_matchtable.cpp: the match table of the LIKE, ANY / EVERY and IN terms, built and extended before the launches that read it
+n1k_status ensure_match_table(n1k_handle* h);
 
 // n1k_scan.cpp: one batch through Filter + InitialGroup (kernel choice), Filter-only batches, staging of host batches
 bool build_fast_args(n1k_handle* h, uint32_t max_slots, FastArgs& F, bool fuse = false, bool partition_only = false);

@@ -28,8 +28,7 @@ static n1k_status run_partition(n1k_handle* h, const n1k_batch* b, PartArgs& A) 
         // what the staging needs in LDS (n1k_spec.h PartLds: 2048 rows x (9 B per TAGGED64 column, 4 B per DICT32 column, 1))
         size_t lds = 2048 + 2048 + 4096;  // (+ the per-destination tables of PartLds)
         for (uint32_t c = 0; c < F.ncols; c++) lds += 2048u * (F.cols[c].kind == COLK_DICT32 ? 4u : 9u);
-        for (uint32_t t = 0; t < F.nterms; t++)
-            if (term_is_table_bit(F.terms[t].op)) { lds += kLikeLdsBytes; break; }  // (the staged match table, present by shape)
+        lds += match_lds_bytes(F);
         if (lds <= 60 * 1024) {
             SpecSig sig = make_plan_sig(h, F);
             sig.mode = 1;
@@ -57,13 +56,11 @@ static n1k_status run_partition(n1k_handle* h, const n1k_batch* b, PartArgs& A) 
         const uint32_t pblock = wide && h->opt_part_block == 256 ? 256u : 512u;
         const uint64_t tiles = (n + pblock * 4 - 1) / (pblock * 4);
         uint32_t part_per_cu = h->opt_part_per_cu ? h->opt_part_per_cu : (pblock == 256 ? 6u : 2u);
-        for (uint32_t t = 0; t < F.nterms && !h->opt_part_per_cu; t++)
-            if (term_is_table_bit(F.terms[t].op)) {  // with the staged match table beside a tile's staging: as many workgroups as still fit a CU
-                size_t wg = 2048 + 2048 + 4096 + kLikeLdsBytes;
-                for (uint32_t c = 0; c < F.ncols; c++) wg += (size_t)pblock * 4u * (F.cols[c].kind == COLK_DICT32 ? 4u : 9u);
-                part_per_cu = std::max<uint32_t>(1u, std::min<uint32_t>(part_per_cu, (uint32_t)(160u * 1024u / wg)));
-                break;
-            }
+        if (match_lds_bytes(F) && !h->opt_part_per_cu) {  // with the staged match table beside a tile's staging: as many workgroups as still fit a CU
+            size_t wg = 2048 + 2048 + 4096 + kMatchLdsBytes;
+            for (uint32_t c = 0; c < F.ncols; c++) wg += (size_t)pblock * 4u * (F.cols[c].kind == COLK_DICT32 ? 4u : 9u);
+            part_per_cu = std::max<uint32_t>(1u, std::min<uint32_t>(part_per_cu, (uint32_t)(160u * 1024u / wg)));
+        }
         uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)h->num_cus * part_per_cu, tiles));
         // many tiles: every destination's region in kRowSubs sub-regions with their own counters, workgroups dealt round-robin
         // (tile t goes to sub-region t % kRowSubs: an even share of the rows whatever their order)
@@ -119,7 +116,7 @@ n1k_status n1k_partition_device_batch(n1k_handle* h, const n1k_batch* batch, uin
     }
     st = ensure_rank(h);
     if (st != N1K_OK) return st;
-    st = ensure_like(h);
+    st = ensure_match_table(h);
     if (st != N1K_OK) return st;
     A.nrows = batch->nrows;
     A.capacity = capacity_rows;
@@ -807,7 +804,7 @@ n1k_status exchange_rows_impl(n1k_comm* c, n1k_handle* sender, const n1k_batch* 
         if (s != N1K_OK) return s;
         s = ensure_rank(sender);
         if (s != N1K_OK) return s;
-        s = ensure_like(sender);
+        s = ensure_match_table(sender);
         if (s != N1K_OK) return s;
         PartArgs A{};
         A.nrows = batch->nrows;

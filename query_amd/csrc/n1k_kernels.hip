@@ -134,7 +134,7 @@ N1K_DEV void eval_term(const Program& P, const Term& t, const uint64_t (&row)[R]
 #pragma unroll
             for (int j = 0; j < R; j++) {
                 const uint32_t code = (uint32_t)pa[j];
-                const bool hit = ta[j] == want && code < P.like_n && (P.like_bits[code] & bit) != 0;
+                const bool hit = ta[j] == want && code < P.match_n && (P.match_bits[code] & bit) != 0;
                 out[j] = ta[j] == T_MISSING ? L_MISSING : (ta[j] != want ? L_NULL : (hit ? L_TRUE : L_FALSE));
             }
             break;
@@ -146,7 +146,7 @@ N1K_DEV void eval_term(const Program& P, const Term& t, const uint64_t (&row)[R]
 #pragma unroll
             for (int j = 0; j < R; j++) {
                 const uint32_t code = (uint32_t)pa[j];
-                const bool str_hit = ta[j] == T_STRING && mask && code < P.like_n && (P.like_bits[code] & mask) != 0;
+                const bool str_hit = ta[j] == T_STRING && mask && code < P.match_n && (P.match_bits[code] & mask) != 0;
                 out[j] = in_term_l(flags, P.in_nums + begin, end - begin, ta[j], pa[j], str_hit);
             }
             break;
@@ -1015,16 +1015,16 @@ N1K_DEV bool fast_term_true(const FastTerm& t, uint32_t tg, uint64_t p, const ui
         case TERM_STR_EQ: return tg == T_STRING && p == t.cpayload;
         case TERM_LIKE:
         case TERM_COLL: {
-            if (tg != term_table_tag(t.op) || (uint32_t)p >= t.like_n) return false;
-            const uint8_t b = like_lds ? like_lds[(uint32_t)p] : t.like_bits[(uint32_t)p];
-            return (b & t.like_bit) != 0;
+            if (tg != term_table_tag(t.op) || (uint32_t)p >= t.match_n) return false;
+            const uint8_t b = like_lds ? like_lds[(uint32_t)p] : t.match_bits[(uint32_t)p];
+            return (b & t.match_mask) != 0;
         }
         case TERM_IN: {  // TRUE exactly when the value equals a constant of the list
             if (tg == T_INT || tg == T_FLOAT) return in_num_hit(t.in_nums, t.in_n, tg, p);
-            if (tg != T_STRING) return tg == T_TRUE ? (t.like_bit & IN_HAS_TRUE) != 0 : (tg == T_FALSE && (t.like_bit & IN_HAS_FALSE) != 0);
-            if (!(t.like_bit & 0xFFu) || (uint32_t)p >= t.like_n) return false;
-            const uint8_t b = like_lds ? like_lds[(uint32_t)p] : t.like_bits[(uint32_t)p];
-            return (b & t.like_bit & 0xFFu) != 0;
+            if (tg != T_STRING) return tg == T_TRUE ? (t.match_mask & IN_HAS_TRUE) != 0 : (tg == T_FALSE && (t.match_mask & IN_HAS_FALSE) != 0);
+            if (!(t.match_mask & 0xFFu) || (uint32_t)p >= t.match_n) return false;
+            const uint8_t b = like_lds ? like_lds[(uint32_t)p] : t.match_bits[(uint32_t)p];
+            return (b & t.match_mask & 0xFFu) != 0;
         }
         default: {
             if (tg <= T_NULL) return false;  // MISSING / NULL are never TRUE
@@ -1065,14 +1065,14 @@ __global__ __launch_bounds__(BLOCK) void scan_fast_kernel(const Program P, const
     const uint32_t S = F.lds_slots;
     const uint32_t tid = threadIdx.x;
     lds_table_init<BLOCK>(P, lds, S, tid);
-    // LIKE, ANY / EVERY: a match table of at most kLikeLdsBytes entries sits behind the workgroup's table (launch_scan_fast sized it)
+    // LIKE, ANY / EVERY: a match table of at most kMatchLdsBytes entries sits behind the workgroup's table (launch_scan_fast sized it)
     const uint8_t* like_lds = nullptr;
 #pragma unroll
     for (int t = 0; t < kFastTerms; t++) {
-        if (t < (int)F.nterms && term_is_table_bit(F.terms[t].op) && F.terms[t].like_n <= kLikeLdsBytes && !like_lds) {
+        if (t < (int)F.nterms && term_is_table_bit(F.terms[t].op) && F.terms[t].match_n <= kMatchLdsBytes && !like_lds) {
             uint32_t* words = (uint32_t*)(lds + (size_t)S * P.lds_words);
-            const uint32_t* src = (const uint32_t*)F.terms[t].like_bits;
-            for (uint32_t k = tid; k < (F.terms[t].like_n + 3u) / 4u; k += BLOCK) words[k] = src[k];
+            const uint32_t* src = (const uint32_t*)F.terms[t].match_bits;
+            for (uint32_t k = tid; k < (F.terms[t].match_n + 3u) / 4u; k += BLOCK) words[k] = src[k];
             like_lds = (const uint8_t*)words;
         }
     }
@@ -2968,8 +2968,8 @@ hipError_t launch_scan_fast(const Program& P, const FastArgs& F, const GlobalTab
                             uint32_t grid, uint32_t block, uint32_t rows_per_lane, hipStream_t st) {
     size_t shmem = (size_t)F.lds_slots * P.lds_words * 8;
     for (uint32_t t = 0; t < F.nterms; t++)
-        if (term_is_table_bit(F.terms[t].op) && F.terms[t].like_n <= kLikeLdsBytes) {  // room for the staged match table
-            shmem += kLikeLdsBytes;
+        if (term_is_table_bit(F.terms[t].op) && F.terms[t].match_n <= kMatchLdsBytes) {  // room for the staged match table
+            shmem += kMatchLdsBytes;
             break;
         }
     if (block == 512) {

@@ -110,13 +110,13 @@ void like_match_block_host(const std::vector<LikePattern>& pats, uint64_t n, con
             for (size_t p = 0; p < pats.size(); p++)
                 b |= (uint8_t)(like_match(pats[p].prog.data(), (uint32_t)pats[p].prog.size(), pats[p].anchor_end, LikeRunes{r.data(), (uint32_t)r.size()}) ? 1u << p : 0u);
         }
-        bits[i] = b;
+        bits[i] |= b;
     }
 }
 
 bool like_dev_patterns(const std::vector<LikePattern>& pats, LikeDevPatterns& out) {
     memset(&out, 0, sizeof out);
-    if (pats.size() > kLikeMaxPatterns) return false;
+    if (pats.size() > kMatchBits) return false;
     out.npat = (uint32_t)pats.size();
     for (size_t p = 0; p < pats.size(); p++) {
         if (pats[p].prog.size() > kLikeDevProgBytes) return false;

@@ -29,7 +29,8 @@ namespace n1k {
 
 enum : uint8_t { LIKE_OP_MANY = 0, LIKE_OP_ONE = 1, LIKE_OP_LIT = 2 };
 
-constexpr uint32_t kLikeMaxPatterns = 8;     // one byte per dictionary code carries every pattern of a plan
+constexpr uint32_t kMatchBits = 8;          // bits of a match-table entry: one byte per dictionary code carries every LIKE pattern,
+                                            // ANY / EVERY predicate and IN list of strings of a plan ("The match table")
 constexpr uint32_t kLikeDevProgBytes = 240;  // a longer program stays with the host matcher
 constexpr uint32_t kLikeDevMaxLen = 128;     // bytes of a dictionary string the device kernel takes
 // New dictionary entries below this count are matched on the host and copied; from it on they go through
@@ -150,9 +151,9 @@ N1K_HD bool like_match(const uint8_t* prog, uint32_t plen, bool anchor_end, cons
 // the patterns of one plan as the device kernel takes them (a kernel argument)
 struct LikeDevPatterns {
     uint32_t npat;
-    uint8_t plen[kLikeMaxPatterns];
-    uint8_t anchor_end[kLikeMaxPatterns];
-    uint8_t prog[kLikeMaxPatterns][kLikeDevProgBytes];
+    uint8_t plen[kMatchBits];
+    uint8_t anchor_end[kMatchBits];
+    uint8_t prog[kMatchBits][kLikeDevProgBytes];
 };
 
 // a block of dictionary entries as the match table's kernels take it (n1k_matchtable.hip), whatever they evaluate
@@ -168,6 +169,7 @@ struct LikeKernelArgs {
     EntryBlockArgs blk;   // out_bits: bit p = pattern p matches; left: longer than kLikeDevMaxLen, or not valid UTF-8
     LikeDevPatterns pat;
 };
+static_assert(sizeof(EntryBlockArgs) == 40 && sizeof(LikeDevPatterns) == 1940 && sizeof(LikeKernelArgs) == 1984, "kernel argument layout");
 
 }  // namespace n1k
 
@@ -188,7 +190,7 @@ struct LikePattern {
 bool like_compile(const char* pattern, size_t len, LikePattern& out);
 // one string against one pattern, any bytes (the host matcher: invalid UTF-8 decodes byte by byte, as Go does)
 bool like_match_host(const LikePattern& p, const uint8_t* s, size_t n);
-// bits[i] = OR over patterns p of (match << p), for the n strings bytes[offsets[i] - offsets[0] ..)
+// bits[i] |= OR over patterns p of (match << p), for the n strings bytes[offsets[i] - offsets[0] ..)
 void like_match_block_host(const std::vector<LikePattern>& pats, uint64_t n, const uint64_t* offsets, const uint8_t* bytes, uint8_t* bits);
 // false: some pattern's program is longer than the device kernel takes
 bool like_dev_patterns(const std::vector<LikePattern>& pats, LikeDevPatterns& out);

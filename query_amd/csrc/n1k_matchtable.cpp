@@ -1,11 +1,88 @@
-// n1k_matchtable.cpp — the match table on the host side: like_bits[code] bit p = LIKE pattern p matches dictionary entry
-// `code`, bit 7 - q = collection predicate q holds for it, the bits between = the IN lists that hold it.  One driver for
-// "evaluate a block of entries on the device" (match_block_device), the handle's table around it (ensure_like) and the six
-// diagnostic entry points of the C ABI.
+// n1k_matchtable.cpp — the match table on the host side ("The match table"): the plan's predicates and their
+// bits (MatchTable's adders, finalize_bits), ONE driver that takes a block of dictionary entries through every kind's
+// route (match_block), the handle's table around it (ensure_match_table) and the diagnostic entry points of the C ABI.
 #include "n1k_engine.h"
 
 using namespace n1k;
 using namespace n1k_eng;
+
+// ---- the plan side: which predicate owns which bit
+
+namespace n1k_eng {
+
+// The eight bits of an entry are shared by the three kinds: one more predicate that needs a bit, or refused.
+static bool take_bit(const MatchTable& M, PlanError& err) {
+    if (M.patterns.size() + M.preds.size() + M.string_lists < kMatchBits) return true;
+    err.unsupported = true;
+    err.msg = "more than " + std::to_string(kMatchBits) + " distinct LIKE patterns, ANY / EVERY predicates and IN lists of strings in one plan";
+    return false;
+}
+
+int MatchTable::add_like(const std::string& pattern, PlanError& err) {
+    for (size_t ix = 0; ix < patterns.size(); ix++)
+        if (patterns[ix].text == pattern) return (int)ix;
+    if (!take_bit(*this, err)) return -1;
+    LikePattern lp;
+    if (!like_compile(pattern.data(), pattern.size(), lp)) {
+        err.unsupported = true;
+        err.msg = "LIKE pattern is not valid UTF-8 (the reference's regexp.Compile fails on it)";
+        return -1;
+    }
+    patterns.push_back(std::move(lp));
+    return (int)patterns.size() - 1;
+}
+
+int MatchTable::add_coll(const Expr* e, PlanError& err) {  // (the text holds the binding expression too)
+    for (size_t ix = 0; ix < preds.size(); ix++)
+        if (preds[ix].text == e->text) return (int)ix;
+    if (!take_bit(*this, err)) return -1;
+    CollPred cp;
+    cp.text = e->text;
+    if (!coll_compile(e, cp.prog, err)) return -1;
+    preds.push_back(std::move(cp));
+    return (int)preds.size() - 1;
+}
+
+int MatchTable::add_in(const Expr* e, PlanError& err) {
+    for (size_t ix = 0; ix < lists.size(); ix++)
+        if (lists[ix].text == e->text) return (int)ix;
+    InList il;
+    if (!in_compile(e, il, err)) return -1;
+    if (!il.strings.empty() && !take_bit(*this, err)) return -1;  // (a list without strings takes no bit)
+    if (in_numbers.size() + il.numbers.size() > kInMaxNumbers) {
+        err.unsupported = true;
+        err.msg = "more than " + std::to_string(kInMaxNumbers) + " distinct number constants in the IN lists of one plan";
+        return -1;
+    }
+    il.num_begin = (uint32_t)in_numbers.size();
+    in_numbers.insert(in_numbers.end(), il.numbers.begin(), il.numbers.end());
+    il.num_end = (uint32_t)in_numbers.size();
+    if (!il.strings.empty()) string_lists++;
+    lists.push_back(std::move(il));
+    return (int)lists.size() - 1;
+}
+
+// THE bit scheme: LIKE pattern p owns bit p; the IN lists that hold strings own the next bits above, in the order of their
+// first use; collection predicate q owns bit coll_top - q, from bit 7 down.  A TERM_IN carries its list's flags beside the mask.
+void MatchTable::finalize_bits(Program& P) {
+    uint32_t in_bit = (uint32_t)patterns.size();
+    for (InList& l : lists)
+        if (!l.strings.empty()) l.mask = (uint8_t)(1u << in_bit++);
+    for (uint32_t t = 0; t < P.nterms; t++) {
+        uint64_t& ix = P.terms[t].b.cpayload;  // the predicate's index (compile_cond) -> what the row test reads
+        if (P.terms[t].op == TERM_COLL) ix = coll_top - ix;
+        if (P.terms[t].op == TERM_IN) {
+            const InList& l = lists[(size_t)ix];
+            ix = l.mask | (l.has_true ? IN_HAS_TRUE : 0u) | (l.has_false ? IN_HAS_FALSE : 0u) | (l.has_null ? IN_HAS_NULL : 0u) | (l.empty ? IN_EMPTY : 0u);
+        }
+    }
+    in_build_table(lists, in_table);
+    in_uploaded = false;
+}
+
+}  // namespace n1k_eng
+
+// ---- the driver
 
 namespace {
 
@@ -16,109 +93,150 @@ struct EntryBlock {
     const uint8_t* at(uint64_t i) const { return bytes + (off[i] - off[0]); }
 };
 
-struct MatchCounts {
-    uint64_t like_dev = 0, like_host = 0;  // strings matched by like_match_kernel / by the host matcher
-    uint64_t coll_dev = 0, coll_host = 0;  // arrays evaluated by coll_match_kernel / by the host evaluator
-    uint64_t in_dev = 0, in_host = 0;      // strings looked up by in_match_kernel / by the host matcher
-};
-
-uint64_t count_array_text(const EntryBlock& B) {
-    uint64_t k = 0;
-    for (uint64_t i = 0; i < B.n; i++) k += coll_array_text(B.at(i), B.off[i + 1] - B.off[i]);
-    return k;
-}
-
 #define HIP_RET(expr)                      \
     do {                                   \
         const hipError_t _e = (expr);      \
         if (_e != hipSuccess) return _e;   \
     } while (0)
 
-// The block through the kernels: `like` (its patterns filled in by like_dev_patterns; nullptr: no LIKE here), `coll`
-// (nullptr: no ANY / EVERY here) and / or `in` (its table in device memory, `in_host` the same table on the host; nullptr:
-// no IN here), ONE upload, one launch per kind, one synchronisation; what a kernel left goes through the
-// host matchers.  The final bytes land at d_dst (device; nullptr: nowhere) and, whenever the host came to hold them, in
-// bits[0, n) — always with d_dst == nullptr.  LIKE alone writes d_dst from the kernel, and the bytes come back only when
-// some string was left; ANY / EVERY and IN (alone or beside LIKE) are merged on the host and written once.
-hipError_t match_block_device(MatchScratch& S, const EntryBlock& B, LikeKernelArgs* like, const std::vector<LikePattern>& pats,
-                              const std::vector<CollPred>* coll, uint32_t first_bit, InKernelArgs* in, const InTable* in_host,
-                              hipStream_t st, uint8_t* d_dst, uint8_t* bits, MatchCounts& c) {
-    const uint64_t n = B.n, nbytes = B.off[n] - B.off[0];
-    HIP_RET(hipStreamSynchronize(st));  // (the scratch buffers may still be read by the last extension)
-    HIP_RET(S.bytes.ensure(nbytes + 16));
-    HIP_RET(S.off.ensure(n + 1));
-    HIP_RET(S.left.ensure(3 * n));
-    if (coll || in || !d_dst) HIP_RET(S.bits.ensure(3 * n));
-    if (nbytes) HIP_RET(hipMemcpy(S.bytes.p, B.bytes, nbytes, hipMemcpyHostToDevice));
-    HIP_RET(hipMemcpy(S.off.p, B.off, (n + 1) * 8, hipMemcpyHostToDevice));
-    if (coll) {
-        HIP_RET(S.progs.ensure(coll->size() * sizeof(CollProg)));
-        for (size_t q = 0; q < coll->size(); q++)
-            HIP_RET(hipMemcpy(S.progs.p + q * sizeof(CollProg), &(*coll)[q].prog, sizeof(CollProg), hipMemcpyHostToDevice));
+// where each kind of one block goes; like: the LIKE kernel's arguments, its patterns filled in when LIKE goes to the device
+enum Route : uint8_t { R_NONE, R_HOST, R_DEVICE };
+struct Routes {
+    Route r[MK_COUNT];
+    uint32_t ndev = 0, nhost = 0;
+    LikeKernelArgs like{};
+};
+
+// What a kind tells the driver: whether the plan holds it, ...
+bool kind_present(const MatchTable& M, int k) {
+    switch (k) {
+        case MK_LIKE: return !M.patterns.empty();
+        case MK_COLL: return !M.preds.empty();
+        default: return M.string_lists != 0;
     }
-    const EntryBlockArgs blk{S.bytes.p, S.off.p, (uint32_t)n, 0, nullptr, nullptr};
-    uint8_t* const d_like_bits = d_dst ? d_dst : S.bits.p;
-    const bool merge = coll || in;                         // kinds whose bits the host merges and writes once
-    const bool like_bits_up = like && (merge || !d_dst);  // the host merges or returns them: read with the flags
-    if (like) {
-        like->blk = blk;
-        like->blk.out_bits = d_like_bits;
-        like->blk.out_left = S.left.p;
-        HIP_RET(launch_like_match(*like, st));
+}
+
+// ... how many of a block's entries are its business (what its two counters add up to), ...
+uint64_t kind_business(int k, const EntryBlock& B) {
+    if (k != MK_COLL) return B.n;
+    uint64_t narr = 0;
+    for (uint64_t i = 0; i < B.n; i++) narr += coll_array_text(B.at(i), B.off[i + 1] - B.off[i]);
+    return narr;
+}
+
+// ... its host matcher over entries [0, n) of (off, bytes) — every one ORs its bits into bits[i], none assumes a zeroed
+// destination — ...
+void kind_host(const MatchTable& M, int k, uint64_t n, const uint64_t* off, const uint8_t* bytes, uint8_t* bits) {
+    switch (k) {
+        case MK_LIKE: like_match_block_host(M.patterns, n, off, bytes, bits); break;
+        case MK_COLL: coll_eval_block_host(M.preds, M.coll_top, n, off, bytes, bits); break;
+        default: in_match_block_host(M.in_table.view(), n, off, bytes, bits);
     }
-    std::vector<uint8_t> left(3 * n), cb(coll ? n : 0), ib(in ? n : 0);
-    if (coll) {
-        CollKernelArgs C{blk, (uint32_t)coll->size(), first_bit, (const CollProg*)S.progs.p};
-        C.blk.out_bits = S.bits.p + n;
-        C.blk.out_left = S.left.p + n;
-        HIP_RET(launch_coll_match(C, st));
-        HIP_RET(hipMemcpyAsync(cb.data(), S.bits.p + n, n, hipMemcpyDeviceToHost, st));
+}
+
+// ... and its kernel over the uploaded block
+hipError_t kind_launch(MatchTable& M, Routes& R, int k, const EntryBlockArgs& blk, hipStream_t st) {
+    switch (k) {
+        case MK_LIKE: R.like.blk = blk; return launch_like_match(R.like, st);
+        case MK_COLL: return launch_coll_match(CollKernelArgs{blk, (uint32_t)M.preds.size(), M.coll_top, (const CollProg*)M.scratch.progs.p}, st);
+        default: return launch_in_match(InKernelArgs{blk, in_table_at(M.in_table, M.d_in_table.p)}, st);
     }
-    if (in) {
-        in->blk = blk;
-        in->blk.out_bits = S.bits.p + 2 * n;
-        in->blk.out_left = S.left.p + 2 * n;
-        HIP_RET(launch_in_match(*in, st));
-        HIP_RET(hipMemcpyAsync(ib.data(), S.bits.p + 2 * n, n, hipMemcpyDeviceToHost, st));
+}
+
+// A kind the plan holds goes to the device where the caller wants it there (the thresholds; the device flavour of a
+// diagnostic entry point) — LIKE only with programs its kernel takes — and to the host otherwise.
+void choose_routes(const MatchTable& M, const bool want_dev[MK_COUNT], Routes& R) {
+    for (int k = 0; k < MK_COUNT; k++) {
+        const bool dev = kind_present(M, k) && want_dev[k] && (k != MK_LIKE || like_dev_patterns(M.patterns, R.like.pat));
+        R.r[k] = dev ? R_DEVICE : (kind_present(M, k) ? R_HOST : R_NONE);
+        R.ndev += R.r[k] == R_DEVICE;
+        R.nhost += R.r[k] == R_HOST;
     }
-    const uint64_t lo = like ? 0 : (coll ? n : 2 * n), hi = in ? 3 * n : (coll ? 2 * n : n);  // the flags of the kinds that ran (and of one that did not, between two that did: never read)
-    HIP_RET(hipMemcpyAsync(left.data() + lo, S.left.p + lo, hi - lo, hipMemcpyDeviceToHost, st));
-    if (like_bits_up) HIP_RET(hipMemcpyAsync(bits, d_like_bits, n, hipMemcpyDeviceToHost, st));
+}
+
+// The constants of the plan's IN lists — the numbers the row term searches, the strings in_match_kernel probes — go to the
+// device once, before the first launch.
+hipError_t upload_in_constants(MatchTable& M, hipStream_t st) {
+    if (M.lists.empty() || M.in_uploaded) return hipSuccess;
     HIP_RET(hipStreamSynchronize(st));
-    uint64_t like_left = 0, coll_left = 0;
-    if (like) {
-        for (uint64_t i = 0; i < n; i++) like_left += left[i];
-        if (like_left && !like_bits_up) HIP_RET(hipMemcpy(bits, d_like_bits, n, hipMemcpyDeviceToHost));
-        for (uint64_t i = 0; i < n && like_left; i++)
-            if (left[i]) like_match_block_host(pats, 1, &B.off[i], B.at(i), &bits[i]);
-        c.like_dev += n - like_left;
-        c.like_host += like_left;
+    if (!M.in_numbers.empty()) {
+        HIP_RET(M.d_in_nums.ensure(M.in_numbers.size()));
+        HIP_RET(hipMemcpy(M.d_in_nums.p, M.in_numbers.data(), M.in_numbers.size() * sizeof(double), hipMemcpyHostToDevice));
     }
-    if (coll) {
-        for (uint64_t i = 0; i < n; i++) {
-            if (left[n + i]) {  // (the kernel wrote 0 for it)
-                coll_left++;
-                coll_eval_block_host(*coll, first_bit, 1, &B.off[i], B.at(i), &cb[i]);
-            }
-            bits[i] = (uint8_t)((like ? bits[i] : 0) | cb[i]);
+    if (M.string_lists) {
+        std::vector<uint8_t> blob;
+        in_table_blob(M.in_table, blob);
+        HIP_RET(M.d_in_table.ensure(blob.size()));
+        HIP_RET(hipMemcpy(M.d_in_table.p, blob.data(), blob.size(), hipMemcpyHostToDevice));
+    }
+    M.in_uploaded = true;
+    return hipSuccess;
+}
+
+// One block of entries through every kind's route.  The kinds on the device: ONE upload, one launch per kind, one
+// synchronisation; what a kernel flagged `left` (it wrote 0 for it) goes through that kind's host matcher one by one.  The
+// kinds on the host: their matchers over the whole block.  The final bytes land at d_dst (device memory; nullptr: nowhere)
+// and, unless the direct rule held and nothing was left, in bits[0, n).
+// The direct rule: exactly one kind on the device and none on the host — its kernel writes straight to d_dst, only its
+// flags come back, and the bytes are read back and patched only if some entry was left.  Otherwise the host merges the
+// kinds' bits and writes d_dst once.
+hipError_t match_block(MatchTable& M, const EntryBlock& B, Routes& R, hipStream_t st, uint8_t* d_dst, uint8_t* bits) {
+    MatchScratch& S = M.scratch;
+    const uint64_t n = B.n, nbytes = B.off[n] - B.off[0];
+    const bool direct = d_dst && R.ndev == 1 && R.nhost == 0;
+    std::vector<uint8_t> left, kbits;  // the kernels' flags and bits, kind k at k * n
+    if (R.ndev) {
+        HIP_RET(hipStreamSynchronize(st));  // (the scratch buffers may still be read by the last extension)
+        HIP_RET(S.bytes.ensure(nbytes + 16));
+        HIP_RET(S.off.ensure(n + 1));
+        HIP_RET(S.left.ensure(MK_COUNT * n));
+        if (!direct) HIP_RET(S.bits.ensure(MK_COUNT * n));
+        if (nbytes) HIP_RET(hipMemcpy(S.bytes.p, B.bytes, nbytes, hipMemcpyHostToDevice));
+        HIP_RET(hipMemcpy(S.off.p, B.off, (n + 1) * 8, hipMemcpyHostToDevice));
+        if (R.r[MK_COLL] == R_DEVICE) {
+            HIP_RET(S.progs.ensure(M.preds.size() * sizeof(CollProg)));
+            for (size_t q = 0; q < M.preds.size(); q++)
+                HIP_RET(hipMemcpy(S.progs.p + q * sizeof(CollProg), &M.preds[q].prog, sizeof(CollProg), hipMemcpyHostToDevice));
         }
-        const uint64_t narr = count_array_text(B);
-        c.coll_dev += narr - coll_left;
-        c.coll_host += coll_left;
-    }
-    if (in) {
-        uint64_t in_left = 0;
-        for (uint64_t i = 0; i < n; i++) {
-            if (left[2 * n + i]) {  // (the kernel wrote 0 for it)
-                in_left++;
-                in_match_block_host(*in_host, 1, &B.off[i], B.at(i), &ib[i]);
-            }
-            bits[i] = (uint8_t)((like || coll ? bits[i] : 0) | ib[i]);
+        left.resize(MK_COUNT * n);
+        kbits.resize(direct ? 0 : MK_COUNT * n);
+        for (int k = 0; k < MK_COUNT; k++)
+            if (R.r[k] == R_DEVICE)
+                HIP_RET(kind_launch(M, R, k, EntryBlockArgs{S.bytes.p, S.off.p, (uint32_t)n, 0, direct ? d_dst : S.bits.p + k * n, S.left.p + k * n}, st));
+        for (int k = 0; k < MK_COUNT; k++) {  // only the slices of the kinds that ran
+            if (R.r[k] != R_DEVICE) continue;
+            HIP_RET(hipMemcpyAsync(left.data() + k * n, S.left.p + k * n, n, hipMemcpyDeviceToHost, st));
+            if (!direct) HIP_RET(hipMemcpyAsync(kbits.data() + k * n, S.bits.p + k * n, n, hipMemcpyDeviceToHost, st));
         }
-        c.in_dev += n - in_left;
-        c.in_host += in_left;
+        HIP_RET(hipStreamSynchronize(st));
     }
-    if (d_dst && (merge || like_left)) HIP_RET(hipMemcpy(d_dst, bits, n, hipMemcpyHostToDevice));
+    uint64_t nleft[MK_COUNT] = {}, any_left = 0;
+    for (int k = 0; k < MK_COUNT; k++) {
+        if (R.r[k] != R_DEVICE) continue;
+        for (uint64_t i = 0; i < n; i++) nleft[k] += left[k * n + i];
+        any_left += nleft[k];
+    }
+    if (!direct) {
+        memset(bits, 0, n);
+        for (int k = 0; k < MK_COUNT; k++)
+            for (uint64_t i = 0; i < n && R.r[k] == R_DEVICE; i++) bits[i] |= kbits[k * n + i];
+    } else if (any_left) {
+        HIP_RET(hipMemcpy(bits, d_dst, n, hipMemcpyDeviceToHost));
+    }
+    for (int k = 0; k < MK_COUNT; k++) {
+        if (R.r[k] == R_NONE) continue;
+        const uint64_t business = kind_business(k, B);
+        if (R.r[k] == R_HOST) {
+            kind_host(M, k, n, B.off, B.bytes, bits);
+            M.counts[k].host += business;
+            continue;
+        }
+        for (uint64_t i = 0; i < n && nleft[k]; i++)
+            if (left[k * n + i]) kind_host(M, k, 1, &B.off[i], B.at(i), &bits[i]);
+        M.counts[k].dev += business - nleft[k];
+        M.counts[k].host += nleft[k];
+    }
+    if (d_dst && (!direct || any_left)) HIP_RET(hipMemcpy(d_dst, bits, n, hipMemcpyHostToDevice));
     return hipSuccess;
 }
 
@@ -128,105 +246,52 @@ namespace n1k_eng {
 
 // The handle's table.  Same rules as the rank table (ensure_rank), except that a grown dictionary EXTENDS it: the entries
 // of the old codes stay as they are (equal bytes, equal code), only the new codes are evaluated — per kind on the host
-// below kLikeDeviceThreshold / kCollDeviceThreshold / kInDeviceThreshold of them, by the kernels from there on (what a
-// kernel leaves goes through the host matchers either way; patterns whose programs the LIKE kernel does not take stay with
-// the host).  The constants of the plan's IN lists — the numbers the row term searches, the strings in_match_kernel
-// probes — go to the device once, here, before the first launch.
-n1k_status ensure_like(n1k_handle* h) {
+// below kLikeDeviceThreshold / kCollDeviceThreshold / kInDeviceThreshold of them, by the kernels from there on.
+n1k_status ensure_match_table(n1k_handle* h) {
     Program& P = h->prog;
-    const std::vector<LikePattern>& pats = h->like_patterns;
-    const std::vector<CollPred>& preds = h->coll_preds;
-    const bool in_strings = h->in_string_lists != 0;
-    InKernelArgs I{};
-    if (!h->in_lists.empty() && !h->in_uploaded) {
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        if (!h->in_numbers.empty()) {
-            HIP_TRY(h, h->d_in_nums.ensure(h->in_numbers.size()));
-            HIP_TRY(h, hipMemcpy(h->d_in_nums.p, h->in_numbers.data(), h->in_numbers.size() * sizeof(double), hipMemcpyHostToDevice));
-        }
-        if (in_strings) {
-            std::vector<uint8_t> blob;
-            in_table_blob(h->in_table, blob);
-            HIP_TRY(h, h->d_in_table.ensure(blob.size()));
-            HIP_TRY(h, hipMemcpy(h->d_in_table.p, blob.data(), blob.size(), hipMemcpyHostToDevice));
-        }
-        h->in_uploaded = true;
-    }
-    P.in_nums = h->in_numbers.empty() ? nullptr : h->d_in_nums.p;
-    P.in_n = (uint32_t)h->in_numbers.size();
-    if (pats.empty() && preds.empty() && !in_strings) {
-        P.like_bits = nullptr;
-        P.like_n = 0;
+    MatchTable& M = h->match;
+    HIP_TRY(h, upload_in_constants(M, h->stream));
+    P.in_nums = M.in_numbers.empty() ? nullptr : M.d_in_nums.p;  // (bound also when the plan holds no kind of the table)
+    P.in_n = (uint32_t)M.in_numbers.size();
+    if (M.patterns.empty() && M.preds.empty() && !M.string_lists) {
+        P.match_bits = nullptr;
+        P.match_n = 0;
         return N1K_OK;
     }
-    const size_t n = h->dict.size(), first = h->like_built_for;
+    const size_t n = h->dict.size(), first = M.built_for;
     if (n > first) {
-        if (n + 4 > h->d_like.n) {  // (4 spare bytes: the kernels that stage the table in LDS copy whole words)
+        if (n + 4 > M.d_bits.n) {  // (4 spare bytes: the kernels that stage the table in LDS copy whole words)
             // the table moves: launches in flight may still read the old allocation
             DevBuf<uint8_t> nb;
-            HIP_TRY(h, nb.ensure(std::max(n, h->d_like.n * 2) + 4));
+            HIP_TRY(h, nb.ensure(std::max(n, M.d_bits.n * 2) + 4));
             hipError_t e = hipStreamSynchronize(h->stream);
-            if (e == hipSuccess && first) e = hipMemcpy(nb.p, h->d_like.p, first, hipMemcpyDeviceToDevice);
+            if (e == hipSuccess && first) e = hipMemcpy(nb.p, M.d_bits.p, first, hipMemcpyDeviceToDevice);
             if (e != hipSuccess) nb.release();
             HIP_TRY(h, e);
-            h->d_like.release();
-            h->d_like = nb;
+            M.d_bits.release();
+            M.d_bits = nb;
         }
         const size_t cnt = n - first;
         std::vector<uint64_t> off(cnt + 1);
         off[0] = 0;
         for (size_t i = 0; i < cnt; i++) off[i + 1] = off[i] + h->dict[first + i].size();
-        std::vector<uint8_t> bytes(off[cnt] + 1);
+        std::vector<uint8_t> bytes(off[cnt] + 1), bits(cnt);
         for (size_t i = 0; i < cnt; i++) memcpy(bytes.data() + off[i], h->dict[first + i].data(), h->dict[first + i].size());
-        const EntryBlock B{cnt, off.data(), bytes.data()};
-        const uint32_t top = kLikeMaxPatterns - 1;
-        LikeKernelArgs A{};
-        const bool like_dev = !pats.empty() && cnt >= kLikeDeviceThreshold && like_dev_patterns(pats, A.pat);
-        const bool coll_dev = !preds.empty() && cnt >= kCollDeviceThreshold;
-        const bool in_dev = in_strings && cnt >= kInDeviceThreshold;
-        const bool like_host = !pats.empty() && !like_dev, coll_host = !preds.empty() && !coll_dev, in_host = in_strings && !in_dev;
-        const bool dev = like_dev || coll_dev || in_dev, host = like_host || coll_host || in_host;
-        const InTable in_tab = h->in_table.view();
-        if (in_dev) I.tab = in_table_at(h->in_table, h->d_in_table.p);
-        uint8_t* const dst = h->d_like.p + first;  // (entries no launch has been told about yet: like_n grows below)
-        std::vector<uint8_t> bits(host ? cnt : 0, 0), dev_bits(dev ? cnt : 0);
-        MatchCounts c;
-        // the device's part goes straight to the table unless the host has bits of the other kind to add
-        if (dev)
-            HIP_TRY(h, match_block_device(h->match_scratch, B, like_dev ? &A : nullptr, pats, coll_dev ? &preds : nullptr, top,
-                                          in_dev ? &I : nullptr, &in_tab, h->stream, host ? nullptr : dst, dev_bits.data(), c));
-        if (like_host) {
-            like_match_block_host(pats, cnt, B.off, B.bytes, bits.data());
-            c.like_host += cnt;
-        }
-        if (coll_host) {
-            coll_eval_block_host(preds, top, cnt, B.off, B.bytes, bits.data());
-            c.coll_host += count_array_text(B);
-        }
-        if (in_host) {
-            in_match_block_host(in_tab, cnt, B.off, B.bytes, bits.data());
-            c.in_host += cnt;
-        }
-        if (host) {
-            for (size_t i = 0; i < cnt && dev; i++) bits[i] |= dev_bits[i];
-            HIP_TRY(h, hipMemcpy(dst, bits.data(), cnt, hipMemcpyHostToDevice));
-        }
-        h->like_on_device += c.like_dev;
-        h->like_on_host += c.like_host;
-        h->coll_on_device += c.coll_dev;
-        h->coll_on_host += c.coll_host;
-        h->in_on_device += c.in_dev;
-        h->in_on_host += c.in_host;
-        h->like_built_for = n;
+        const bool want_dev[MK_COUNT] = {cnt >= kLikeDeviceThreshold, cnt >= kCollDeviceThreshold, cnt >= kInDeviceThreshold};
+        Routes R;
+        choose_routes(M, want_dev, R);
+        // (d_bits + first: entries no launch has been told about yet, match_n grows below)
+        HIP_TRY(h, match_block(M, EntryBlock{cnt, off.data(), bytes.data()}, R, h->stream, M.d_bits.p + first, bits.data()));
+        M.built_for = n;
     }
-    P.like_bits = h->d_like.p;
-    P.like_n = (uint32_t)h->like_built_for;
+    P.match_bits = M.d_bits.p;
+    P.match_n = (uint32_t)M.built_for;
     return N1K_OK;
 }
 
 }  // namespace n1k_eng
 
-// ---- the diagnostic entry points: the matchers on their own
+// ---- the diagnostic entry points: one kind's matcher on its own, over a table of that one predicate (bit 0)
 
 // what all four check of their arguments (device: the kernels count entries in 32 bits)
 static bool block_args_ok(const char* text, size_t text_len, uint64_t n, const uint64_t* offsets, const char* bytes, const uint8_t* out_bits,
@@ -237,145 +302,98 @@ static bool block_args_ok(const char* text, size_t text_len, uint64_t n, const u
     return !(n && offsets[n] > offsets[0] && !bytes);
 }
 
+// the pattern -> its program
+static n1k_status like_parse(const char* text, size_t len, MatchTable& M) {
+    M.patterns.resize(1);
+    return like_compile(text ? text : "", len, M.patterns[0]) ? N1K_OK : N1K_INVALID;
+}
+
 // one whole `any ... end` term -> program; N1K_UNSUPPORTED for what n1k_create refuses in a plan, N1K_INVALID for text
 // that is no such term
-static n1k_status coll_parse(const char* text, size_t len, std::vector<CollPred>& preds) {
+static n1k_status coll_parse(const char* text, size_t len, MatchTable& M) {
     PlanError err;
     const std::string src(text ? text : "", len);
     auto e = parse_expression(src, err);
     if (!e) return err.unsupported ? N1K_UNSUPPORTED : N1K_INVALID;
     if (e->kind != EK::Coll) return N1K_INVALID;
-    preds.resize(1);
-    preds[0].text = src;
-    if (!coll_compile(e.get(), preds[0].prog, err)) return err.unsupported ? N1K_UNSUPPORTED : N1K_INVALID;
+    M.preds.resize(1);
+    M.preds[0].text = src;
+    M.coll_top = 0;
+    if (!coll_compile(e.get(), M.preds[0].prog, err)) return err.unsupported ? N1K_UNSUPPORTED : N1K_INVALID;
     return N1K_OK;
 }
 
-// the bracketed list alone -> the table of its strings (bit 0); N1K_UNSUPPORTED for what n1k_create refuses in a plan,
-// N1K_INVALID for text that is no list
-static n1k_status in_parse(const char* text, size_t len, InTableHost& T) {
+// the bracketed list alone -> the table of its strings; N1K_UNSUPPORTED for what n1k_create refuses in a plan,
+// N1K_INVALID for text that is no list.  (A list without strings holds no entry: not present, zeros without a launch.)
+static n1k_status in_parse(const char* text, size_t len, MatchTable& M) {
     PlanError err;
     const std::string src = "(`x` in " + std::string(text ? text : "", len) + ")";
     auto e = parse_expression(src, err);
     if (!e) return err.unsupported ? N1K_UNSUPPORTED : N1K_INVALID;
     if (e->kind != EK::In) return N1K_INVALID;
-    std::vector<InList> lists(1);
-    if (!in_compile(e.get(), lists[0], err)) return err.unsupported ? N1K_UNSUPPORTED : N1K_INVALID;
-    lists[0].mask = lists[0].strings.empty() ? 0 : 1;
-    in_build_table(lists, T);
+    M.lists.resize(1);
+    if (!in_compile(e.get(), M.lists[0], err)) return err.unsupported ? N1K_UNSUPPORTED : N1K_INVALID;
+    M.string_lists = M.lists[0].strings.empty() ? 0 : 1;
+    M.lists[0].mask = (uint8_t)M.string_lists;
+    in_build_table(M.lists, M.in_table);
     return N1K_OK;
 }
 
-// one kind through the driver on `device`, with scratch of its own
-static n1k_status block_on_device(int device, const EntryBlock& B, LikeKernelArgs* like, const std::vector<LikePattern>& pats,
-                                  const std::vector<CollPred>* coll, const InTableHost* in, uint8_t* out_bits, uint64_t* out_left_to_host) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev || hipSetDevice(device) != hipSuccess) return N1K_DEVICE_ERROR;
-    struct Scratch : MatchScratch {
-        DevBuf<uint8_t> in_table;
-        ~Scratch() {
-            release();
-            in_table.release();
-        }
-    } S;
-    MatchCounts c;
-    InKernelArgs I{};
-    InTable in_host{};
-    if (in) {
-        std::vector<uint8_t> blob;
-        in_table_blob(*in, blob);
-        if (S.in_table.ensure(blob.size()) != hipSuccess || hipMemcpy(S.in_table.p, blob.data(), blob.size(), hipMemcpyHostToDevice) != hipSuccess)
-            return N1K_DEVICE_ERROR;
-        I.tab = in_table_at(*in, S.in_table.p);
-        in_host = in->view();
+// All six: the block through the driver with the one kind `parse` compiles — through its host matcher, or (on_device) through
+// its kernel on `device` with scratch of its own; a LIKE program the kernel does not take sends every string to the host.
+static n1k_status match_alone(int kind, n1k_status (*parse)(const char*, size_t, MatchTable&), bool on_device, int device, const char* text,
+                              size_t text_len, uint64_t n, const uint64_t* offsets, const char* bytes, uint8_t* out_bits, uint64_t* out_left_to_host) {
+    return guarded(nullptr, [&]() -> n1k_status {
+    if (!block_args_ok(text, text_len, n, offsets, bytes, out_bits, on_device)) return N1K_INVALID;
+    struct Table : MatchTable {
+        ~Table() { release(); }
+    } M;
+    const n1k_status st = parse(text, text_len, M);
+    if (st != N1K_OK) return st;
+    if (out_left_to_host) *out_left_to_host = 0;
+    if (n == 0) return N1K_OK;
+    bool want_dev[MK_COUNT] = {};
+    want_dev[kind] = on_device;
+    Routes R;
+    choose_routes(M, want_dev, R);
+    if (R.ndev) {
+        int ndev = 0;
+        if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev || hipSetDevice(device) != hipSuccess) return N1K_DEVICE_ERROR;
+        if (upload_in_constants(M, nullptr) != hipSuccess) return N1K_DEVICE_ERROR;
     }
-    if (match_block_device(S, B, like, pats, coll, 0, in ? &I : nullptr, &in_host, nullptr, nullptr, out_bits, c) != hipSuccess) return N1K_DEVICE_ERROR;
-    if (out_left_to_host) *out_left_to_host = c.like_host + c.coll_host + c.in_host;
+    if (match_block(M, EntryBlock{n, offsets, (const uint8_t*)bytes}, R, nullptr, nullptr, out_bits) != hipSuccess) return N1K_DEVICE_ERROR;
+    if (out_left_to_host) *out_left_to_host = M.counts[kind].host;
     return N1K_OK;
+    });
 }
 
 extern "C" {
 
 n1k_status n1k_like_match(const char* pattern, size_t pattern_len, uint64_t n, const uint64_t* offsets, const char* bytes, uint8_t* out_bits) {
-    return guarded(nullptr, [&]() -> n1k_status {
-    if (!block_args_ok(pattern, pattern_len, n, offsets, bytes, out_bits, false)) return N1K_INVALID;
-    std::vector<LikePattern> pats(1);
-    if (!like_compile(pattern ? pattern : "", pattern_len, pats[0])) return N1K_INVALID;
-    like_match_block_host(pats, n, offsets, (const uint8_t*)bytes, out_bits);
-    return N1K_OK;
-    });
+    return match_alone(MK_LIKE, like_parse, false, 0, pattern, pattern_len, n, offsets, bytes, out_bits, nullptr);
 }
 
 n1k_status n1k_like_match_device(int device, const char* pattern, size_t pattern_len, uint64_t n, const uint64_t* offsets, const char* bytes,
                                  uint8_t* out_bits, uint64_t* out_left_to_host) {
-    return guarded(nullptr, [&]() -> n1k_status {
-    if (!block_args_ok(pattern, pattern_len, n, offsets, bytes, out_bits, true)) return N1K_INVALID;
-    std::vector<LikePattern> pats(1);
-    if (!like_compile(pattern ? pattern : "", pattern_len, pats[0])) return N1K_INVALID;
-    if (out_left_to_host) *out_left_to_host = 0;
-    if (n == 0) return N1K_OK;
-    LikeKernelArgs A{};
-    if (!like_dev_patterns(pats, A.pat)) {  // a program the kernel does not take: every string is the host's
-        like_match_block_host(pats, n, offsets, (const uint8_t*)bytes, out_bits);
-        if (out_left_to_host) *out_left_to_host = n;
-        return N1K_OK;
-    }
-    return block_on_device(device, EntryBlock{n, offsets, (const uint8_t*)bytes}, &A, pats, nullptr, nullptr, out_bits, out_left_to_host);
-    });
+    return match_alone(MK_LIKE, like_parse, true, device, pattern, pattern_len, n, offsets, bytes, out_bits, out_left_to_host);
 }
 
 n1k_status n1k_coll_eval(const char* predicate_text, size_t len, uint64_t n, const uint64_t* offsets, const char* bytes, uint8_t* out_bits) {
-    return guarded(nullptr, [&]() -> n1k_status {
-    if (!block_args_ok(predicate_text, len, n, offsets, bytes, out_bits, false)) return N1K_INVALID;
-    std::vector<CollPred> preds;
-    const n1k_status st = coll_parse(predicate_text, len, preds);
-    if (st != N1K_OK) return st;
-    if (n) memset(out_bits, 0, n);
-    coll_eval_block_host(preds, 0, n, offsets, (const uint8_t*)bytes, out_bits);
-    return N1K_OK;
-    });
+    return match_alone(MK_COLL, coll_parse, false, 0, predicate_text, len, n, offsets, bytes, out_bits, nullptr);
 }
 
 n1k_status n1k_coll_eval_device(int device, const char* predicate_text, size_t len, uint64_t n, const uint64_t* offsets, const char* bytes,
                                 uint8_t* out_bits, uint64_t* out_left_to_host) {
-    return guarded(nullptr, [&]() -> n1k_status {
-    if (!block_args_ok(predicate_text, len, n, offsets, bytes, out_bits, true)) return N1K_INVALID;
-    std::vector<CollPred> preds;
-    const n1k_status st = coll_parse(predicate_text, len, preds);
-    if (st != N1K_OK) return st;
-    if (out_left_to_host) *out_left_to_host = 0;
-    if (n == 0) return N1K_OK;
-    return block_on_device(device, EntryBlock{n, offsets, (const uint8_t*)bytes}, nullptr, {}, &preds, nullptr, out_bits, out_left_to_host);
-    });
+    return match_alone(MK_COLL, coll_parse, true, device, predicate_text, len, n, offsets, bytes, out_bits, out_left_to_host);
 }
 
 n1k_status n1k_in_match(const char* list_text, size_t len, uint64_t n, const uint64_t* offsets, const char* bytes, uint8_t* out_bits) {
-    return guarded(nullptr, [&]() -> n1k_status {
-    if (!block_args_ok(list_text, len, n, offsets, bytes, out_bits, false)) return N1K_INVALID;
-    InTableHost T;
-    const n1k_status st = in_parse(list_text, len, T);
-    if (st != N1K_OK) return st;
-    if (n) memset(out_bits, 0, n);
-    in_match_block_host(T.view(), n, offsets, (const uint8_t*)bytes, out_bits);
-    return N1K_OK;
-    });
+    return match_alone(MK_IN, in_parse, false, 0, list_text, len, n, offsets, bytes, out_bits, nullptr);
 }
 
 n1k_status n1k_in_match_device(int device, const char* list_text, size_t len, uint64_t n, const uint64_t* offsets, const char* bytes,
                                uint8_t* out_bits, uint64_t* out_left_to_host) {
-    return guarded(nullptr, [&]() -> n1k_status {
-    if (!block_args_ok(list_text, len, n, offsets, bytes, out_bits, true)) return N1K_INVALID;
-    InTableHost T;
-    const n1k_status st = in_parse(list_text, len, T);
-    if (st != N1K_OK) return st;
-    if (out_left_to_host) *out_left_to_host = 0;
-    if (n == 0) return N1K_OK;
-    if (T.c_mask.empty()) {  // a list without strings holds no entry: nothing to launch
-        memset(out_bits, 0, n);
-        return N1K_OK;
-    }
-    return block_on_device(device, EntryBlock{n, offsets, (const uint8_t*)bytes}, nullptr, {}, nullptr, &T, out_bits, out_left_to_host);
-    });
+    return match_alone(MK_IN, in_parse, true, device, list_text, len, n, offsets, bytes, out_bits, out_left_to_host);
 }
 
 }  // extern "C"

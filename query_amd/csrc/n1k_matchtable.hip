@@ -48,7 +48,7 @@ struct LikeMatcher {
 
 struct CollMatcher {
     using Args = CollKernelArgs;
-    struct Params { CollProg progs[kLikeMaxPatterns]; };
+    struct Params { CollProg progs[kMatchBits]; };
     static constexpr uint32_t kMaxLen = kCollDevMaxLen;
     static __device__ void stage(Params& par, const Args& A, uint32_t tid) {
         const uint32_t* src = (const uint32_t*)A.progs;
@@ -126,7 +126,7 @@ hipError_t launch_like_match(const LikeKernelArgs& A, hipStream_t st) {
 
 hipError_t launch_coll_match(const CollKernelArgs& A, hipStream_t st) {
     if (A.blk.n == 0 || A.nprog == 0) return hipSuccess;
-    if (A.nprog > kLikeMaxPatterns) return hipErrorInvalidValue;
+    if (A.nprog > kMatchBits) return hipErrorInvalidValue;
     const uint32_t grid = (A.blk.n + kMatchBlock - 1) / kMatchBlock;
     hipLaunchKernelGGL(coll_match_kernel, dim3(grid), dim3(kMatchBlock), 0, st, A);
     return hipGetLastError();

@@ -46,16 +46,16 @@ bool build_fast_args(n1k_handle* h, uint32_t max_slots, FastArgs& F, bool fuse, 
             ft.op = t.op; ft.col = t.a.col;
         } else if (term_is_table_bit(t.op)) {  // column LIKE "pattern", ANY / EVERY over a column, column IN [constants]: the table and its extent travel in the term
             if (t.a.is_const) return false;
-            ft.op = t.op; ft.col = t.a.col; ft.like_n = P.like_n; ft.like_bit = 1u << (uint32_t)t.b.cpayload;
-            ft.like_bits = P.like_bits;
+            ft.op = t.op; ft.col = t.a.col; ft.match_n = P.match_n; ft.match_mask = 1u << (uint32_t)t.b.cpayload;
+            ft.match_bits = P.match_bits;
             if (t.op == TERM_IN) {  // its mask and flags as the term holds them, and its range of the plan's number constants
                 const uint32_t begin = (uint32_t)t.c.cpayload, end = (uint32_t)(t.c.cpayload >> 32);
-                ft.like_bit = (uint32_t)t.b.cpayload;
+                ft.match_mask = (uint32_t)t.b.cpayload;
                 ft.in_nums = P.in_nums + begin;
                 ft.in_n = end - begin;
             }
-            // (the kernels stage a small table in LDS, kLikeLdsBytes beside the workgroup's table)
-            max_slots = (uint32_t)std::min<uint64_t>(max_slots, (156u * 1024u - kLikeLdsBytes) / (P.lds_words * 8));
+            // (the kernels stage a small table in LDS, kMatchLdsBytes beside the workgroup's table)
+            max_slots = (uint32_t)std::min<uint64_t>(max_slots, (156u * 1024u - kMatchLdsBytes) / (P.lds_words * 8));
         } else if (t.op == TERM_EQ) {  // column = "string constant" (either side)
             const Operand *c = nullptr, *k = nullptr;
             if (!t.a.is_const && t.b.is_const && t.b.ctag == T_STRING) { c = &t.a; k = &t.b; }
@@ -261,22 +261,18 @@ n1k_status run_group_batch(n1k_handle* h, const n1k_batch* b) {
         }
         const Program& P = ndist ? Pc : h->prog;  // (shadows the handle's program for the launches below)
         const uint32_t table_bytes = F.lds_slots * P.lds_words * 8;
-        // a shape with a LIKE or an ANY / EVERY term carries kLikeLdsBytes of static LDS for the staged match table (n1k_spec.h: present by
-        // shape, whatever the table's size) — part of every budget below
-        uint32_t like_lds = 0;
-        for (uint32_t t = 0; t < F.nterms; t++)
-            if (term_is_table_bit(F.terms[t].op)) like_lds = kLikeLdsBytes;
+        const uint32_t match_lds = match_lds_bytes(F);  // static LDS of the staged match table: part of every budget below
         // the word scatter's LDS (per DISTINCT aggregate one ScatterLds<uint64_t, 512, 4>, n1k_scatter.h: 2048 staged words,
         // counters, run starts) and, in what is left of the workgroup's share of the CU, its "already logged" caches
         const uint32_t scatter_bytes = ndist * (2048u * 8u + 2u * 256u * 4u + 256u * 4u + 256u * 8u + 2048u) + (ndist ? 64u : 0u);
         uint32_t dcache_slots = 0;
         if (ndist) {
-            const uint32_t without = table_bytes + scatter_bytes + like_lds;
+            const uint32_t without = table_bytes + scatter_bytes + match_lds;
             const uint32_t share = 160u * 1024u / std::max(1u, std::min(3u, 160u * 1024u / (without + 512u)));
             for (uint32_t sl = 4096; sl >= 64; sl >>= 1)
                 if (without + ndist * sl * 8u + 512u <= share) { dcache_slots = sl; break; }
         }
-        const uint32_t lds_total = table_bytes + scatter_bytes + ndist * dcache_slots * 8u + like_lds;
+        const uint32_t lds_total = table_bytes + scatter_bytes + ndist * dcache_slots * 8u + match_lds;
         // workgroups per CU that fit: 512 threads x 3 (<= 48 KiB each), x 2 (<= 72 KiB), else 1024 threads x 1
         uint32_t fblock = h->opt_block == 1024 || h->opt_block == 512 ? h->opt_block : (table_bytes <= 72 * 1024 ? 512u : 1024u);
         if (ndist) fblock = 512;
@@ -309,7 +305,7 @@ n1k_status run_group_batch(n1k_handle* h, const n1k_batch* b) {
         }
         if (jit && fblock != 512) {  // run-time instantiations are built for 512-thread workgroups
             fblock = 512;
-            per_cu = table_bytes + like_lds <= 48 * 1024 ? 3u : 2u;
+            per_cu = table_bytes + match_lds <= 48 * 1024 ? 3u : 2u;
             fgrid = h->opt_grid_blocks ? h->opt_grid_blocks : (uint32_t)(h->num_cus * per_cu);
         }
         h->stats.spec_kernel = spec ? 1u : (jit ? (F.nderived ? 3u : 2u) : 0u);
@@ -666,7 +662,7 @@ n1k_status push_device(n1k_handle* h, const n1k_batch* b) {
     if (st != N1K_OK) return st;
     st = ensure_rank(h);
     if (st != N1K_OK) return st;
-    st = ensure_like(h);
+    st = ensure_match_table(h);
     if (st != N1K_OK) return st;
     bool partition = can_partition && head == 0 && b->nrows > 0;
     uint64_t groups_est = b->nrows;

@@ -61,35 +61,35 @@ constexpr bool spec_hashed() {
 }
 
 // LIKE and ANY / EVERY terms of a Spec: the match table (one byte per dictionary code, all terms of a plan share it) is staged in LDS before
-// the tile loop when it has at most kLikeLdsBytes entries — a per-row gather then costs an LDS read instead of a dependent
+// the tile loop when it has at most kMatchLdsBytes entries — a per-row gather then costs an LDS read instead of a dependent
 // trip to L2 — and read from global memory otherwise.
 template <class Spec>
-constexpr bool spec_has_like() {
+constexpr bool spec_has_match() {
     bool h = false;
     for (int t = 0; t < Spec::nterms; t++) h = h || term_is_table_bit(Spec::terms[t].op);
     return h;
 }
 template <class Spec>
-constexpr int spec_like_term() {
+constexpr int spec_match_term() {
     for (int t = 0; t < Spec::nterms; t++)
         if (term_is_table_bit(Spec::terms[t].op)) return t;
     return 0;
 }
-struct SpecLike {
+struct SpecMatch {
     const uint8_t* lds;  // the staged copy
-    bool in_lds;         // wave-uniform: read the copy (else FastTerm::like_bits)
+    bool in_lds;         // wave-uniform: read the copy (else FastTerm::match_bits)
 };
 // Every thread of the workgroup calls this ahead of a __syncthreads() that precedes the tile loop.  `words`: the
-// workgroup's kLikeLdsBytes / 4 words of LDS (one word for a Spec without LIKE).  The table's allocation carries spare
+// workgroup's kMatchLdsBytes / 4 words of LDS (one word for a Spec without LIKE).  The table's allocation carries spare
 // bytes, so whole words may be read.
 template <class Spec, int BLOCK>
-N1K_DEV SpecLike spec_stage_like(const FastArgs& F, uint32_t* words, uint32_t tid) {
-    SpecLike K{(const uint8_t*)words, false};
-    if constexpr (spec_has_like<Spec>()) {
-        constexpr int t = spec_like_term<Spec>();
-        const uint32_t n = F.terms[t].like_n;
-        if (n <= kLikeLdsBytes) {
-            const uint32_t* src = (const uint32_t*)F.terms[t].like_bits;
+N1K_DEV SpecMatch spec_stage_match(const FastArgs& F, uint32_t* words, uint32_t tid) {
+    SpecMatch K{(const uint8_t*)words, false};
+    if constexpr (spec_has_match<Spec>()) {
+        constexpr int t = spec_match_term<Spec>();
+        const uint32_t n = F.terms[t].match_n;
+        if (n <= kMatchLdsBytes) {
+            const uint32_t* src = (const uint32_t*)F.terms[t].match_bits;
             for (uint32_t k = tid; k < (n + 3u) / 4u; k += BLOCK) words[k] = src[k];
             K.in_lds = true;
         }
@@ -98,7 +98,7 @@ N1K_DEV SpecLike spec_stage_like(const FastArgs& F, uint32_t* words, uint32_t ti
 }
 
 template <class Spec>
-N1K_DEV bool spec_term_true(int t, const FastArgs& F, const SpecLike& K, uint32_t tg, uint64_t p) {
+N1K_DEV bool spec_term_true(int t, const FastArgs& F, const SpecMatch& K, uint32_t tg, uint64_t p) {
     constexpr int kT = kFastTerms;
     (void)kT;
     const uint32_t op = Spec::terms[t].op;
@@ -112,16 +112,16 @@ N1K_DEV bool spec_term_true(int t, const FastArgs& F, const SpecLike& K, uint32_
         case TERM_STR_EQ: return tg == T_STRING && p == F.terms[t].cpayload;
         case TERM_LIKE:
         case TERM_COLL: {  // one bit of the match table (a string's entry, an array's); a code the table does not cover is not read
-            if (tg != term_table_tag(op) || (uint32_t)p >= F.terms[t].like_n) return false;
-            const uint8_t b = K.in_lds ? K.lds[(uint32_t)p] : F.terms[t].like_bits[(uint32_t)p];
-            return (b & F.terms[t].like_bit) != 0;
+            if (tg != term_table_tag(op) || (uint32_t)p >= F.terms[t].match_n) return false;
+            const uint8_t b = K.in_lds ? K.lds[(uint32_t)p] : F.terms[t].match_bits[(uint32_t)p];
+            return (b & F.terms[t].match_mask) != 0;
         }
         case TERM_IN: {  // TRUE exactly when the value equals a constant of the list (In.Apply, expression/coll_in.go:61-91)
-            const uint32_t flags = F.terms[t].like_bit;
+            const uint32_t flags = F.terms[t].match_mask;
             if (tg == T_INT || tg == T_FLOAT) return in_num_hit(F.terms[t].in_nums, F.terms[t].in_n, tg, p);
             if (tg != T_STRING) return tg == T_TRUE ? (flags & IN_HAS_TRUE) != 0 : (tg == T_FALSE && (flags & IN_HAS_FALSE) != 0);
-            if (!(flags & 0xFFu) || (uint32_t)p >= F.terms[t].like_n) return false;
-            const uint8_t b = K.in_lds ? K.lds[(uint32_t)p] : F.terms[t].like_bits[(uint32_t)p];
+            if (!(flags & 0xFFu) || (uint32_t)p >= F.terms[t].match_n) return false;
+            const uint8_t b = K.in_lds ? K.lds[(uint32_t)p] : F.terms[t].match_bits[(uint32_t)p];
             return (b & flags & 0xFFu) != 0;
         }
         default: {
@@ -228,7 +228,7 @@ template <class Spec>
 N1K_DEV void spec_row(const Program& P, const FastArgs& F, const GlobalTable& G, unsigned long long* ngroups,
                       uint64_t* lds, uint32_t S, uint32_t* lds_fill, const uint32_t (&tg)[kSpecCols],
                       const uint64_t (&pv)[kSpecCols], uint32_t& selected, uint32_t& unpackable, const WordLogArgs& L,
-                      uint64_t* dcache, uint64_t (&words)[kSpecDistinct], uint32_t (&bins)[kSpecDistinct], const SpecLike& K) {
+                      uint64_t* dcache, uint64_t (&words)[kSpecDistinct], uint32_t (&bins)[kSpecDistinct], const SpecMatch& K) {
     constexpr int kND = spec_ndistinct<Spec>();
     bool pass = true;
 #pragma unroll
@@ -474,7 +474,7 @@ N1K_DEV uint32_t rec16_region(const Rec16& r) { return part_hash(r.k & ~kRecIntF
 
 template <class Spec>
 N1K_DEV void spec_row_record(const Program& P, const FastArgs& F, const uint32_t (&tg)[kSpecCols], const uint64_t (&pv)[kSpecCols],
-                             uint32_t& selected, uint32_t& unpackable, Rec16& rec, uint32_t& bin, const SpecLike& K) {
+                             uint32_t& selected, uint32_t& unpackable, Rec16& rec, uint32_t& bin, const SpecMatch& K) {
     bool pass = true;
 #pragma unroll
     for (int t = 0; t < Spec::nterms; t++) pass = pass && spec_term_true<Spec>(t, F, K, tg[Spec::terms[t].col], pv[Spec::terms[t].col]);
@@ -502,8 +502,8 @@ N1K_DEV void scan_spec_records_body(const Program& P, const FastArgs& F, const W
     extern __shared__ uint64_t lds[];
     ScatterLds<Rec16, BLOCK, kNW>& S = *(ScatterLds<Rec16, BLOCK, kNW>*)lds;
     const uint32_t tid = threadIdx.x;
-    __shared__ uint32_t like_words[spec_has_like<Spec>() ? kLikeLdsBytes / 4 : 1];
-    const SpecLike K = spec_stage_like<Spec, BLOCK>(F, like_words, tid);
+    __shared__ uint32_t match_words[spec_has_match<Spec>() ? kMatchLdsBytes / 4 : 1];
+    const SpecMatch K = spec_stage_match<Spec, BLOCK>(F, match_words, tid);
     scatter_init<BLOCK>(S.cnt);
     __syncthreads();
     const uint32_t sub = blockIdx.x % kRecSubs;
@@ -618,9 +618,9 @@ N1K_DEV void scan_spec_partition_body(const Program& P, const FastArgs& F, const
     constexpr int kNW = R * (int)kRowsPerItem;
     constexpr int TILE = BLOCK * kNW;
     __shared__ PartLds<Spec, TILE> S;
-    __shared__ uint32_t like_words[spec_has_like<Spec>() ? kLikeLdsBytes / 4 : 1];
+    __shared__ uint32_t match_words[spec_has_match<Spec>() ? kMatchLdsBytes / 4 : 1];
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
-    const SpecLike K = spec_stage_like<Spec, BLOCK>(F, like_words, tid);
+    const SpecMatch K = spec_stage_match<Spec, BLOCK>(F, match_words, tid);
     for (uint32_t i = tid; i < 128; i += BLOCK) (&S.cnt[0][0])[i] = 0;
     if (tid < 64 && A.per_dest) {
         const uint64_t capd = A.dest_cap[tid];
@@ -826,8 +826,8 @@ N1K_DEV void scan_spec_body(const Program& P, const FastArgs& F, const GlobalTab
         for (int d = 0; d < kND; d++) scatter_init<BLOCK>(w_lds[d].cnt);
     }
     lds_table_init<BLOCK>(P, lds, S, tid);
-    __shared__ uint32_t like_words[spec_has_like<Spec>() ? kLikeLdsBytes / 4 : 1];
-    const SpecLike K = spec_stage_like<Spec, BLOCK>(F, like_words, tid);
+    __shared__ uint32_t match_words[spec_has_match<Spec>() ? kMatchLdsBytes / 4 : 1];
+    const SpecMatch K = spec_stage_match<Spec, BLOCK>(F, match_words, tid);
     if (tid == 0) lds_fill = 0;
     __syncthreads();
 

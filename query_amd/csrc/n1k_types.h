@@ -93,7 +93,7 @@ enum : uint32_t {
 constexpr bool term_is_table_bit(uint32_t op) { return op == TERM_LIKE || op == TERM_COLL || op == TERM_IN; }
 constexpr uint32_t term_table_tag(uint32_t op) { return op == TERM_COLL ? (uint32_t)T_ARRAY : (uint32_t)T_STRING; }
 
-// TERM_IN: what the list holds besides strings and numbers (b.cpayload, FastTerm::like_bit)
+// TERM_IN: what the list holds besides strings and numbers (b.cpayload, FastTerm::match_mask)
 enum : uint32_t { IN_HAS_TRUE = 1u << 8, IN_HAS_FALSE = 1u << 9, IN_HAS_NULL = 1u << 10, IN_EMPTY = 1u << 11 };
 // Distinct number constants of all IN lists of one plan.  A choice, not a measurement: 10 probe steps per row and 8 KiB
 // that stay in L2.
@@ -207,10 +207,10 @@ struct Program {
     uint64_t* wide_flt;
     unsigned long long* wide_count;  // distinct wide values met so far
     uint32_t wide_bits, pad1;
-    // LIKE: like_bits[code] bit p = pattern p of the plan matches dictionary string `code`; ANY / EVERY: bit 7 - q = collection
-    // predicate q holds for the array whose canonical text is entry `code`; codes at or beyond like_n have no entry and are not read
-    const uint8_t* like_bits;
-    uint32_t like_n, pad2;
+    // The match table of the plan's LIKE, ANY / EVERY and IN terms ("The match table"): match_bits[code] holds
+    // one bit per predicate for dictionary entry `code`; codes at or beyond match_n have no entry and are not read
+    const uint8_t* match_bits;
+    uint32_t match_n, pad2;
     // IN: the number constants of the plan's lists as float64 (each within +-2^53, so an INT constant is exactly its
     // double); every list's distinct numbers ascending, the lists back to back (device memory owned by the handle)
     const double* in_nums;
@@ -400,23 +400,28 @@ struct FastTerm {
     uint32_t col;   // column slot of operand a
     union {
         uint32_t ctag;    // the constant's tag
-        uint32_t like_n;  // TERM_LIKE / TERM_COLL: entries of the match table (Program::like_n); codes at or beyond it are not read
+        uint32_t match_n;  // TERM_LIKE / TERM_COLL / TERM_IN: entries of the match table (Program::match_n); codes at or beyond it are not read
     };
     union {
         uint32_t pad;
-        uint32_t like_bit;  // TERM_LIKE / TERM_COLL: the pattern's (predicate's) bit in a table entry; TERM_IN: the list's
-                            // mask (0: no string in the list) | IN_* flags
+        uint32_t match_mask;  // TERM_LIKE / TERM_COLL: the pattern's (predicate's) one bit of a table entry.  TERM_IN: the list's
+                              // bit (0: no string in the list) in the low byte PLUS its IN_* flags above it: mask the byte to test the entry
     };
     union {
         uint64_t cpayload;         // the constant's payload
-        const uint8_t* like_bits;  // TERM_LIKE / TERM_COLL / TERM_IN: the match table (Program::like_bits)
+        const uint8_t* match_bits;  // TERM_LIKE / TERM_COLL / TERM_IN: the match table (Program::match_bits)
     };
     const double* in_nums;  // TERM_IN: the list's number constants, ascending (its range of Program::in_nums), in_n of them
     uint32_t in_n, pad2;
 };
 // A match table of at most this many bytes (= dictionary codes) is copied into LDS by the bounded and the plan-specialised
 // kernels before their tile loop; a larger one is read from global memory ("LIKE").
-constexpr uint32_t kLikeLdsBytes = 4096;
+constexpr uint32_t kMatchLdsBytes = 4096;
+// (kernel arguments: the renames of the match table's fields moved nothing)
+static_assert(sizeof(Term) == 80 && sizeof(FastTerm) == 40, "Term / FastTerm layout");
+static_assert(__builtin_offsetof(FastTerm, match_n) == 8 && __builtin_offsetof(FastTerm, match_mask) == 12 && __builtin_offsetof(FastTerm, match_bits) == 16, "FastTerm layout");
+static_assert(sizeof(Program) == 2288 && __builtin_offsetof(Program, match_bits) == 112 && __builtin_offsetof(Program, match_n) == 120 && __builtin_offsetof(Program, in_nums) == 128,
+              "Program layout");
 struct FastKey {
     uint32_t col, stride, radix, shift;
 };

@@ -503,6 +503,110 @@ def test_eight_bits_shared_with_like_and_any_every():
         assert ei.value.status == _ffi.UNSUPPORTED and "more than 8" in ei.value.message
 
 
+LIKE_MAX_LEN, COLL_MAX_LEN = 128, 192  # bytes of an entry like_match_kernel / coll_match_kernel takes (tests/test_gpu_coll.py)
+LONG_PATTERN = "%" + "x" * 250 + "7"    # its program (a MANY and a literal of 251 bytes) is longer than the LIKE kernel takes
+THREE_KIND_TAGS = ("s", "u", "v")
+
+
+def three_kind_dictionary(n, tag):
+    """n distinct entries marked with `tag`, strings then arrays, as tests/test_gpu_coll.py's mixed_dictionary builds them;
+    from 16 entries on with what each kernel leaves to the host and what only looks like an array among them.  Returns
+    (entries, texts of the strings as Go reads them, array values)."""
+    import coll_util as cu
+    ns = n - n // 2
+    strings = [("%s%d" % (tag, i)).encode() for i in range(ns)]
+    arrays = [[tag + "w%d" % i] + (["t_1"] if i % 3 == 0 else []) + ([i] if i % 2 else []) for i in range(n - ns)]
+    if n >= 16:
+        strings[1] = (tag + "x" * 300 + "7").encode()     # over 128 B: the host's for LIKE and IN; "%7", LONG_PATTERN and a list hold it
+        strings[2] = b"ab\xffc" + tag.encode()            # not valid UTF-8: the host's for LIKE (the byte is one U+FFFD, which `_` takes)
+        strings[3] = ("[looks like one " + tag).encode()  # a STRING that begins with '[': evaluated as array text; a list holds it
+        arrays[1] = [tag + "w1"] * 60 + ["t_1"]           # over 192 B: the host's for ANY / EVERY and for IN
+        arrays[2] = ['x"y', tag, "t_1"]                   # an escaped string FIRST, under both predicates: the host's for ANY / EVERY
+    return strings + cu.texts_of(arrays), [s.decode("utf-8", errors="replace") for s in strings], arrays
+
+
+def three_kind_counts(entries, like_dev, dev):
+    """(LIKE device, host; ANY / EVERY device, host; IN device, host) of one extension of the table by `entries`, by the rules
+    DESIGN.md §4 states.  LIKE and IN are evaluated for every entry, ANY / EVERY for one of at least 2 bytes that begins
+    with '['.  On the device route the LIKE kernel leaves an entry over 128 B or not valid UTF-8, the ANY / EVERY kernel one
+    over 192 B or with an escaped string where these predicates compare, the IN kernel one over 128 B."""
+    def valid(b):
+        try:
+            b.decode("utf-8")
+            return True
+        except UnicodeDecodeError:
+            return False
+    n = len(entries)
+    arr = [e for e in entries if len(e) >= 2 and e[:1] == b"["]
+    like_left = sum(1 for e in entries if len(e) > LIKE_MAX_LEN or not valid(e)) if like_dev else n
+    coll_left = sum(1 for e in arr if len(e) > COLL_MAX_LEN or b"\\" in e) if dev else len(arr)
+    in_left = sum(1 for e in entries if len(e) > iu.DEV_MAX_LEN) if dev else n
+    return n - like_left, like_left, len(arr) - coll_left, coll_left, n - in_left, in_left
+
+
+@pytest.mark.parametrize("long_pattern", [False, True], ids=["every-kind-on-the-device", "like-stays-on-the-host"])
+def test_a_plan_with_all_three_kinds_builds_one_table_on_both_routes(long_pattern):
+    """Two LIKE patterns and three IN lists (two with strings, one of numbers) over a string column and an ANY and an EVERY
+    over an array column in one Filter.  (a) T - 1 new entries go through the host matchers for every kind; (b) T more,
+    from an odd entry on, through the three kernels (one upload, merged once) — or, when one pattern's program is longer
+    than the LIKE kernel takes, through two kernels while LIKE stays with the host in the same extension; (c) 5 more through
+    the host matchers again, onto a table the device built.  The old entries keep their bits throughout."""
+    import json
+
+    import coll_util as cu
+    import like_util as lu
+    patterns = ["%b_c%", LONG_PATTERN] if long_pattern else ["%7", "%b_c%"]
+    preds = [(cu.ANY, ("cmp", "=", [], "t_1", False)), (cu.EVERY, ("like", [], "%w%4"))]
+    lists = [[tag + "x" * 300 + "7" for tag in THREE_KIND_TAGS] + ["s7", "u17", "v1", "nope"],
+             ["%s%d" % (tag, i) for tag in THREE_KIND_TAGS for i in range(5, 400, 9)] + ["[looks like one u"],
+             [1, 2.5]]
+    some = [b"a", b"", b"x" * 300 + b"7", b"ab\xffc", b"[1]", b"b7", b"abxc", b"7"]
+    # (no device is asked: a program the kernel does not take sends every string to the host before anything is launched)
+    assert [lu.device_match(p.encode(), some)[1] == len(some) for p in patterns] == [False, long_pattern]
+    cond = "(%s)" % " or ".join(["(%s like %s)" % (D("s"), json.dumps(p)) for p in patterns] + [iu.term(D("s"), l) for l in lists] +
+                                [cu.term_text(m, c, over=D("a")) for m, c in preds])
+    op = query_amd.GpuFilterGroup(plan.filter_group_plan(cond, [], ["count(*)"]))
+    T = op.like_stats()["device_threshold"]
+    assert T == op.coll_stats()["device_threshold"] == op.in_stats()["device_threshold"] and T % 2 == 0
+    in_fns = [iu.matcher(l) for l in lists]
+    rng = np.random.default_rng(int(long_pattern))
+    dictionary, str_hit, arr_hit, str_codes, arr_codes = [], [], [], [], []
+    want_stats = np.zeros(6, np.int64)
+    for tag, n in zip(THREE_KIND_TAGS, (T - 1, T, 5)):
+        entries, texts, arrays = three_kind_dictionary(n, tag)
+        base, ns = len(dictionary), len(texts)
+        dictionary += entries
+        str_codes += range(base, base + ns)
+        arr_codes += range(base + ns, base + n)
+        str_hit += [any(lu.like4(t, p) is True for p in patterns) or any(f(t) is True for f in in_fns) for t in texts]
+        arr_hit += [any(cu.coll_mirror(m, c, a) is True for m, c in preds) for a in arrays]
+        # rows over every entry interned so far (the old ones too), each special entry among them
+        rows = 20_000
+        si = np.concatenate([np.arange(len(str_codes)), rng.integers(0, len(str_codes), rows - len(str_codes))])
+        ai = np.concatenate([rng.integers(0, len(arr_codes), rows - len(arr_codes)), np.arange(len(arr_codes))])
+        cols = {D("s"): n1o.Column(D("s"), n1o.COL_DICT32, codes=np.array(str_codes, np.uint32)[si]),
+                D("a"): n1o.Column(D("a"), n1o.COL_TAGGED64, tags=np.full(rows, n1o.T_ARRAY, np.uint8), payload=np.array(arr_codes, np.uint64)[ai])}
+        op.process_items([cols[p] for p in op.column_paths], dictionary)
+        got = op.after_items().aggs[0][0][1]
+        assert int(_ffi.lib().n1k_dict_size(op._h)) == len(dictionary)  # (the handle interned nothing of its own: n new entries)
+        want = int((np.array(str_hit)[si] | np.array(arr_hit)[ai]).sum())
+        assert 0 < want < rows and got == want, (tag, got, want)
+        want_stats += three_kind_counts(entries, like_dev=n >= T and not long_pattern, dev=n >= T)
+        ls, cs, ins = op.like_stats(), op.coll_stats(), op.in_stats()
+        got_stats = (ls["device_strings"], ls["host_strings"], cs["device_arrays"], cs["host_arrays"], ins["device_strings"], ins["host_strings"])
+        assert got_stats == tuple(want_stats), (tag, got_stats, want_stats)
+        assert ls["patterns"] == 2 and cs["predicates"] == 2 and ins["lists"] == 3
+        op.reopen()  # (keeps the table)
+    # both routes were taken, the kernels left their special entries to the host, every pattern and list selected something
+    assert (want_stats[0] > 0) != long_pattern and want_stats[2] > 0 and want_stats[4] > 0
+    assert want_stats[1] >= T + 4 + 3 and want_stats[3] >= 2 and want_stats[5] >= T + 4 + 2
+    if long_pattern:
+        assert ls["device_strings"] == 0 and cs["device_arrays"] > 0 and ins["device_strings"] > 0
+    strings = [dictionary[c].decode("utf-8", errors="replace") for c in str_codes]
+    assert all(any(f(t) is True for t in strings) for f in in_fns[:2]) and all(any(lu.like4(t, p) for t in strings) for p in patterns)
+    op.done()
+
+
 def test_having_in_over_an_aggregate_and_over_a_string_group_key():
     rng = np.random.default_rng(9)
     t = make_table(rng, 4000)

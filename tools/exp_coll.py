@@ -9,7 +9,7 @@
              wall step time, and the spread of the baseline over the rounds.
   evaluator  N distinct arrays of about 30 bytes, one term: n1k_coll_eval on one thread against the device route end to
              end (upload + kernel + results back), arrays per second each, for several block sizes.
-  route      the handle's own route (ensure_like): a plan with two collection predicates, N new dictionary entries interned,
+  route      the handle's own route (ensure_match_table): a plan with two collection predicates, N new dictionary entries interned,
              then the first push of a one-row batch timed against a second push that brings no new entry.
   mixed      route, with exp_like.py's three LIKE patterns over a string column in the same Filter: both kinds of term
              evaluated for every new entry, one table.

@@ -9,7 +9,7 @@ list's strings cross.
            (an IN passes more rows than the `=` beside it: the rows selected are printed with the times).
   matcher  N distinct strings of 29 bytes against a list of 1000 strings, half of them present: n1k_in_match on one thread
            against n1k_in_match_device end to end (upload + kernel + results back), for 1 Ki, 4 Ki, 64 Ki and 1 Mi strings.
-  route    the handle's own route (ensure_like: buffers kept, the list's table uploaded once): N new dictionary strings
+  route    the handle's own route (ensure_match_table: buffers kept, the list's table uploaded once): N new dictionary strings
            interned, then the first push of a one-row batch timed against a second push that brings no new string.  N just
            below kInDeviceThreshold goes through the host matcher, N from it on through the kernel.
 

@@ -9,7 +9,7 @@
            end to end (upload + kernel + results back), strings per second each, for several block sizes: the crossover
            is what kLikeDeviceThreshold (n1k_like.h) is set from.
 
-  route    the handle's own route (ensure_like: buffers kept, ONE upload and one launch for all patterns of the plan): a
+  route    the handle's own route (ensure_match_table: buffers kept, ONE upload and one launch for all patterns of the plan): a
            plan with three patterns, N new dictionary strings interned, then the first push of a one-row batch timed
            against a second push that brings no new string.  N just below kLikeDeviceThreshold goes through the host
            matcher, N at it through the kernel: both routes measured where they are meant to cross.
