@@ -410,6 +410,37 @@ n1k_status n1k_in_match_device(int device, const char *list_text, size_t len, ui
  * out[3] the number of new dictionary entries from which the device route is taken */
 n1k_status n1k_in_stats(const n1k_handle *h, uint64_t out[4]);
 
+/* ------------------------------------------------------- string functions -- */
+
+/*
+ * A condition term over string functions of ONE leaf path (expression/func_str.go) runs on the device: the path wrapped in
+ * up to four of lower (func_str.go:204), upper (:1155), trim / ltrim / rtrim with an optional constant cutset (:255-275,
+ * :672-676, :1085-1089; default " \t\n\f\r", :301), then compared with STRING constants (=, <, <=, either side, BETWEEN),
+ * matched by LIKE with a constant pattern or searched by contains (:81); or position / pos / position0 / pos0 / position1 /
+ * pos1 (:1168-1177, func_registry.go:148-153) of the bare path compared with NUMBER constants.  Such a term is MISSING for
+ * MISSING, NULL for a non-STRING and a plain boolean for a STRING — a function of the string alone, so it is one more
+ * predicate of the match table: one evaluation per DISTINCT dictionary string, one bit test per row, one of the eight
+ * bits the kinds share.  Under lower / upper every constant of the term must be pure ASCII; n1k_create answers
+ * N1K_UNSUPPORTED for that and for length, substr, replace, regexp_* and the other string functions.  The two entry points
+ * below run the evaluators on their own (tests, diagnostics); n1k_strfn_stats says which route built a handle's table.
+ *
+ * n1k_strfn_eval: the host evaluator, no GPU needed.  term_text is one whole term as expression/stringer.go writes it
+ * ((lower((`d`.`name`)) like "%phone%"), contains((`d`.`s`), "amazon")); the path is parsed and otherwise unused.
+ * String i is bytes[offsets[i] - offsets[0], offsets[i + 1] - offsets[0]); out_bits[i] = 1 when the term is TRUE for it.
+ * N1K_UNSUPPORTED for a term n1k_create refuses in a plan, N1K_INVALID for text that is no such term.
+ */
+n1k_status n1k_strfn_eval(const char *term_text, size_t len, uint64_t n, const uint64_t *offsets, const char *bytes,
+                          uint8_t *out_bits);
+/* The same through strfn_match_kernel on `device`.  *out_left_to_host counts the strings the kernel left to the host
+ * evaluator: longer than 128 bytes; holding U+0130 or U+212A under lower, U+017F or U+0131 under upper (the four
+ * non-ASCII runes whose simple case mapping is ASCII); not valid UTF-8 under LIKE.  The results are those of
+ * n1k_strfn_eval. */
+n1k_status n1k_strfn_eval_device(int device, const char *term_text, size_t len, uint64_t n, const uint64_t *offsets,
+                                 const char *bytes, uint8_t *out_bits, uint64_t *out_left_to_host);
+/* out[0] dictionary strings evaluated on the device so far, out[1] on the host, out[2] distinct string-function
+ * predicates of the plan, out[3] the number of new dictionary entries from which the device route is taken */
+n1k_status n1k_strfn_stats(const n1k_handle *h, uint64_t out[4]);
+
 /* ------------------------------------------------- multi-GPU (one per rank) -- */
 
 /*

@@ -85,6 +85,7 @@ SYMBOLS = [
     "n1k_like_match", "n1k_like_match_device", "n1k_like_stats",
     "n1k_coll_eval", "n1k_coll_eval_device", "n1k_coll_stats",
     "n1k_in_match", "n1k_in_match_device", "n1k_in_stats",
+    "n1k_strfn_eval", "n1k_strfn_eval_device", "n1k_strfn_stats",
 ]
 
 _lib = None
@@ -244,6 +245,14 @@ def lib():
                                           C.POINTER(C.c_uint64)]
         L.n1k_in_stats.restype = C.c_int
         L.n1k_in_stats.argtypes = [H, C.POINTER(C.c_uint64 * 4)]
+    if hasattr(L, "n1k_strfn_eval"):  # (idem)
+        L.n1k_strfn_eval.restype = C.c_int
+        L.n1k_strfn_eval.argtypes = [C.c_char_p, C.c_size_t, C.c_uint64, C.c_void_p, C.c_char_p, C.c_void_p]
+        L.n1k_strfn_eval_device.restype = C.c_int
+        L.n1k_strfn_eval_device.argtypes = [C.c_int, C.c_char_p, C.c_size_t, C.c_uint64, C.c_void_p, C.c_char_p, C.c_void_p,
+                                            C.POINTER(C.c_uint64)]
+        L.n1k_strfn_stats.restype = C.c_int
+        L.n1k_strfn_stats.argtypes = [H, C.POINTER(C.c_uint64 * 4)]
     L.n1k_abi_version.restype = C.c_int
     L.n1k_device_count.restype = C.c_int
     _lib = L

@@ -69,6 +69,11 @@ bool to_operand(n1k_handle* h, const Expr* e, Operand& o, PlanError& err) {
     uint32_t op;
     if (e->kind == EK::Func) {
         const std::string& f = e->fname;
+        if (strfn_name(f)) {  // (its value is a new string per row, not a dictionary code: only a term's predicate is tabulated)
+            err.unsupported = true;
+            err.msg = "string function '" + f + "' used as a value (a group key, an aggregate's operand, an operand of arithmetic or of a comparison with a path): only a Filter / HAVING term over it runs on the device";
+            return false;
+        }
         op = f == "round" ? AR_ROUND : f == "trunc" ? AR_TRUNC : f == "abs" ? AR_ABS : f == "ceil" ? AR_CEIL
              : f == "floor" ? AR_FLOOR : f == "sign" ? AR_SIGN : f == "sqrt" ? AR_SQRT : f == "greatest" ? AR_GREATEST : AR_LEAST;
         n1k_handle::Derived d{};
@@ -182,6 +187,18 @@ bool compile_cond(n1k_handle* h, const Expr* e, PlanError& err) {
         P.logic[P.nlogic++] = LogicOp{op, arg};
         return true;
     };
+    // The fourth kind of the match table: a term over string functions of one leaf path (n1k_strfn.h).  Like the three
+    // below: compiled once per plan, evaluated once per distinct dictionary entry; equal programs share predicate and bit.
+    if (strfn_term(e)) {
+        const Expr* path = nullptr;
+        const int ix = h->match.add_strfn(e, path, err);
+        if (ix < 0 || !push_term(TERM_STRFN, path, nullptr, nullptr)) return false;
+        Operand& b = P.terms[P.nterms - 1].b;
+        b.is_const = 1;
+        b.ctag = T_STRING;
+        b.cpayload = (uint64_t)ix;
+        return true;
+    }
     switch (e->kind) {
         case EK::And:
         case EK::Or:
@@ -213,7 +230,7 @@ bool compile_cond(n1k_handle* h, const Expr* e, PlanError& err) {
         case EK::Between:
             h->need_rank = true;
             return push_term(TERM_BETWEEN, e->ch[0].get(), e->ch[1].get(), e->ch[2].get());
-        // The three kinds of the match table: the predicate is compiled once per plan and evaluated once per
+        // The three earlier kinds of the match table: the predicate is compiled once per plan and evaluated once per
         // distinct dictionary entry (ensure_match_table); the row test reads its bit.  Two terms with the same text share
         // everything.  b.cpayload holds the predicate's index until MatchTable::finalize_bits puts its bit there (pad
         // stays 0: not a dictionary string, bind_columns leaves it alone).
@@ -1221,6 +1238,17 @@ n1k_status n1k_in_stats(const n1k_handle* h, uint64_t out[4]) {
     out[1] = h->match.counts[MK_IN].dev;
     out[2] = h->match.counts[MK_IN].host;
     out[3] = kInDeviceThreshold;
+    return N1K_OK;
+    });
+}
+
+n1k_status n1k_strfn_stats(const n1k_handle* h, uint64_t out[4]) {
+    return guarded(h, [&]() -> n1k_status {
+    if (!h || !out) return N1K_INVALID;
+    out[0] = h->match.counts[MK_STRFN].dev;
+    out[1] = h->match.counts[MK_STRFN].host;
+    out[2] = h->match.strfns.size();
+    out[3] = kStrFnDeviceThreshold;
     return N1K_OK;
     });
 }

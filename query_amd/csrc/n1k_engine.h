@@ -28,6 +28,7 @@
 #include "n1k_in.h"
 #include "n1k_like.h"
 #include "n1k_plan.h"
+#include "n1k_strfn.h"
 
 
 using namespace n1k;
@@ -68,20 +69,22 @@ struct MatchScratch {
     DevBuf<uint8_t> left;    // MK_COUNT * n: the kernels' left-to-host flags, kind k at k * n
     DevBuf<uint8_t> bits;    // MK_COUNT * n: the kernels' bits where they do not go straight into the table, kind k at k * n
     DevBuf<uint8_t> progs;   // CollProg[]
+    DevBuf<uint8_t> sprogs;  // StrFnProg[]
     void release() {
         bytes.release();
         off.release();
         left.release();
         bits.release();
         progs.release();
+        sprogs.release();
     }
 };
 
 // the kinds of predicate that own bits of a match-table entry
-enum MatchKind { MK_LIKE, MK_COLL, MK_IN, MK_COUNT };
+enum MatchKind { MK_LIKE, MK_COLL, MK_IN, MK_STRFN, MK_COUNT };
 
 // The match table ("The match table"): one byte per dictionary code, a predicate evaluated once per distinct
-// entry, one bit per row in the scan.  The plan's compiled predicates of the three kinds, the constants of its IN lists and
+// entry, one bit per row in the scan.  The plan's compiled predicates of the four kinds, the constants of its IN lists and
 // the table in device memory: built before the first launch that needs it and EXTENDED when the dictionary has grown
 // (ensure_match_table), kept across n1k_reset, freed with the handle.
 struct MatchTable {
@@ -89,6 +92,8 @@ struct MatchTable {
     std::vector<CollPred> preds;        // distinct ANY / EVERY predicates: predicate q owns bit coll_top - q
     std::vector<InList> lists;          // distinct IN lists; those that hold strings own the bits above the patterns', in order of first use
     uint32_t string_lists = 0;          // lists that hold strings
+    std::vector<StrFnPred> strfns;      // distinct string-function predicates: predicate q owns the bit above the lists', in order of first use
+    uint32_t strfn_first = 0;           // ... which is bit strfn_first + q (finalize_bits)
     uint32_t coll_top = kMatchBits - 1; // (the diagnostic entry points evaluate one predicate into bit 0)
     std::vector<double> in_numbers;     // the numbers of all lists, list by list (Program::in_nums)
     InTableHost in_table;               // the strings of all lists in one open-addressed table
@@ -104,13 +109,15 @@ struct MatchTable {
     int add_like(const std::string& pattern, PlanError& err);
     int add_coll(const Expr* e, PlanError& err);
     int add_in(const Expr* e, PlanError& err);
+    int add_strfn(const Expr* e, const Expr*& path, PlanError& err);  // (path: the leaf path the term reads)
     void finalize_bits(Program& P);  // once the condition is compiled: the bit of every predicate, into the terms that read them
     void clear_plan() {
         patterns.clear();
         preds.clear();
         lists.clear();
+        strfns.clear();
         in_numbers.clear();
-        string_lists = 0;
+        string_lists = strfn_first = 0;
     }
     void release() {
         d_bits.release();
@@ -252,7 +259,7 @@ struct n1k_handle {
     size_t rank_built_for = (size_t)-1;
     DevBuf<uint32_t> d_rank;
 
-    MatchTable match;  // LIKE, ANY / EVERY, IN: the plan's predicates over dictionary entries and their table
+    MatchTable match;  // LIKE, ANY / EVERY, IN, string functions: the plan's predicates over dictionary entries and their table
 
     // compiled program (column pointers are patched per batch)
     Program prog{};
@@ -373,7 +380,7 @@ n1k_status validate_batch(n1k_handle* h, const n1k_batch* b);
 uint64_t batch_bytes_per_row(const n1k_handle* h);
 void default_value(const AggDef& d, n1k_value& v, n1k_partial& p);
 
-// n1k_matchtable.cpp: the match table of the LIKE, ANY / EVERY and IN terms, built and extended before the launches that read it
+// n1k_matchtable.cpp: the match table of the LIKE, ANY / EVERY, IN and string-function terms, built and extended before the launches that read it
 n1k_status ensure_match_table(n1k_handle* h);
 
 // n1k_scan.cpp: one batch through Filter + InitialGroup (kernel choice), Filter-only batches, staging of host batches

@@ -127,6 +127,7 @@ N1K_DEV void eval_term(const Program& P, const Term& t, const uint64_t (&row)[R]
             break;
         case TERM_LIKE:    // Like.Apply (expression/comp_like.go:68-88) with a STRING constant pattern: MISSING, NULL for a non-string,
                            // else the pattern's bit of the string's entry in the match table
+        case TERM_STRFN:   // a term over string functions (expression/func_str.go): the same, with the predicate's bit
         case TERM_COLL: {  // Any / Every / AnyEvery.Evaluate (expression/coll_any.go:42-85) over a column: MISSING, NULL for a
                            // non-array (collEval, coll_util.go:27-35, 49-57), else the predicate's bit of the array's entry
             const uint32_t bit = 1u << (uint32_t)t.b.cpayload;
@@ -1014,6 +1015,7 @@ N1K_DEV bool fast_term_true(const FastTerm& t, uint32_t tg, uint64_t p, const ui
         case TERM_IS_NOT_VALUED: return tg <= T_NULL;
         case TERM_STR_EQ: return tg == T_STRING && p == t.cpayload;
         case TERM_LIKE:
+        case TERM_STRFN:
         case TERM_COLL: {
             if (tg != term_table_tag(t.op) || (uint32_t)p >= t.match_n) return false;
             const uint8_t b = like_lds ? like_lds[(uint32_t)p] : t.match_bits[(uint32_t)p];

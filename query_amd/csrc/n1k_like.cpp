@@ -70,7 +70,9 @@ struct LikeRunes {
     }
 };
 
-void decode_runes(const uint8_t* s, uint32_t n, std::vector<uint32_t>& out) {
+}  // namespace
+
+void like_decode_runes(const uint8_t* s, uint32_t n, std::vector<uint32_t>& out) {
     out.clear();
     for (uint32_t i = 0; i < n;) {
         const uint32_t l = like_utf8_valid_at(s, n, i);
@@ -86,13 +88,15 @@ void decode_runes(const uint8_t* s, uint32_t n, std::vector<uint32_t>& out) {
     }
 }
 
-}  // namespace
+bool like_match_runes(const uint8_t* prog, uint32_t plen, bool anchor_end, const uint32_t* r, uint32_t n) {
+    return like_match(prog, plen, anchor_end, LikeRunes{r, n});
+}
 
 bool like_match_host(const LikePattern& p, const uint8_t* s, size_t n) {
     if (like_utf8_valid(s, (uint32_t)n))
         return like_match(p.prog.data(), (uint32_t)p.prog.size(), p.anchor_end, LikeBytes{s, (uint32_t)n});
     std::vector<uint32_t> r;
-    decode_runes(s, (uint32_t)n, r);
+    like_decode_runes(s, (uint32_t)n, r);
     return like_match(p.prog.data(), (uint32_t)p.prog.size(), p.anchor_end, LikeRunes{r.data(), (uint32_t)r.size()});
 }
 
@@ -106,7 +110,7 @@ void like_match_block_host(const std::vector<LikePattern>& pats, uint64_t n, con
             for (size_t p = 0; p < pats.size(); p++)
                 b |= (uint8_t)(like_match(pats[p].prog.data(), (uint32_t)pats[p].prog.size(), pats[p].anchor_end, LikeBytes{s, len}) ? 1u << p : 0u);
         } else {
-            decode_runes(s, len, r);
+            like_decode_runes(s, len, r);
             for (size_t p = 0; p < pats.size(); p++)
                 b |= (uint8_t)(like_match(pats[p].prog.data(), (uint32_t)pats[p].prog.size(), pats[p].anchor_end, LikeRunes{r.data(), (uint32_t)r.size()}) ? 1u << p : 0u);
         }

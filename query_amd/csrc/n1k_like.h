@@ -30,7 +30,7 @@ namespace n1k {
 enum : uint8_t { LIKE_OP_MANY = 0, LIKE_OP_ONE = 1, LIKE_OP_LIT = 2 };
 
 constexpr uint32_t kMatchBits = 8;          // bits of a match-table entry: one byte per dictionary code carries every LIKE pattern,
-                                            // ANY / EVERY predicate and IN list of strings of a plan ("The match table")
+                                            // ANY / EVERY predicate, IN list of strings and string-function predicate of a plan ("The match table")
 constexpr uint32_t kLikeDevProgBytes = 240;  // a longer program stays with the host matcher
 constexpr uint32_t kLikeDevMaxLen = 128;     // bytes of a dictionary string the device kernel takes
 // New dictionary entries below this count are matched on the host and copied; from it on they go through
@@ -190,6 +190,9 @@ struct LikePattern {
 bool like_compile(const char* pattern, size_t len, LikePattern& out);
 // one string against one pattern, any bytes (the host matcher: invalid UTF-8 decodes byte by byte, as Go does)
 bool like_match_host(const LikePattern& p, const uint8_t* s, size_t n);
+// Go's view of any bytes: code points, every byte that begins no valid encoding one U+FFFD; and a program over them
+void like_decode_runes(const uint8_t* s, uint32_t n, std::vector<uint32_t>& out);
+bool like_match_runes(const uint8_t* prog, uint32_t plen, bool anchor_end, const uint32_t* r, uint32_t n);
 // bits[i] |= OR over patterns p of (match << p), for the n strings bytes[offsets[i] - offsets[0] ..)
 void like_match_block_host(const std::vector<LikePattern>& pats, uint64_t n, const uint64_t* offsets, const uint8_t* bytes, uint8_t* bits);
 // false: some pattern's program is longer than the device kernel takes

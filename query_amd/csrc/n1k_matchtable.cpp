@@ -1,5 +1,5 @@
 // n1k_matchtable.cpp — the match table on the host side ("The match table"): the plan's predicates and their
-// bits (MatchTable's adders, finalize_bits), ONE driver that takes a block of dictionary entries through every kind's
+// bits of the four kinds (MatchTable's adders, finalize_bits), ONE driver that takes a block of dictionary entries through every kind's
 // route (match_block), the handle's table around it (ensure_match_table) and the diagnostic entry points of the C ABI.
 #include "n1k_engine.h"
 
@@ -10,11 +10,11 @@ using namespace n1k_eng;
 
 namespace n1k_eng {
 
-// The eight bits of an entry are shared by the three kinds: one more predicate that needs a bit, or refused.
+// The eight bits of an entry are shared by the four kinds: one more predicate that needs a bit, or refused.
 static bool take_bit(const MatchTable& M, PlanError& err) {
-    if (M.patterns.size() + M.preds.size() + M.string_lists < kMatchBits) return true;
+    if (M.patterns.size() + M.preds.size() + M.string_lists + M.strfns.size() < kMatchBits) return true;
     err.unsupported = true;
-    err.msg = "more than " + std::to_string(kMatchBits) + " distinct LIKE patterns, ANY / EVERY predicates and IN lists of strings in one plan";
+    err.msg = "more than " + std::to_string(kMatchBits) + " distinct LIKE patterns, ANY / EVERY predicates, IN lists of strings and string-function predicates in one plan";
     return false;
 }
 
@@ -62,15 +62,28 @@ int MatchTable::add_in(const Expr* e, PlanError& err) {
     return (int)lists.size() - 1;
 }
 
+int MatchTable::add_strfn(const Expr* e, const Expr*& path, PlanError& err) {
+    StrFnPred sp;
+    if (!strfn_compile(e, sp.prog, path, err)) return -1;
+    for (size_t ix = 0; ix < strfns.size(); ix++)  // (equal programs, whatever their text: ("a" < f(x)) and (f(x) > "a") share)
+        if (!memcmp(&strfns[ix].prog, &sp.prog, sizeof sp.prog)) return (int)ix;
+    if (!take_bit(*this, err)) return -1;
+    strfns.push_back(sp);
+    return (int)strfns.size() - 1;
+}
+
 // THE bit scheme: LIKE pattern p owns bit p; the IN lists that hold strings own the next bits above, in the order of their
-// first use; collection predicate q owns bit coll_top - q, from bit 7 down.  A TERM_IN carries its list's flags beside the mask.
+// first use; the string-function predicates the bits above those, in the order of their first use; collection predicate q
+// owns bit coll_top - q, from bit 7 down.  A TERM_IN carries its list's flags beside the mask.
 void MatchTable::finalize_bits(Program& P) {
     uint32_t in_bit = (uint32_t)patterns.size();
     for (InList& l : lists)
         if (!l.strings.empty()) l.mask = (uint8_t)(1u << in_bit++);
+    strfn_first = in_bit;
     for (uint32_t t = 0; t < P.nterms; t++) {
         uint64_t& ix = P.terms[t].b.cpayload;  // the predicate's index (compile_cond) -> what the row test reads
         if (P.terms[t].op == TERM_COLL) ix = coll_top - ix;
+        if (P.terms[t].op == TERM_STRFN) ix = strfn_first + ix;
         if (P.terms[t].op == TERM_IN) {
             const InList& l = lists[(size_t)ix];
             ix = l.mask | (l.has_true ? IN_HAS_TRUE : 0u) | (l.has_false ? IN_HAS_FALSE : 0u) | (l.has_null ? IN_HAS_NULL : 0u) | (l.empty ? IN_EMPTY : 0u);
@@ -112,7 +125,8 @@ bool kind_present(const MatchTable& M, int k) {
     switch (k) {
         case MK_LIKE: return !M.patterns.empty();
         case MK_COLL: return !M.preds.empty();
-        default: return M.string_lists != 0;
+        case MK_IN: return M.string_lists != 0;
+        default: return !M.strfns.empty();
     }
 }
 
@@ -130,7 +144,8 @@ void kind_host(const MatchTable& M, int k, uint64_t n, const uint64_t* off, cons
     switch (k) {
         case MK_LIKE: like_match_block_host(M.patterns, n, off, bytes, bits); break;
         case MK_COLL: coll_eval_block_host(M.preds, M.coll_top, n, off, bytes, bits); break;
-        default: in_match_block_host(M.in_table.view(), n, off, bytes, bits);
+        case MK_IN: in_match_block_host(M.in_table.view(), n, off, bytes, bits); break;
+        default: strfn_eval_block_host(M.strfns, M.strfn_first, n, off, bytes, bits);
     }
 }
 
@@ -139,7 +154,8 @@ hipError_t kind_launch(MatchTable& M, Routes& R, int k, const EntryBlockArgs& bl
     switch (k) {
         case MK_LIKE: R.like.blk = blk; return launch_like_match(R.like, st);
         case MK_COLL: return launch_coll_match(CollKernelArgs{blk, (uint32_t)M.preds.size(), M.coll_top, (const CollProg*)M.scratch.progs.p}, st);
-        default: return launch_in_match(InKernelArgs{blk, in_table_at(M.in_table, M.d_in_table.p)}, st);
+        case MK_IN: return launch_in_match(InKernelArgs{blk, in_table_at(M.in_table, M.d_in_table.p)}, st);
+        default: return launch_strfn_match(StrFnKernelArgs{blk, (uint32_t)M.strfns.size(), M.strfn_first, (const StrFnProg*)M.scratch.sprogs.p}, st);
     }
 }
 
@@ -198,6 +214,11 @@ hipError_t match_block(MatchTable& M, const EntryBlock& B, Routes& R, hipStream_
             for (size_t q = 0; q < M.preds.size(); q++)
                 HIP_RET(hipMemcpy(S.progs.p + q * sizeof(CollProg), &M.preds[q].prog, sizeof(CollProg), hipMemcpyHostToDevice));
         }
+        if (R.r[MK_STRFN] == R_DEVICE) {
+            HIP_RET(S.sprogs.ensure(M.strfns.size() * sizeof(StrFnProg)));
+            for (size_t q = 0; q < M.strfns.size(); q++)
+                HIP_RET(hipMemcpy(S.sprogs.p + q * sizeof(StrFnProg), &M.strfns[q].prog, sizeof(StrFnProg), hipMemcpyHostToDevice));
+        }
         left.resize(MK_COUNT * n);
         kbits.resize(direct ? 0 : MK_COUNT * n);
         for (int k = 0; k < MK_COUNT; k++)
@@ -246,14 +267,15 @@ namespace n1k_eng {
 
 // The handle's table.  Same rules as the rank table (ensure_rank), except that a grown dictionary EXTENDS it: the entries
 // of the old codes stay as they are (equal bytes, equal code), only the new codes are evaluated — per kind on the host
-// below kLikeDeviceThreshold / kCollDeviceThreshold / kInDeviceThreshold of them, by the kernels from there on.
+// below kLikeDeviceThreshold / kCollDeviceThreshold / kInDeviceThreshold / kStrFnDeviceThreshold of them, by the kernels
+// from there on.
 n1k_status ensure_match_table(n1k_handle* h) {
     Program& P = h->prog;
     MatchTable& M = h->match;
     HIP_TRY(h, upload_in_constants(M, h->stream));
     P.in_nums = M.in_numbers.empty() ? nullptr : M.d_in_nums.p;  // (bound also when the plan holds no kind of the table)
     P.in_n = (uint32_t)M.in_numbers.size();
-    if (M.patterns.empty() && M.preds.empty() && !M.string_lists) {
+    if (M.patterns.empty() && M.preds.empty() && !M.string_lists && M.strfns.empty()) {
         P.match_bits = nullptr;
         P.match_n = 0;
         return N1K_OK;
@@ -277,7 +299,7 @@ n1k_status ensure_match_table(n1k_handle* h) {
         for (size_t i = 0; i < cnt; i++) off[i + 1] = off[i] + h->dict[first + i].size();
         std::vector<uint8_t> bytes(off[cnt] + 1), bits(cnt);
         for (size_t i = 0; i < cnt; i++) memcpy(bytes.data() + off[i], h->dict[first + i].data(), h->dict[first + i].size());
-        const bool want_dev[MK_COUNT] = {cnt >= kLikeDeviceThreshold, cnt >= kCollDeviceThreshold, cnt >= kInDeviceThreshold};
+        const bool want_dev[MK_COUNT] = {cnt >= kLikeDeviceThreshold, cnt >= kCollDeviceThreshold, cnt >= kInDeviceThreshold, cnt >= kStrFnDeviceThreshold};
         Routes R;
         choose_routes(M, want_dev, R);
         // (d_bits + first: entries no launch has been told about yet, match_n grows below)
@@ -293,7 +315,7 @@ n1k_status ensure_match_table(n1k_handle* h) {
 
 // ---- the diagnostic entry points: one kind's matcher on its own, over a table of that one predicate (bit 0)
 
-// what all four check of their arguments (device: the kernels count entries in 32 bits)
+// what all eight check of their arguments (device: the kernels count entries in 32 bits)
 static bool block_args_ok(const char* text, size_t text_len, uint64_t n, const uint64_t* offsets, const char* bytes, const uint8_t* out_bits,
                           bool device) {
     if ((text_len && !text) || (n && (!offsets || !out_bits)) || (device && n >= 0xFFFFFFF0ull)) return false;
@@ -339,7 +361,21 @@ static n1k_status in_parse(const char* text, size_t len, MatchTable& M) {
     return N1K_OK;
 }
 
-// All six: the block through the driver with the one kind `parse` compiles — through its host matcher, or (on_device) through
+// one whole term over a path -> program; N1K_UNSUPPORTED for what n1k_create refuses in a plan, N1K_INVALID for text that
+// is no such term
+static n1k_status strfn_parse(const char* text, size_t len, MatchTable& M) {
+    PlanError err;
+    const std::string src(text ? text : "", len);
+    auto e = parse_expression(src, err);
+    if (!e) return err.unsupported ? N1K_UNSUPPORTED : N1K_INVALID;
+    if (!strfn_term(e.get())) return N1K_INVALID;
+    M.strfns.resize(1);
+    const Expr* path = nullptr;
+    if (!strfn_compile(e.get(), M.strfns[0].prog, path, err)) return err.unsupported ? N1K_UNSUPPORTED : N1K_INVALID;
+    return N1K_OK;
+}
+
+// All eight: the block through the driver with the one kind `parse` compiles — through its host matcher, or (on_device) through
 // its kernel on `device` with scratch of its own; a LIKE program the kernel does not take sends every string to the host.
 static n1k_status match_alone(int kind, n1k_status (*parse)(const char*, size_t, MatchTable&), bool on_device, int device, const char* text,
                               size_t text_len, uint64_t n, const uint64_t* offsets, const char* bytes, uint8_t* out_bits, uint64_t* out_left_to_host) {
@@ -385,6 +421,15 @@ n1k_status n1k_coll_eval(const char* predicate_text, size_t len, uint64_t n, con
 n1k_status n1k_coll_eval_device(int device, const char* predicate_text, size_t len, uint64_t n, const uint64_t* offsets, const char* bytes,
                                 uint8_t* out_bits, uint64_t* out_left_to_host) {
     return match_alone(MK_COLL, coll_parse, true, device, predicate_text, len, n, offsets, bytes, out_bits, out_left_to_host);
+}
+
+n1k_status n1k_strfn_eval(const char* term_text, size_t len, uint64_t n, const uint64_t* offsets, const char* bytes, uint8_t* out_bits) {
+    return match_alone(MK_STRFN, strfn_parse, false, 0, term_text, len, n, offsets, bytes, out_bits, nullptr);
+}
+
+n1k_status n1k_strfn_eval_device(int device, const char* term_text, size_t len, uint64_t n, const uint64_t* offsets, const char* bytes,
+                                 uint8_t* out_bits, uint64_t* out_left_to_host) {
+    return match_alone(MK_STRFN, strfn_parse, true, device, term_text, len, n, offsets, bytes, out_bits, out_left_to_host);
 }
 
 n1k_status n1k_in_match(const char* list_text, size_t len, uint64_t n, const uint64_t* offsets, const char* bytes, uint8_t* out_bits) {

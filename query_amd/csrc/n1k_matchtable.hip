@@ -16,9 +16,14 @@
 //   InMatcher (in_match_kernel): in_lookup (n1k_in.h) — hash the entry's bytes, probe the plan's table of IN-list string
 //     constants, compare the candidate's bytes — gives the mask of the lists that hold the entry.  Every entry is its
 //     business; bytes are bytes, so only an entry beyond the limit is the host's.
+//   StrFnMatcher (strfn_match_kernel): strfn_eval (n1k_strfn.h) per predicate — the view {begin, end, case mode} over the
+//     entry's bytes where they lie, no copy — bit first_bit + q = predicate q.  Every entry is its business.  An entry
+//     that holds one of the four runes with an ASCII case mapping under the matching case step, or that is not valid UTF-8
+//     under LIKE (strfn_needs_host), is flagged for the host.
 #include <hip/hip_runtime.h>
 #include "n1k_coll.h"
 #include "n1k_in.h"
+#include "n1k_strfn.h"
 
 namespace n1k {
 
@@ -73,6 +78,26 @@ struct InMatcher {
     static __device__ uint8_t match(const Params&, const Args& A, const uint8_t* s, uint32_t len, bool&) { return in_lookup(A.tab, s, len); }
 };
 
+struct StrFnMatcher {
+    using Args = StrFnKernelArgs;
+    struct Params { StrFnProg progs[kMatchBits]; };
+    static constexpr uint32_t kMaxLen = kStrFnDevMaxLen;
+    static __device__ void stage(Params& par, const Args& A, uint32_t tid) {
+        const uint32_t* src = (const uint32_t*)A.progs;
+        uint32_t* dst = (uint32_t*)&par.progs[0];
+        for (uint32_t k = tid; k < A.nprog * (uint32_t)(sizeof(StrFnProg) / 4); k += kMatchBlock) dst[k] = src[k];
+    }
+    static __device__ bool wants(const uint8_t*, uint64_t) { return true; }
+    static __device__ uint8_t match(const Params& par, const Args& A, const uint8_t* s, uint32_t len, bool& left) {
+        uint8_t bits = 0;
+        for (uint32_t q = 0; q < A.nprog; q++) {
+            if (strfn_needs_host(par.progs[q], s, len)) left = true;
+            else bits |= (uint8_t)(strfn_eval(par.progs[q], s, len) ? 1u << (A.first_bit + q) : 0u);
+        }
+        return bits;
+    }
+};
+
 template <class Matcher>
 __global__ __launch_bounds__(256) void match_table_kernel(const typename Matcher::Args A) {
     constexpr uint32_t kSlab = 64 * Matcher::kMaxLen;  // bytes 64 entries within the limit span at most
@@ -116,6 +141,7 @@ __global__ __launch_bounds__(256) void match_table_kernel(const typename Matcher
 constexpr auto like_match_kernel = match_table_kernel<LikeMatcher>;
 constexpr auto coll_match_kernel = match_table_kernel<CollMatcher>;
 constexpr auto in_match_kernel = match_table_kernel<InMatcher>;
+constexpr auto strfn_match_kernel = match_table_kernel<StrFnMatcher>;
 
 hipError_t launch_like_match(const LikeKernelArgs& A, hipStream_t st) {
     if (A.blk.n == 0) return hipSuccess;
@@ -137,6 +163,14 @@ hipError_t launch_in_match(const InKernelArgs& A, hipStream_t st) {
     if (A.tab.nconst == 0 || !A.tab.slots) return hipErrorInvalidValue;
     const uint32_t grid = (A.blk.n + kMatchBlock - 1) / kMatchBlock;
     hipLaunchKernelGGL(in_match_kernel, dim3(grid), dim3(kMatchBlock), 0, st, A);
+    return hipGetLastError();
+}
+
+hipError_t launch_strfn_match(const StrFnKernelArgs& A, hipStream_t st) {
+    if (A.blk.n == 0 || A.nprog == 0) return hipSuccess;
+    if (A.nprog > kMatchBits || A.first_bit + A.nprog > kMatchBits || !A.progs) return hipErrorInvalidValue;
+    const uint32_t grid = (A.blk.n + kMatchBlock - 1) / kMatchBlock;
+    hipLaunchKernelGGL(strfn_match_kernel, dim3(grid), dim3(kMatchBlock), 0, st, A);
     return hipGetLastError();
 }
 

@@ -394,6 +394,29 @@ struct EParser {
                     if (e->ch.size() < 2) return bad(w + " takes at least 2 arguments");
                     return e;
                 }
+                // String functions (expression/func_str.go; registry names func_registry.go:148-153 for the positions): a
+                // node like the numeric functions'.  What a term may do with them is decided where it is compiled
+                // (strfn_compile, n1k_strfn.cpp).
+                const bool str_unary = w == "lower" || w == "upper", str_trim = w == "trim" || w == "ltrim" || w == "rtrim";
+                const bool str_binary = w == "contains" || w == "position" || w == "pos" || w == "position0" || w == "pos0" ||
+                                        w == "position1" || w == "pos1";
+                if ((str_unary || str_trim || str_binary) && lx.toks[p + 1].kind == TK::LParen) {
+                    p += 2;
+                    auto e = mk(EK::Func);
+                    e->fname = w;
+                    for (;;) {
+                        auto a = primary();
+                        if (!a) return nullptr;
+                        e->ch.push_back(std::move(a));
+                        if (cur().kind == TK::Comma) { p++; continue; }
+                        break;
+                    }
+                    if (cur().kind != TK::RParen) return bad("expected ) in " + w);
+                    p++;
+                    const size_t minargs = str_binary ? 2 : 1, maxargs = str_unary ? 1 : 2;
+                    if (e->ch.size() < minargs || e->ch.size() > maxargs) return bad(w + " takes " + std::to_string(minargs) + (maxargs > minargs ? " or 2" : "") + " arguments");
+                    return e;
+                }
                 if ((w == "any" || w == "every") && lx.toks[p + 1].kind != TK::LParen) return collection();
                 return unsupported("function or keyword '" + w + "'");
             }

@@ -27,7 +27,8 @@ enum class EK {
            // coll_any_every.go): ch[0] the binding expression, coll_* the rest
     In,    // (a in [c, c, ...]), expression/coll_in.go, over a constant list: ch[0] the left operand, ch[1..] the elements
            // (Const), `text` the bracketed list as the stringer wrote it; NOT IN arrives as (not (a in [...]))
-    Func  // numeric functions of one or two arguments (expression/func_num.go): fname
+    Func  // numeric functions of one or two arguments (expression/func_num.go) and the string functions a term may hold
+          // (expression/func_str.go; n1k_strfn.h): fname
 };
 
 struct Expr {
@@ -40,7 +41,8 @@ struct Expr {
     // Path
     std::string text;        // exact stringer text, e.g. (`default`.`price`)
     // Func
-    std::string fname;       // round | trunc | abs | ceil | floor | sign | sqrt
+    std::string fname;       // round | trunc | abs | ceil | floor | sign | sqrt | greatest | least | lower | upper | trim | ltrim |
+                             // rtrim | contains | position[0|1] | pos[0|1]
     // Coll: `text` is the whole term as the stringer wrote it.  The SATISFIES tree is kept apart from ch: its paths name
     // the bound variable, not the row, so collect_paths must not meet them.
     uint32_t coll_mode = 0;  // COLL_ANY | COLL_EVERY | COLL_ANY_EVERY (n1k_coll.h)

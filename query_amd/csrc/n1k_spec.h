@@ -111,6 +111,7 @@ N1K_DEV bool spec_term_true(int t, const FastArgs& F, const SpecMatch& K, uint32
         case TERM_IS_NOT_VALUED: return tg <= T_NULL;
         case TERM_STR_EQ: return tg == T_STRING && p == F.terms[t].cpayload;
         case TERM_LIKE:
+        case TERM_STRFN:
         case TERM_COLL: {  // one bit of the match table (a string's entry, an array's); a code the table does not cover is not read
             if (tg != term_table_tag(op) || (uint32_t)p >= F.terms[t].match_n) return false;
             const uint8_t b = K.in_lds ? K.lds[(uint32_t)p] : F.terms[t].match_bits[(uint32_t)p];

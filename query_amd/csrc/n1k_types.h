@@ -83,14 +83,16 @@ enum : uint32_t {
                        // b.cpayload = the pattern's index in the plan (its bit)
     TERM_COLL,         // ANY / EVERY / ANY AND EVERY v IN a SATISFIES ... END (expression/coll_any.go, coll_every.go,
                        // coll_any_every.go): the same bit test over the same table, for an ARRAY's entry; b.cpayload = its bit
-    TERM_IN            // a IN [constants] (expression/coll_in.go:61-91).  b.cpayload = the list's mask in a match-table entry
+    TERM_IN,           // a IN [constants] (expression/coll_in.go:61-91).  b.cpayload = the list's mask in a match-table entry
                        // (bits 0..7; 0: the list holds no string) | IN_* flags; c.cpayload = begin | end << 32, the list's
                        // range of Program::in_nums
+    TERM_STRFN         // a term over string functions of a (expression/func_str.go; n1k_strfn.h): LIKE's row test as it stands,
+                       // b.cpayload = the predicate's bit
 };
-// TERM_LIKE and TERM_COLL are one row test: MISSING stays MISSING, a value whose tag is not the expected one is NULL, else
+// TERM_LIKE, TERM_STRFN and TERM_COLL are one row test: MISSING stays MISSING, a value whose tag is not the expected one is NULL, else
 // the term's bit of the value's dictionary entry in the match table.  TERM_IN reads the same table for a STRING value (the
-// kernels that stage the table in LDS do so for all three) and answers the other tags from its numbers and flags.
-constexpr bool term_is_table_bit(uint32_t op) { return op == TERM_LIKE || op == TERM_COLL || op == TERM_IN; }
+// kernels that stage the table in LDS do so for all of them) and answers the other tags from its numbers and flags.
+constexpr bool term_is_table_bit(uint32_t op) { return op == TERM_LIKE || op == TERM_COLL || op == TERM_IN || op == TERM_STRFN; }
 constexpr uint32_t term_table_tag(uint32_t op) { return op == TERM_COLL ? (uint32_t)T_ARRAY : (uint32_t)T_STRING; }
 
 // TERM_IN: what the list holds besides strings and numbers (b.cpayload, FastTerm::match_mask)

@@ -348,6 +348,14 @@ class GpuFilterGroup:
         self._check(self._lib.n1k_in_stats(self._h, C.byref(out)))
         return {"lists": int(out[0]), "device_strings": int(out[1]), "host_strings": int(out[2]), "device_threshold": int(out[3])}
 
+    def strfn_stats(self) -> dict:
+        """How the string-function bits of this operator's match table were built: dictionary strings evaluated on the
+        device / on the host, distinct string-function predicates of the plan, and the number of new dictionary entries from
+        which the device route is taken."""
+        out = (C.c_uint64 * 4)()
+        self._check(self._lib.n1k_strfn_stats(self._h, C.byref(out)))
+        return {"device_strings": int(out[0]), "host_strings": int(out[1]), "predicates": int(out[2]), "device_threshold": int(out[3])}
+
     def reopen(self):
         self._check(self._lib.n1k_reset(self._h))
 
