@@ -2332,6 +2332,8 @@ __global__ __launch_bounds__(BLOCK) void agg_bins_kernel(const Program P, const 
 // float64 order image, strings through the bytewise rank of their code), not injective — a radix select finds the
 // image T of the (offset+limit)-th row, and only the groups with image <= T (the answer plus ties on the first
 // term) are compacted and copied to the host, which orders them exactly.  G = 6.4 M groups ship ~k rows, not 640 MB.
+// The image must be EQUAL on values that Collate ties — the later terms order those, so all of them have to be candidates:
+// -0.0, 0.0 and INT 0 tie, and -0.0 (what MIN / MAX return when it is a group's only float) gets the image of 0.0.
 N1K_DEV uint64_t order_image(const Program& P, uint64_t tag, uint64_t p, bool desc) {
     uint64_t cls, body = 0;
     switch ((uint32_t)(tag & 0xFF)) {
@@ -2340,7 +2342,7 @@ N1K_DEV uint64_t order_image(const Program& P, uint64_t tag, uint64_t p, bool de
         case T_FALSE: cls = 2; break;
         case T_TRUE: cls = 2; body = 1; break;
         case T_INT: cls = 3; body = f64_sortable((double)(int64_t)p) >> 3; break;
-        case T_FLOAT: cls = 3; body = f64_sortable(as_f64(p)) >> 3; break;
+        case T_FLOAT: cls = 3; body = f64_sortable(as_f64(as_f64(p) == 0.0 ? 0ull : p)) >> 3; break;  // (either zero: +0.0)
         case T_STRING: cls = 4; body = P.str_rank ? (uint64_t)P.str_rank[(uint32_t)p] : 0ull; break;
         case T_ARRAY: cls = 5; break;
         default: cls = 6; break;

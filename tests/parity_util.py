@@ -155,6 +155,10 @@ def collate_values(a, b) -> int:
     if ca == 2:
         return (a[0] == n1o.T_TRUE) - (b[0] == n1o.T_TRUE)
     x, y = a[1], b[1]
+    if ca == 3:  # NaN sorts first among the numbers, and NaN ties NaN (value/float.go:123-172)
+        xn, yn = x != x, y != y
+        if xn or yn:
+            return 0 if (xn and yn) else (-1 if xn else 1)
     return (x > y) - (x < y)
 
 
