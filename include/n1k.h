@@ -441,6 +441,11 @@ n1k_status n1k_strfn_eval_device(int device, const char *term_text, size_t len, 
  * predicates of the plan, out[3] the number of new dictionary entries from which the device route is taken */
 n1k_status n1k_strfn_stats(const n1k_handle *h, uint64_t out[4]);
 
+/* Diagnostics: the bytes of device memory that the handles, communicators and calls of this process hold at this moment.
+ * Exact (counted where the library allocates and frees, not read from the device, whose free memory moves under other
+ * processes' work): back at its earlier value once everything created since then has been destroyed. */
+uint64_t n1k_device_bytes_live(void);
+
 /* ------------------------------------------------- multi-GPU (one per rank) -- */
 
 /*

@@ -86,6 +86,7 @@ SYMBOLS = [
     "n1k_coll_eval", "n1k_coll_eval_device", "n1k_coll_stats",
     "n1k_in_match", "n1k_in_match_device", "n1k_in_stats",
     "n1k_strfn_eval", "n1k_strfn_eval_device", "n1k_strfn_stats",
+    "n1k_device_bytes_live",
 ]
 
 _lib = None
@@ -253,6 +254,9 @@ def lib():
                                             C.POINTER(C.c_uint64)]
         L.n1k_strfn_stats.restype = C.c_int
         L.n1k_strfn_stats.argtypes = [H, C.POINTER(C.c_uint64 * 4)]
+    if hasattr(L, "n1k_device_bytes_live"):  # (idem)
+        L.n1k_device_bytes_live.restype = C.c_uint64
+        L.n1k_device_bytes_live.argtypes = []
     L.n1k_abi_version.restype = C.c_int
     L.n1k_device_count.restype = C.c_int
     _lib = L

@@ -301,7 +301,7 @@ bool compile_plan(n1k_handle* h, PlanError& err) {
         if (!to_operand(h, pl.keys[k].get(), P.keys[k].src, err)) return false;
     P.naggs = (uint32_t)pl.aggs.size();
     uint32_t lds_w = 1, glob_w = 0;
-    if (h->opt_rep_row) {
+    if (h->opt.rep_row) {
         P.want_rep_row = 1;
         P.rep_lds_word = lds_w++;
     }
@@ -350,7 +350,7 @@ bool compile_plan(n1k_handle* h, PlanError& err) {
     P.lds_words = lds_w;
     P.glob_words = glob_w ? glob_w : 1;
     if (h->has_array_agg) {
-        if (h->opt_rep_row) { err.unsupported = true; err.msg = "array_agg with representative rows"; return false; }
+        if (h->opt.rep_row) { err.unsupported = true; err.msg = "array_agg with representative rows"; return false; }
         P.emit_packed_key = 1;
     }
     P.ncols = (uint32_t)(pl.paths.size() + h->derived.size());  // inputs, then derived columns
@@ -379,9 +379,9 @@ n1k_status ensure_device(n1k_handle* h) {
         HIP_TRY(h, hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
         h->own_stream = true;
     }
-    HIP_TRY(h, h->d_counters.ensure(kCounters));
-    h->d_errp = (uint32_t*)(h->d_counters.p + 12);
-    HIP_TRY(h, hipMemsetAsync(h->d_counters.p, 0, kCounters * sizeof(unsigned long long), h->stream));
+    HIP_TRY(h, h->groups.counters.ensure(kCounters));
+    h->groups.errp = (uint32_t*)(h->groups.counters.p + 12);
+    HIP_TRY(h, hipMemsetAsync(h->groups.counters.p, 0, kCounters * sizeof(unsigned long long), h->stream));
     h->device_ready = true;
     return N1K_OK;
 }
@@ -404,8 +404,8 @@ n1k_status ensure_rank(n1k_handle* h) {
     h->rank_built_for = n;
     h->prog.str_rank = h->d_rank.p;
     // groups that hold string MIN / MAX winners carry ranks of the old order: re-stamp them (n1k_kernels.hip)
-    if (rebuilt && h->has_minmax && h->layout_fixed && h->table.capacity && (h->row_base || h->merged_groups_bound))
-        HIP_TRY(h, launch_restamp_ranks(h->prog, h->table, h->stream));
+    if (rebuilt && h->has_minmax && h->layout_fixed && h->groups.table.capacity && (h->row_base || h->groups.merged_bound))
+        HIP_TRY(h, launch_restamp_ranks(h->prog, h->groups.table, h->stream));
     return N1K_OK;
 }
 
@@ -439,18 +439,18 @@ n1k_status fix_layout(n1k_handle* h, const n1k_batch* b) {
     // value tables for the numbers a TAGGED field cannot hold itself (n1k_device.h: wide_code)
     P.wide_int = P.wide_flt = nullptr;
     P.wide_bits = 0;
-    P.wide_count = h->d_counters.p + 13;
-    if (n_tag && h->opt_wide_values) {
+    P.wide_count = h->groups.counters.p + 13;
+    if (n_tag && h->opt.wide_values) {
         uint32_t wb = 4;
-        while ((1ull << wb) < h->opt_wide_values * 2 && wb < 30) wb++;
+        while ((1ull << wb) < h->opt.wide_values * 2 && wb < 30) wb++;
         wb = std::min(wb, tbits - 4);
         const size_t n = (size_t)1 << wb;
-        HIP_TRY(h, h->d_wide_int.ensure(n));
-        HIP_TRY(h, h->d_wide_flt.ensure(n));
-        HIP_TRY(h, hipMemsetAsync(h->d_wide_int.p, 0xFF, n * 8, h->stream));
-        HIP_TRY(h, hipMemsetAsync(h->d_wide_flt.p, 0xFF, n * 8, h->stream));
-        P.wide_int = h->d_wide_int.p;
-        P.wide_flt = h->d_wide_flt.p;
+        HIP_TRY(h, h->groups.wide_int.ensure(n));
+        HIP_TRY(h, h->groups.wide_flt.ensure(n));
+        HIP_TRY(h, hipMemsetAsync(h->groups.wide_int.p, 0xFF, n * 8, h->stream));
+        HIP_TRY(h, hipMemsetAsync(h->groups.wide_flt.p, 0xFF, n * 8, h->stream));
+        P.wide_int = h->groups.wide_int.p;
+        P.wide_flt = h->groups.wide_flt.p;
         P.wide_bits = wb;
     }
     // COUNT(DISTINCT) member words: [packed key : K1][class : 3][value : 61 - K1].  A layout of few bits keeps all
@@ -458,11 +458,11 @@ n1k_status fix_layout(n1k_handle* h, const n1k_batch* b) {
     {
         uint32_t total = 0;
         for (uint32_t k = 0; k < P.nkeys; k++) total += P.keys[k].bits;
-        h->nw_key_bits = P.nkeys == 0 ? 1u : (total <= 34 ? total : 24u);
-        h->nw_val_bits = 61 - h->nw_key_bits;
+        h->distinct.nw_key_bits = P.nkeys == 0 ? 1u : (total <= 34 ? total : 24u);
+        h->distinct.nw_val_bits = 61 - h->distinct.nw_key_bits;
         for (uint32_t a = 0; a < P.naggs; a++)
             if (P.aggs[a].distinct)
-                h->distinct_words[P.aggs[a].log_index] = h->opt_distinct_words && P.aggs[a].kind == AGG_COUNT;
+                h->distinct.words[P.aggs[a].log_index] = h->opt.distinct_words && P.aggs[a].kind == AGG_COUNT;
     }
     h->layout_fixed = true;
     return N1K_OK;
@@ -484,7 +484,7 @@ n1k_status alloc_table(n1k_handle* h, uint64_t capacity, GlobalTable& t, DevBuf<
 // Make sure the global table can take `incoming_rows` more rows worth of new groups (bounded by max_groups).
 n1k_status ensure_table(n1k_handle* h, uint64_t incoming_rows) {
     // groups <= rows pushed so far: an upper bound that needs no device round trip
-    uint64_t want_groups = std::min<uint64_t>(h->opt_max_groups, h->row_base + h->merged_groups_bound + incoming_rows);
+    uint64_t want_groups = std::min<uint64_t>(h->opt.max_groups, h->row_base + h->groups.merged_bound + incoming_rows);
     if (h->prog.nkeys == 0) want_groups = 1;
     else {
         // all keys dictionary coded: the key domain bounds the number of groups (|dict| + MISSING + NULL per key)
@@ -497,57 +497,51 @@ n1k_status ensure_table(n1k_handle* h, uint64_t incoming_rows) {
         if (all_dict && dom < (long double)want_groups) want_groups = (uint64_t)dom;
     }
     uint64_t cap = next_pow2(std::max<uint64_t>(want_groups * 2, 1024));
-    if (cap <= h->table.capacity) return N1K_OK;
-    if (!h->table.capacity) return alloc_table(h, cap, h->table, h->d_keys, h->d_acc, h->d_rep);
+    if (cap <= h->groups.table.capacity) return N1K_OK;
+    if (!h->groups.table.capacity) return alloc_table(h, cap, h->groups.table, h->groups.keys, h->groups.acc, h->groups.rep);
     // grow: rehash every occupied slot into a bigger table (keys keep their packed form)
     GlobalTable nt{};
     DevBuf<uint64_t> nk, na, nr;
     n1k_status st = alloc_table(h, cap, nt, nk, na, nr);
     if (st != N1K_OK) return st;
-    HIP_TRY(h, launch_rehash(h->prog, h->table, nt, h->d_errp, h->d_counters.p + 4, h->stream));
+    HIP_TRY(h, launch_rehash(h->prog, h->groups.table, nt, h->groups.errp, h->groups.counters.p + 4, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    h->d_keys.release();
-    h->d_acc.release();
-    h->d_rep.release();
-    h->d_keys = nk;
-    h->d_acc = na;
-    h->d_rep = nr;
-    h->table = nt;
+    h->groups.keys = std::move(nk);
+    h->groups.acc = std::move(na);
+    h->groups.rep = std::move(nr);
+    h->groups.table = nt;
     return N1K_OK;
 }
 
 // the same for a known number of groups (the partitioned path counts its groups before it inserts them)
 n1k_status ensure_table_groups(n1k_handle* h, uint64_t groups) {
-    if (groups > h->opt_max_groups)
-        return fail(h, N1K_OOM, "group table capacity exceeded: raise the max_groups option (now %llu)", (unsigned long long)h->opt_max_groups);
+    if (groups > h->opt.max_groups)
+        return fail(h, N1K_OOM, "group table capacity exceeded: raise the max_groups option (now %llu)", (unsigned long long)h->opt.max_groups);
     uint64_t cap = next_pow2(std::max<uint64_t>(groups * 2, 1024));
-    if (cap <= h->table.capacity) return N1K_OK;
-    if (!h->table.capacity) return alloc_table(h, cap, h->table, h->d_keys, h->d_acc, h->d_rep);
+    if (cap <= h->groups.table.capacity) return N1K_OK;
+    if (!h->groups.table.capacity) return alloc_table(h, cap, h->groups.table, h->groups.keys, h->groups.acc, h->groups.rep);
     GlobalTable nt{};
     DevBuf<uint64_t> nk, na, nr;
     n1k_status st = alloc_table(h, cap, nt, nk, na, nr);
     if (st != N1K_OK) return st;
-    HIP_TRY(h, launch_rehash(h->prog, h->table, nt, h->d_errp, h->d_counters.p + 4, h->stream));
+    HIP_TRY(h, launch_rehash(h->prog, h->groups.table, nt, h->groups.errp, h->groups.counters.p + 4, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    h->d_keys.release();
-    h->d_acc.release();
-    h->d_rep.release();
-    h->d_keys = nk;
-    h->d_acc = na;
-    h->d_rep = nr;
-    h->table = nt;
+    h->groups.keys = std::move(nk);
+    h->groups.acc = std::move(na);
+    h->groups.rep = std::move(nr);
+    h->groups.table = nt;
     return N1K_OK;
 }
 
 n1k_status ensure_pinned_counters(n1k_handle* h) {
-    if (!h->pin_counters) HIP_TRY(h, hipHostMalloc((void**)&h->pin_counters, (kCounters + kPinScratch) * sizeof(unsigned long long), hipHostMallocDefault));
+    HIP_TRY(h, h->res.pin_counters.ensure(kCounters + kPinScratch));
     return N1K_OK;
 }
 
 hipEvent_t get_event(n1k_handle* h) {
-    if (!h->event_pool.empty()) {
-        hipEvent_t e = h->event_pool.back();
-        h->event_pool.pop_back();
+    if (!h->timing.event_pool.empty()) {
+        hipEvent_t e = h->timing.event_pool.back();
+        h->timing.event_pool.pop_back();
         return e;
     }
     hipEvent_t e = nullptr;
@@ -556,13 +550,13 @@ hipEvent_t get_event(n1k_handle* h) {
 }
 
 void drain_events(n1k_handle* h) {
-    for (auto& pr : h->events) {
+    for (auto& pr : h->timing.events) {
         float ms = 0.f;
-        if (pr.first && pr.second && hipEventElapsedTime(&ms, pr.first, pr.second) == hipSuccess) h->stats.device_ms += ms;
-        if (pr.first) h->event_pool.push_back(pr.first);
-        if (pr.second) h->event_pool.push_back(pr.second);
+        if (pr.first && pr.second && hipEventElapsedTime(&ms, pr.first, pr.second) == hipSuccess) h->timing.stats.device_ms += ms;
+        if (pr.first) h->timing.event_pool.push_back(pr.first);
+        if (pr.second) h->timing.event_pool.push_back(pr.second);
     }
-    h->events.clear();
+    h->timing.events.clear();
 }
 
 n1k_status validate_batch(n1k_handle* h, const n1k_batch* b) {
@@ -617,6 +611,8 @@ int n1k_device_count(void) {
 
 const char* n1k_create_error(void) { return g_create_error.c_str(); }
 
+uint64_t n1k_device_bytes_live(void) { return g_device_bytes_live.load(std::memory_order_relaxed); }
+
 n1k_status n1k_create(const char* plan_json, size_t len, n1k_handle** out) {
     return guarded(nullptr, [&]() -> n1k_status {
     if (out) *out = nullptr;
@@ -657,30 +653,30 @@ n1k_status n1k_create(const char* plan_json, size_t len, n1k_handle** out) {
                 js.push_back(c);
         }
         js += "\"}";
-        n1k_status hst = n1k_create(js.c_str(), js.size(), &h->having);
+        n1k_status hst = n1k_create(js.c_str(), js.size(), &h->tail.having);
         if (hst != N1K_OK) {
             g_create_error = "HAVING: " + g_create_error;
             delete h;
             return hst;
         }
-        for (const std::string& p : h->having->plan.paths) {
+        for (const std::string& p : h->tail.having->plan.paths) {
             int idx = -1;
             char kind = 0;
             if (sscanf(p.c_str(), "(`$g`.`%c%d`)", &kind, &idx) != 2 || (kind != 'k' && kind != 'a') || idx < 0 ||
                 (size_t)idx >= (kind == 'k' ? h->plan.key_texts.size() : h->plan.aggs.size())) {
                 g_create_error = "HAVING refers to " + p + ", which is neither a group key nor an aggregate of the plan";
-                n1k_destroy(h->having);
+                n1k_destroy(h->tail.having);
                 delete h;
                 return N1K_UNSUPPORTED;
             }
-            h->having_cols.push_back(kind == 'k' ? idx : -idx - 1);
+            h->tail.having_cols.push_back(kind == 'k' ? idx : -idx - 1);
         }
     }
     if (h->plan.has_project) {
         n1k_status pst = build_projection(h);
         if (pst != N1K_OK) {
-            if (h->having) n1k_destroy(h->having);
-            h->having = nullptr;
+            if (h->tail.having) n1k_destroy(h->tail.having);
+            h->tail.having = nullptr;
             delete h;
             return pst;
         }
@@ -700,95 +696,29 @@ void n1k_destroy(n1k_handle* h) {
     }
 }
 static void destroy_handle(n1k_handle* h) {
-    if (h->host_us[5] > 0)
+    if (h->timing.host_us[5] > 0)
         fprintf(stderr, "n1k host trace: %.0f one-call executions; per call: reset %.1f us, push %.1f us, finish %.1f us (of which waiting %.1f us, after the wait %.1f us)\n",
-                h->host_us[5], h->host_us[0] / h->host_us[5], h->host_us[1] / h->host_us[5], h->host_us[2] / h->host_us[5],
-                h->host_us[3] / h->host_us[5], h->host_us[4] / h->host_us[5]);
-    if (h->having) n1k_destroy(h->having);
-    h->having = nullptr;
-    if (h->project) n1k_destroy(h->project);
-    h->project = nullptr;
+                h->timing.host_us[5], h->timing.host_us[0] / h->timing.host_us[5], h->timing.host_us[1] / h->timing.host_us[5], h->timing.host_us[2] / h->timing.host_us[5],
+                h->timing.host_us[3] / h->timing.host_us[5], h->timing.host_us[4] / h->timing.host_us[5]);
+    if (h->tail.having) n1k_destroy(h->tail.having);
+    h->tail.having = nullptr;
+    if (h->tail.project) n1k_destroy(h->tail.project);
+    h->tail.project = nullptr;
     if (h->device_ready) {
         (void)hipSetDevice(h->device);
         if (h->stream) (void)hipStreamSynchronize(h->stream);
+        if (h->stage.copy_stream) (void)hipStreamSynchronize(h->stage.copy_stream);  // (copies of a push that failed half way)
         drain_events(h);
-        for (auto e : h->event_pool) (void)hipEventDestroy(e);
-        if (h->ev_q0) (void)hipEventDestroy(h->ev_q0);
-        if (h->ev_q1) (void)hipEventDestroy(h->ev_q1);
-        h->d_rank.release();
-        h->match.release();
-        h->d_keys.release();
-        h->d_acc.release();
-        h->d_rep.release();
-        h->d_slabs.release();
-        h->d_block_sel.release();
-        for (auto& b : h->dv_tags) b.release();
-        for (auto& b : h->dv_payload) b.release();
-        h->d_regions.release();
-        h->d_set_table.release();
-        for (uint32_t d = 0; d < kMaxDistinct; d++) {
-            h->d_log_key[d].release();
-            h->d_log_val[d].release();
-            h->d_log_cls[d].release();
-        }
-        h->d_counters.release();
-        for (uint32_t d = 0; d < kMaxDistinct; d++) h->d_log_word[d].release();
-        h->d_part[0].release();
-        h->d_part[1].release();
-        for (auto& b : h->d_seg) b.release();
-        h->d_wtable.release();
-        h->d_hist.release();
-        h->d_cursor.release();
-        h->d_dcounts.release();
-        h->d_word_hist.release();
-        for (uint32_t d = 0; d < kMaxDistinct; d++) h->d_wregion[d].release();
-        h->d_wcursor.release();
-        h->d_woff.release();
-        h->d_wgather.release();
-        h->d_wide_int.release();
-        h->d_wide_flt.release();
-        if (h->pin_out) (void)hipHostFree(h->pin_out);
-        if (h->pin_counters) (void)hipHostFree(h->pin_counters);
-        if (h->pin_rows) (void)hipHostFree(h->pin_rows);
-        h->d_emit.release();
-        h->d_rregion.release();
-        h->d_rbins.release();
-        h->d_rcursor.release();
-        for (int i = 0; i < 3; i++) {
-            h->d_rec_key[i].release();
-            for (uint32_t e = 0; e < kRecOperands; e++) {
-                h->d_rec_pay[i][e].release();
-                h->d_rec_tag[i][e].release();
-            }
-        }
-        h->d_images.release();
-        h->d_cand.release();
-        h->d_topk.release();
-        h->d_out2.release();
-        for (int i = 0; i < 2; i++) {
-            for (auto& b : h->st_tags[i]) b.release();
-            for (auto& b : h->st_payload[i]) b.release();
-            for (auto& b : h->st_codes[i]) b.release();
-            if (h->st_free[i]) (void)hipEventDestroy(h->st_free[i]);
-        }
-        if (h->st_copied) (void)hipEventDestroy(h->st_copied);
-        if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
-        h->jd_bytes.release();
-        h->jd_offsets.release();
-        h->jd_new_first.release();
-        h->jd_patch_docs.release();
-        h->jd_patch_pay.release();
-        h->jd_tab.release();
-        h->jd_status.release();
-        h->jd_patch_tags.release();
-        h->jd_new_list.release();
-        h->jd_code_of.release();
-        h->jd_codes.release();
-        for (auto& b : h->jd_tags) b.release();
-        for (auto& b : h->jd_payload) b.release();
-        h->d_tile_off.release();
-        h->d_sel.release();
-        h->d_out.release();
+        for (auto e : h->timing.event_pool) (void)hipEventDestroy(e);
+        if (h->timing.ev_q0) (void)hipEventDestroy(h->timing.ev_q0);
+        if (h->timing.ev_q1) (void)hipEventDestroy(h->timing.ev_q1);
+        for (auto e : h->stage.free_ev)
+            if (e) (void)hipEventDestroy(e);
+        if (h->stage.copied) (void)hipEventDestroy(h->stage.copied);
+        // Both streams were waited for above and no call on this handle can add work to them any more, so they are idle: they
+        // go before the buffers (the members, which the delete below destroys after this body) without any buffer being
+        // freed under work that uses it.  A stream the caller gave (own_stream false) is the caller's: waited for, not destroyed.
+        if (h->stage.copy_stream) (void)hipStreamDestroy(h->stage.copy_stream);
         if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
     }
     delete h;
@@ -800,41 +730,41 @@ n1k_status n1k_reset(n1k_handle* h) {
     h->stop_flag.store(0);
     h->failure_global = false;
     h->row_base = 0;
-    h->merged_groups_bound = 0;
-    h->selected.clear();
-    h->r_keys.clear();
-    h->r_aggs.clear();
-    h->r_parts.clear();
-    h->r_rep.clear();
-    memset(&h->stats, 0, sizeof h->stats);
+    h->groups.merged_bound = 0;
+    h->filter.selected.clear();
+    h->res.keys.clear();
+    h->res.aggs.clear();
+    h->res.parts.clear();
+    h->res.rep.clear();
+    memset(&h->timing.stats, 0, sizeof h->timing.stats);
     if (h->device_ready) {
         HIP_TRY(h, hipSetDevice(h->device));
-        if (!h->events.empty()) {  // pushes that were never finished: their events must complete before reuse
+        if (!h->timing.events.empty()) {  // pushes that were never finished: their events must complete before reuse
             HIP_TRY(h, hipStreamSynchronize(h->stream));
             drain_events(h);
         }
-        h->stats.device_ms = 0;
-        h->groups_seen = 0;
-        h->out_count_dirty = false;
-        h->pending.count = 0;
-        if (!h->ev_q0) {
-            (void)hipEventCreate(&h->ev_q0);
-            (void)hipEventCreate(&h->ev_q1);
+        h->timing.stats.device_ms = 0;
+        h->part.groups_seen = 0;
+        h->res.out_count_dirty = false;
+        h->part.pending.count = 0;
+        if (!h->timing.ev_q0) {
+            (void)hipEventCreate(&h->timing.ev_q0);
+            (void)hipEventCreate(&h->timing.ev_q1);
         }
-        h->q1_recorded = false;
-        h->q0_recorded = h->ev_q0 && hipEventRecord(h->ev_q0, h->stream) == hipSuccess;  // the query starts here (stats.query_ms)
+        h->timing.q1_recorded = false;
+        h->timing.q0_recorded = h->timing.ev_q0 && hipEventRecord(h->timing.ev_q0, h->stream) == hipSuccess;  // the query starts here (stats.query_ms)
         if (h->device_clean) return N1K_OK;  // the last query's final kernel left the device as the launches below would
         h->device_clean = true;
         // one launch, no host synchronisation: table back to empty and all counters / error flags to zero
-        if (h->table.capacity) HIP_TRY(h, launch_init_table(h->prog, h->table, 0, h->table.capacity, h->d_counters.p, h->stream));
-        else HIP_TRY(h, hipMemsetAsync(h->d_counters.p, 0, kCounters * sizeof(unsigned long long), h->stream));
-        if (h->d_word_hist.p) HIP_TRY(h, hipMemsetAsync(h->d_word_hist.p, 0, kMaxDistinct * 256 * sizeof(unsigned long long), h->stream));
-        if (h->d_wcursor.p) HIP_TRY(h, hipMemsetAsync(h->d_wcursor.p, 0, kMaxDistinct * kWordSubs * kCursorStride * sizeof(unsigned long long), h->stream));
-        h->wregion_used = false;
+        if (h->groups.table.capacity) HIP_TRY(h, launch_init_table(h->prog, h->groups.table, 0, h->groups.table.capacity, h->groups.counters.p, h->stream));
+        else HIP_TRY(h, hipMemsetAsync(h->groups.counters.p, 0, kCounters * sizeof(unsigned long long), h->stream));
+        if (h->distinct.word_hist.p) HIP_TRY(h, hipMemsetAsync(h->distinct.word_hist.p, 0, kMaxDistinct * 256 * sizeof(unsigned long long), h->stream));
+        if (h->distinct.wcursor.p) HIP_TRY(h, hipMemsetAsync(h->distinct.wcursor.p, 0, kMaxDistinct * kWordSubs * kCursorStride * sizeof(unsigned long long), h->stream));
+        h->distinct.wregion_used = false;
         if (h->prog.wide_int) {
             const size_t n = (size_t)1 << h->prog.wide_bits;
-            HIP_TRY(h, hipMemsetAsync(h->d_wide_int.p, 0xFF, n * 8, h->stream));
-            HIP_TRY(h, hipMemsetAsync(h->d_wide_flt.p, 0xFF, n * 8, h->stream));
+            HIP_TRY(h, hipMemsetAsync(h->groups.wide_int.p, 0xFF, n * 8, h->stream));
+            HIP_TRY(h, hipMemsetAsync(h->groups.wide_flt.p, 0xFF, n * 8, h->stream));
         }
     }
     return N1K_OK;
@@ -892,91 +822,91 @@ n1k_status n1k_set_option(n1k_handle* h, const char* name, int64_t value) {
     return guarded(h, [&]() -> n1k_status {
     if (!h || !name) return N1K_INVALID;
     std::string n = name;
-    if (n == "agg_mode") h->opt_agg_mode = value;
-    else if (n == "max_groups") h->opt_max_groups = value > 0 ? (uint64_t)value : 1;
-    else if (n == "grid_blocks") h->opt_grid_blocks = (uint32_t)std::max<int64_t>(0, value);
-    else if (n == "fast") h->opt_fast = value ? 1 : 0;
-    else if (n == "spec") h->opt_spec = value ? 1 : 0;
-    else if (n == "wide") h->opt_wide = value ? 1 : 0;
-    else if (n == "fuse_arith") h->opt_fuse_arith = value ? 1 : 0;
-    else if (n == "lean_topk") h->opt_lean_topk = value ? 1 : 0;
-    else if (n == "topk_sample") h->opt_topk_sample = value ? 1 : 0;
-    else if (n == "distinct_fill_pct") h->opt_distinct_fill_pct = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 1), 75);
-    else if (n == "dedupe_unroll") h->opt_dedupe_unroll = (uint32_t)value;
-    else if (n == "agg_spec") h->opt_agg_spec = value ? 1 : 0;
-    else if (n == "merge_chunks") h->opt_merge_chunks = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 0), 16);
-    else if (n == "inject_failure") h->opt_inject_failure = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 0), 3);
-    else if (n == "part_block") h->opt_part_block = value == 256 ? 256 : 512;
-    else if (n == "part_subs") h->opt_part_subs = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 0), 2);  // 0 off, 1 large batches, 2 always (tests)
-    else if (n == "part_per_cu") h->opt_part_per_cu = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 0), 8);
-    else if (n == "jit") h->opt_jit = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 0), 2);
-    else if (n == "jit_min_rows") h->opt_jit_min_rows = (uint64_t)std::max<int64_t>(value, 0);
+    if (n == "agg_mode") h->opt.agg_mode = value;
+    else if (n == "max_groups") h->opt.max_groups = value > 0 ? (uint64_t)value : 1;
+    else if (n == "grid_blocks") h->opt.grid_blocks = (uint32_t)std::max<int64_t>(0, value);
+    else if (n == "fast") h->opt.fast = value ? 1 : 0;
+    else if (n == "spec") h->opt.spec = value ? 1 : 0;
+    else if (n == "wide") h->opt.wide = value ? 1 : 0;
+    else if (n == "fuse_arith") h->opt.fuse_arith = value ? 1 : 0;
+    else if (n == "lean_topk") h->opt.lean_topk = value ? 1 : 0;
+    else if (n == "topk_sample") h->opt.topk_sample = value ? 1 : 0;
+    else if (n == "distinct_fill_pct") h->opt.distinct_fill_pct = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 1), 75);
+    else if (n == "dedupe_unroll") h->opt.dedupe_unroll = (uint32_t)value;
+    else if (n == "agg_spec") h->opt.agg_spec = value ? 1 : 0;
+    else if (n == "merge_chunks") h->opt.merge_chunks = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 0), 16);
+    else if (n == "inject_failure") h->opt.inject_failure = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 0), 3);
+    else if (n == "part_block") h->opt.part_block = value == 256 ? 256 : 512;
+    else if (n == "part_subs") h->opt.part_subs = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 0), 2);  // 0 off, 1 large batches, 2 always (tests)
+    else if (n == "part_per_cu") h->opt.part_per_cu = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 0), 8);
+    else if (n == "jit") h->opt.jit = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 0), 2);
+    else if (n == "jit_min_rows") h->opt.jit_min_rows = (uint64_t)std::max<int64_t>(value, 0);
     else if (n == "distinct_words") {
         if (h->layout_fixed) return fail(h, N1K_INVALID, "distinct_words must be set before the first batch");
-        h->opt_distinct_words = value ? 1 : 0;
+        h->opt.distinct_words = value ? 1 : 0;
     } else if (n == "distinct_set_slots") {
         uint32_t v = 64;
         while (v < (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 64), 8192)) v <<= 1;
-        h->opt_distinct_set_slots = v;
+        h->opt.distinct_set_slots = v;
     } else if (n == "records") {
-        h->opt_records = value ? 1 : 0;
+        h->opt.records = value ? 1 : 0;
     } else if (n == "rec_slots") {
-        h->opt_rec_slots = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 0), 8192);
+        h->opt.rec_slots = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 0), 8192);
     } else if (n == "rec_bins") {
         uint32_t v = 0;
         if (value > 0) for (v = 1; v < (uint32_t)std::min<int64_t>(value, 256); v <<= 1) {}
-        h->opt_rec_bins = v;
+        h->opt.rec_bins = v;
     } else if (n == "rec_slices") {
-        h->opt_rec_slices = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 0), 64);
+        h->opt.rec_slices = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 0), 64);
     } else if (n == "rec_scan_per_cu") {
-        h->opt_rec_scan_per_cu = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 0), 8);
+        h->opt.rec_scan_per_cu = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 0), 8);
     } else if (n == "rec_block") {
-        h->opt_rec_block = value <= 0 ? 0u : (value <= 256 ? 256u : 512u);
+        h->opt.rec_block = value <= 0 ? 0u : (value <= 256 ? 256u : 512u);
     } else if (n == "rec_unroll") {
-        h->opt_rec_unroll = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 0), 8);
+        h->opt.rec_unroll = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 0), 8);
     } else if (n == "distinct_region_cap") {
-        h->opt_region_cap = (uint64_t)std::max<int64_t>(value, 0);
+        h->opt.region_cap = (uint64_t)std::max<int64_t>(value, 0);
     } else if (n == "dedupe_block") {
         if ((value | 1) != 257 && (value | 1) != 513 && (value | 1) != 1025) return fail(h, N1K_INVALID, "dedupe_block must be 256, 512 or 1024 (+1: probe word by word)");
-        h->opt_dedupe_block = (uint32_t)value;
+        h->opt.dedupe_block = (uint32_t)value;
     } else if (n == "json_device") {
-        h->opt_json_device = value ? 1 : 0;
+        h->opt.json_device = value ? 1 : 0;
     } else if (n == "json_device_left_pct") {
-        h->opt_json_device_left_pct = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 0), 100);
+        h->opt.json_device_left_pct = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 0), 100);
     } else if (n == "json_device_min_docs") {
-        h->opt_json_device_min_docs = (uint64_t)std::max<int64_t>(value, 0);
+        h->opt.json_device_min_docs = (uint64_t)std::max<int64_t>(value, 0);
     } else if (n == "json_threads") {
-        h->opt_json_threads = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 0), 64);
+        h->opt.json_threads = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 0), 64);
     } else if (n == "partition_min_rows") {
-        h->opt_partition_min_rows = (uint64_t)std::max<int64_t>(value, 1);
+        h->opt.partition_min_rows = (uint64_t)std::max<int64_t>(value, 1);
     } else if (n == "partition_probe_rows") {
-        h->opt_partition_probe_rows = (uint64_t)std::max<int64_t>(value, 1);
+        h->opt.partition_probe_rows = (uint64_t)std::max<int64_t>(value, 1);
     } else if (n == "partition_min_groups") {
-        h->opt_partition_min_groups = (uint64_t)std::max<int64_t>(value, 1);
+        h->opt.partition_min_groups = (uint64_t)std::max<int64_t>(value, 1);
     } else if (n == "partition_sticky") {
-        h->opt_partition_sticky = value ? 1 : 0;
-        h->sticky.valid = false;
+        h->opt.partition_sticky = value ? 1 : 0;
+        h->part.sticky.valid = false;
     } else if (n == "partition_levels") {
-        h->opt_partition_levels = (int32_t)std::min<int64_t>(std::max<int64_t>(value, -1), 2);
+        h->opt.partition_levels = (int32_t)std::min<int64_t>(std::max<int64_t>(value, -1), 2);
     } else if (n == "topk_min_groups") {
-        h->opt_topk_min_groups = (uint64_t)std::max<int64_t>(value, 1);
+        h->opt.topk_min_groups = (uint64_t)std::max<int64_t>(value, 1);
     } else if (n == "distinct_levels") {
-        h->opt_distinct_levels = (int32_t)std::min<int64_t>(std::max<int64_t>(value, -1), 2);
+        h->opt.distinct_levels = (int32_t)std::min<int64_t>(std::max<int64_t>(value, -1), 2);
     } else if (n == "wide_values") {
         if (h->layout_fixed) return fail(h, N1K_INVALID, "wide_values must be set before the first batch");
-        h->opt_wide_values = (uint64_t)std::max<int64_t>(value, 0);
+        h->opt.wide_values = (uint64_t)std::max<int64_t>(value, 0);
     }
-    else if (n == "slabs") h->opt_slabs = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 0), 2);  // 0 off, 1 auto, 2 always
+    else if (n == "slabs") h->opt.slabs = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 0), 2);  // 0 off, 1 auto, 2 always
     else if (n == "block") {
         if (value != 0 && value != 256 && value != 512 && value != 1024) return fail(h, N1K_INVALID, "block must be 0 (auto), 256, 512 or 1024");
-        h->opt_block = (uint32_t)value;
+        h->opt.block = (uint32_t)value;
     } else if (n == "rows_per_lane") {
         if (value != 2 && value != 4) return fail(h, N1K_INVALID, "rows_per_lane must be 2 or 4");
-        h->opt_rows_per_lane = (uint32_t)value;
+        h->opt.rows_per_lane = (uint32_t)value;
     }
     // (at most 64 KiB, as the run-time-built kernels take it: a HASHED table of 160 KiB plus the scan kernels' own LDS is more
     //  than a workgroup can have, and the launch failed)
-    else if (n == "lds_bytes") h->opt_lds_bytes = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 1024), 64 * 1024);
+    else if (n == "lds_bytes") h->opt.lds_bytes = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 1024), 64 * 1024);
     else if (n == "device") {
         if (h->device_ready) return fail(h, N1K_INVALID, "device must be chosen before the first push");
         h->device = (int)value;
@@ -986,7 +916,7 @@ n1k_status n1k_set_option(n1k_handle* h, const char* name, int64_t value) {
         h->own_stream = false;
     } else if (n == "rep_row") {
         if (h->layout_fixed) return fail(h, N1K_INVALID, "rep_row must be chosen before the first push");
-        h->opt_rep_row = value ? 1 : 0;
+        h->opt.rep_row = value ? 1 : 0;
         PlanError err;
         h->agg_names.clear();
         h->has_distinct = false;
@@ -1020,10 +950,10 @@ n1k_status n1k_run_device_batch(n1k_handle* h, const n1k_batch* batch, n1k_resul
         h->clear_on_finish = false;
     }
     if (trace) {
-        h->host_us[0] += t1 - t0;
-        h->host_us[1] += t2 - t1;
-        h->host_us[2] += now() - t2;  // (finish in all; its wait is accounted inside)
-        h->host_us[5] += 1;
+        h->timing.host_us[0] += t1 - t0;
+        h->timing.host_us[1] += t2 - t1;
+        h->timing.host_us[2] += now() - t2;  // (finish in all; its wait is accounted inside)
+        h->timing.host_us[5] += 1;
     }
     return st;
 }
@@ -1031,16 +961,16 @@ n1k_status n1k_run_device_batch(n1k_handle* h, const n1k_batch* batch, n1k_resul
 n1k_status n1k_extract_json(n1k_handle* h, uint64_t ndocs, const uint64_t* offsets, const char* bytes, n1k_batch* out) {
     return guarded(h, [&]() -> n1k_status {
     if (!h || !out || (ndocs && (!offsets || !bytes))) return N1K_INVALID;
-    if (h->json_paths_state == 0) {
-        h->json_paths.resize(h->plan.paths.size());
-        h->json_paths_state = 1;
+    if (h->json.paths_state == 0) {
+        h->json.paths.resize(h->plan.paths.size());
+        h->json.paths_state = 1;
         for (size_t c = 0; c < h->plan.paths.size(); c++)
-            if (!parse_leaf_path(h->plan.paths[c], h->json_paths[c])) h->json_paths_state = -1;
+            if (!parse_leaf_path(h->plan.paths[c], h->json.paths[c])) h->json.paths_state = -1;
     }
-    if (h->json_paths_state < 0)
+    if (h->json.paths_state < 0)
         return fail(h, N1K_UNSUPPORTED, "a leaf path of the plan is not a chain of field names: extract the columns yourself");
-    const size_t np = h->json_paths.size();
-    uint32_t nthreads = h->opt_json_threads ? h->opt_json_threads : std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
+    const size_t np = h->json.paths.size();
+    uint32_t nthreads = h->opt.json_threads ? h->opt.json_threads : std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
     nthreads = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(nthreads, ndocs / 2048 + 1));
     std::vector<JsonColumns> part(nthreads);
     std::vector<std::string> errs(nthreads);
@@ -1053,7 +983,7 @@ n1k_status n1k_extract_json(n1k_handle* h, uint64_t ndocs, const uint64_t* offse
     auto work = [&](uint32_t t) {
         try {
             auto r = range(t);
-            bad[t] = extract_json_range(h->json_paths, offsets, bytes, r.first, r.second, part[t], errs[t]);
+            bad[t] = extract_json_range(h->json.paths, offsets, bytes, r.first, r.second, part[t], errs[t]);
         } catch (...) {
             threw[t] = 1;
         }
@@ -1078,11 +1008,11 @@ n1k_status n1k_extract_json(n1k_handle* h, uint64_t ndocs, const uint64_t* offse
             return fail(h, N1K_INVALID, "document %lld is not valid JSON: %s", bad[t], errs[t].c_str());
         }
     // one dictionary: the threads' local strings get the handle's codes
-    h->js_tags.assign(np, std::vector<uint8_t>());
-    h->js_payload.assign(np, std::vector<uint64_t>());
+    h->json.tags.assign(np, std::vector<uint8_t>());
+    h->json.payload.assign(np, std::vector<uint64_t>());
     for (size_t c = 0; c < np; c++) {
-        h->js_tags[c].resize(ndocs);
-        h->js_payload[c].resize(ndocs);
+        h->json.tags[c].resize(ndocs);
+        h->json.payload[c].resize(ndocs);
     }
     for (uint32_t t = 0; t < nthreads; t++) {
         auto r = range(t);
@@ -1090,22 +1020,22 @@ n1k_status n1k_extract_json(n1k_handle* h, uint64_t ndocs, const uint64_t* offse
         for (size_t i = 0; i < code.size(); i++) code[i] = intern(h, part[t].strings[i]);
         for (size_t c = 0; c < np; c++) {
             const size_t n = (size_t)(r.second - r.first);
-            memcpy(h->js_tags[c].data() + r.first, part[t].tags[c].data(), n);
-            uint64_t* dst = h->js_payload[c].data() + r.first;
+            memcpy(h->json.tags[c].data() + r.first, part[t].tags[c].data(), n);
+            uint64_t* dst = h->json.payload[c].data() + r.first;
             const uint64_t* src = part[t].payload[c].data();
             const uint8_t* tg = part[t].tags[c].data();
             for (size_t i = 0; i < n; i++) dst[i] = tg[i] >= N1K_T_STRING ? code[src[i]] : src[i];
         }
     }
-    h->js_cols.assign(np, n1k_col{});
+    h->json.cols.assign(np, n1k_col{});
     for (size_t c = 0; c < np; c++) {
-        h->js_cols[c].kind = N1K_COL_TAGGED64;
-        h->js_cols[c].tags = h->js_tags[c].data();
-        h->js_cols[c].payload = h->js_payload[c].data();
+        h->json.cols[c].kind = N1K_COL_TAGGED64;
+        h->json.cols[c].tags = h->json.tags[c].data();
+        h->json.cols[c].payload = h->json.payload[c].data();
     }
     out->nrows = ndocs;
     out->ncols = (uint32_t)np;
-    out->cols = h->js_cols.data();
+    out->cols = h->json.cols.data();
     return N1K_OK;
     });
 }
@@ -1116,13 +1046,13 @@ n1k_status n1k_push_json(n1k_handle* h, uint64_t ndocs, const uint64_t* offsets,
     if (h->stop_flag.load()) return fail(h, N1K_STOPPED, "operator was stopped");
     // large batches: the device extractor (the bytes cross PCIe as they are; n1k_jsonpush.cpp) — it takes the batch or
     // leaves all of it to the host path below
-    if (h->json_paths_state == 0) {
-        h->json_paths.resize(h->plan.paths.size());
-        h->json_paths_state = 1;
+    if (h->json.paths_state == 0) {
+        h->json.paths.resize(h->plan.paths.size());
+        h->json.paths_state = 1;
         for (size_t c = 0; c < h->plan.paths.size(); c++)
-            if (!parse_leaf_path(h->plan.paths[c], h->json_paths[c])) h->json_paths_state = -1;
+            if (!parse_leaf_path(h->plan.paths[c], h->json.paths[c])) h->json.paths_state = -1;
     }
-    if (h->json_paths_state > 0 && ndocs) {
+    if (h->json.paths_state > 0 && ndocs) {
         bool done = false;
         n1k_status dst = push_json_device(h, ndocs, offsets, bytes, &done);
         if (dst != N1K_OK || done) return dst;
@@ -1159,14 +1089,14 @@ n1k_status n1k_sync(n1k_handle* h) {
     if (!h->device_ready) return N1K_OK;
     HIP_TRY(h, hipSetDevice(h->device));
     unsigned long long counters[kCounters] = {0};
-    HIP_TRY(h, hipMemcpyAsync(counters, h->d_counters.p, sizeof counters, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(counters, h->groups.counters.p, sizeof counters, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     drain_events(h);
     if (h->plan.has_group && !h->device_clean) {  // (clean: the query was finished and its counters zeroed behind the result)
-        h->stats.rows_selected = counters[0];
-        h->stats.groups_out = h->pending.count ? h->pending.count : counters[1];  // groups so far (in the table, or in the kept region)
+        h->timing.stats.rows_selected = counters[0];
+        h->timing.stats.groups_out = h->part.pending.count ? h->part.pending.count : counters[1];  // groups so far (in the table, or in the kept region)
     }
-    if (!h->device_clean) h->stats.wide_key_values = counters[13];
+    if (!h->device_clean) h->timing.stats.wide_key_values = counters[13];
     return N1K_OK;
     });
 }
@@ -1193,7 +1123,7 @@ n1k_status n1k_jit_check(n1k_handle* h, const uint32_t* col_kinds, uint32_t ncol
     FastArgs F;
     const uint32_t max_slots = (uint32_t)std::min<uint64_t>((156u * 1024u) / (h->prog.lds_words * 8), 1u << 15);
     // (plans with arithmetic: the shape that evaluates the nodes in registers, as run_group_batch would choose it)
-    const bool fuse = !h->derived.empty() && h->opt_fuse_arith;
+    const bool fuse = !h->derived.empty() && h->opt.fuse_arith;
     if (!build_fast_args(h, max_slots, F, fuse)) return fail(h, N1K_UNSUPPORTED, "the plan shape is outside the bounded family");
     SpecSig sig = make_plan_sig(h, F);
     std::string l;
@@ -1258,19 +1188,19 @@ n1k_status n1k_get_stats(const n1k_handle* h, n1k_stats* out) {
     if (!h || !out) return N1K_INVALID;
     // account pushes whose events have completed meanwhile (no waiting: hipEventQuery)
     n1k_handle* m = const_cast<n1k_handle*>(h);
-    while (!m->events.empty() && m->events.front().second && hipEventQuery(m->events.front().second) == hipSuccess) {
-        auto pr = m->events.front();
+    while (!m->timing.events.empty() && m->timing.events.front().second && hipEventQuery(m->timing.events.front().second) == hipSuccess) {
+        auto pr = m->timing.events.front();
         float ms = 0.f;
-        if (pr.first && hipEventElapsedTime(&ms, pr.first, pr.second) == hipSuccess) m->stats.device_ms += ms;
-        if (pr.first) m->event_pool.push_back(pr.first);
-        m->event_pool.push_back(pr.second);
-        m->events.erase(m->events.begin());
+        if (pr.first && hipEventElapsedTime(&ms, pr.first, pr.second) == hipSuccess) m->timing.stats.device_ms += ms;
+        if (pr.first) m->timing.event_pool.push_back(pr.first);
+        m->timing.event_pool.push_back(pr.second);
+        m->timing.events.erase(m->timing.events.begin());
     }
-    if (m->q0_recorded && m->q1_recorded && hipEventQuery(m->ev_q1) == hipSuccess) {
+    if (m->timing.q0_recorded && m->timing.q1_recorded && hipEventQuery(m->timing.ev_q1) == hipSuccess) {
         float ms = 0.f;
-        if (hipEventElapsedTime(&ms, m->ev_q0, m->ev_q1) == hipSuccess) m->stats.query_ms = ms;
+        if (hipEventElapsedTime(&ms, m->timing.ev_q0, m->timing.ev_q1) == hipSuccess) m->timing.stats.query_ms = ms;
     }
-    *out = h->stats;
+    *out = h->timing.stats;
     return N1K_OK;
     });
 }

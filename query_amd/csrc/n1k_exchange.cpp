@@ -23,7 +23,7 @@ static n1k_status run_partition(n1k_handle* h, const n1k_batch* b, PartArgs& A) 
     FastArgs F;
     const JitKernel* jit = nullptr;
     const bool fuse = !h->derived.empty() && !h->derived_ready;
-    if (h->opt_spec && h->opt_jit && (h->opt_jit == 2 || n >= h->opt_jit_min_rows) && n < (1ull << 31) && (!fuse || h->opt_fuse_arith) &&
+    if (h->opt.spec && h->opt.jit && (h->opt.jit == 2 || n >= h->opt.jit_min_rows) && n < (1ull << 31) && (!fuse || h->opt.fuse_arith) &&
         sizeof(Program) + sizeof(FastArgs) + sizeof(PartArgs) + 64 <= 4096 && build_fast_args(h, 1u << 15, F, fuse, true)) {
         // what the staging needs in LDS (n1k_spec.h PartLds: 2048 rows x (9 B per TAGGED64 column, 4 B per DICT32 column, 1))
         size_t lds = 2048 + 2048 + 4096;  // (+ the per-destination tables of PartLds)
@@ -47,16 +47,16 @@ static n1k_status run_partition(n1k_handle* h, const n1k_batch* b, PartArgs& A) 
             F.cols[c] = h->prog.cols[c];
             aligned &= ((uintptr_t)F.cols[c].tags % 2 == 0) && ((uintptr_t)F.cols[c].payload % 16 == 0) && ((uintptr_t)F.cols[c].codes % 8 == 0);
         }
-        const bool wide = aligned && h->opt_wide && n >= 2;
+        const bool wide = aligned && h->opt.wide && n >= 2;
         F.nrows = (uint32_t)n;
         F.row_base = h->row_base;
-        F.err_flags = h->d_errp;
+        F.err_flags = h->groups.errp;
         // 256-thread workgroups (tiles of 1024 rows, one in flight, six per CU: many independent workgroups overlap the wait
         // for each tile's reservation) or 512-thread ones (2048 rows, two tiles in flight, two per CU)
-        const uint32_t pblock = wide && h->opt_part_block == 256 ? 256u : 512u;
+        const uint32_t pblock = wide && h->opt.part_block == 256 ? 256u : 512u;
         const uint64_t tiles = (n + pblock * 4 - 1) / (pblock * 4);
-        uint32_t part_per_cu = h->opt_part_per_cu ? h->opt_part_per_cu : (pblock == 256 ? 6u : 2u);
-        if (match_lds_bytes(F) && !h->opt_part_per_cu) {  // with the staged match table beside a tile's staging: as many workgroups as still fit a CU
+        uint32_t part_per_cu = h->opt.part_per_cu ? h->opt.part_per_cu : (pblock == 256 ? 6u : 2u);
+        if (match_lds_bytes(F) && !h->opt.part_per_cu) {  // with the staged match table beside a tile's staging: as many workgroups as still fit a CU
             size_t wg = 2048 + 2048 + 4096 + kMatchLdsBytes;
             for (uint32_t c = 0; c < F.ncols; c++) wg += (size_t)pblock * 4u * (F.cols[c].kind == COLK_DICT32 ? 4u : 9u);
             part_per_cu = std::max<uint32_t>(1u, std::min<uint32_t>(part_per_cu, (uint32_t)(160u * 1024u / wg)));
@@ -64,13 +64,13 @@ static n1k_status run_partition(n1k_handle* h, const n1k_batch* b, PartArgs& A) 
         uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)h->num_cus * part_per_cu, tiles));
         // many tiles: every destination's region in kRowSubs sub-regions with their own counters, workgroups dealt round-robin
         // (tile t goes to sub-region t % kRowSubs: an even share of the rows whatever their order)
-        if (seg_rows && h->opt_part_subs && (tiles >= 4096 || h->opt_part_subs == 2)) {
+        if (seg_rows && h->opt.part_subs && (tiles >= 4096 || h->opt.part_subs == 2)) {
             A.nsub = kRowSubs;
             grid = (grid + kRowSubs - 1) / kRowSubs * kRowSubs;
         }
         if (e0) (void)hipEventRecord(e0, h->stream);
         HIP_TRY(h, jit_launch_partition(jit, h->prog, F, A, grid, wide, pblock, h->stream));
-        h->stats.spec_kernel = F.nderived ? 3u : 2u;
+        h->timing.stats.spec_kernel = F.nderived ? 3u : 2u;
     } else {
         n1k_status st = materialize_derived(h, b);
         if (st != N1K_OK) return st;
@@ -78,11 +78,11 @@ static n1k_status run_partition(n1k_handle* h, const n1k_batch* b, PartArgs& A) 
         const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)h->num_cus * 4, ntiles));
         if (e0) (void)hipEventRecord(e0, h->stream);
         HIP_TRY(h, launch_partition(h->prog, A, grid, h->stream));
-        h->stats.spec_kernel = 0;
+        h->timing.stats.spec_kernel = 0;
     }
     if (seg_rows && A.nsub == 1) HIP_TRY(h, launch_dense_to_segments(A.counts, A.nparts, A.count_stride, seg_rows, h->stream, A.per_dest ? A.dest_cap : nullptr));
     if (e1) (void)hipEventRecord(e1, h->stream);
-    h->events.emplace_back(e0, e1);
+    h->timing.events.emplace_back(e0, e1);
     return N1K_OK;
 }
 
@@ -122,22 +122,22 @@ n1k_status n1k_partition_device_batch(n1k_handle* h, const n1k_batch* batch, uin
     A.capacity = capacity_rows;
     A.nparts = nparts;
     A.counts = (unsigned long long*)out_counts;
-    A.err_flags = h->d_errp;
+    A.err_flags = h->groups.errp;
     HIP_TRY(h, hipMemsetAsync(out_counts, 0, nparts * sizeof(uint64_t), h->stream));
     st = run_partition(h, batch, A);
     if (st != N1K_OK) return st;
     uint32_t err_flags = 0;
-    HIP_TRY(h, hipMemcpyAsync(&err_flags, h->d_errp, 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(&err_flags, h->groups.errp, 4, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     if (err_flags & ERR_TABLE_FULL) {
         // (the flag belongs to this call alone: the caller repeats it with larger regions, on the same handle)
-        HIP_TRY(h, hipMemsetAsync(h->d_errp, 0, 4, h->stream));
+        HIP_TRY(h, hipMemsetAsync(h->groups.errp, 0, 4, h->stream));
         return fail(h, N1K_REGION_FULL, "partition region capacity (%llu rows) exceeded", (unsigned long long)capacity_rows);
     }
     if (err_flags & ERR_UNPACKABLE_KEY) return fail(h, N1K_UNSUPPORTED_DATA, "a group key value does not fit the packed key");
     if (err_flags & ERR_UNSUPPORTED_VALUE) return fail(h, N1K_UNSUPPORTED_DATA, "a value outside the device subset was met");
-    h->stats.rows_in += batch->nrows;
-    h->stats.batches += 1;
+    h->timing.stats.rows_in += batch->nrows;
+    h->timing.stats.batches += 1;
     return N1K_OK;
     });
 }
@@ -152,7 +152,7 @@ uint64_t n1k_partial_region_bytes(const n1k_handle* h, uint64_t capacity_groups)
 n1k_status n1k_export_partials_async(n1k_handle* h, uint32_t nparts, uint64_t capacity_groups, void* out) {
     return guarded(h, [&]() -> n1k_status {
     if (!h || !out || nparts == 0 || capacity_groups == 0) return N1K_INVALID;
-    if (h->pending.count) {
+    if (h->part.pending.count) {
         n1k_status pst = flush_pending(h);
         if (pst != N1K_OK) return pst;
     }
@@ -163,9 +163,9 @@ n1k_status n1k_export_partials_async(n1k_handle* h, uint32_t nparts, uint64_t ca
     if (st != N1K_OK) return st;
     uint64_t region_words = 2 + capacity_groups * (1 + (uint64_t)h->prog.glob_words);
     HIP_TRY(h, hipMemsetAsync(out, 0, (size_t)nparts * region_words * 8, h->stream));  // headers (and padding) to zero
-    if (h->table.capacity)
-        HIP_TRY(h, launch_export_partials(h->prog, h->table, nparts, capacity_groups, (uint64_t*)out, region_words,
-                                          h->d_errp, h->stream));
+    if (h->groups.table.capacity)
+        HIP_TRY(h, launch_export_partials(h->prog, h->groups.table, nparts, capacity_groups, (uint64_t*)out, region_words,
+                                          h->groups.errp, h->stream));
     return N1K_OK;
     });
 }
@@ -176,19 +176,19 @@ n1k_status n1k_export_partials_device(n1k_handle* h, uint32_t nparts, uint64_t c
     if (st != N1K_OK) return st;
     uint32_t err_flags = 0;
     unsigned long long sel = 0, wide = 0;
-    HIP_TRY(h, hipMemcpyAsync(&err_flags, h->d_errp, 4, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(&sel, h->d_counters.p, sizeof sel, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(&wide, h->d_counters.p + 13, sizeof wide, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(&err_flags, h->groups.errp, 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(&sel, h->groups.counters.p, sizeof sel, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(&wide, h->groups.counters.p + 13, sizeof wide, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    h->stats.rows_selected = sel;
-    h->stats.wide_key_values = wide;
+    h->timing.stats.rows_selected = sel;
+    h->timing.stats.wide_key_values = wide;
     // codes of the wide-value tables mean nothing on another device: such groups travel as rows instead
     if (wide) {
-        HIP_TRY(h, hipMemsetAsync(h->d_errp, 0, 4, h->stream));  // a region overflow of the abandoned export is moot
+        HIP_TRY(h, hipMemsetAsync(h->groups.errp, 0, 4, h->stream));  // a region overflow of the abandoned export is moot
         return fail(h, N1K_UNSUPPORTED, "group keys hold %llu float / wide integer values: use the row exchange", wide);
     }
     if (err_flags & ERR_TABLE_FULL) {
-        HIP_TRY(h, hipMemsetAsync(h->d_errp, 0, 4, h->stream));
+        HIP_TRY(h, hipMemsetAsync(h->groups.errp, 0, 4, h->stream));
         return fail(h, N1K_REGION_FULL, "more than %llu groups for one destination: raise the region capacity",
                     (unsigned long long)capacity_groups);
     }
@@ -202,7 +202,7 @@ n1k_status n1k_merge_partials_device(n1k_handle* h, uint32_t nregions, uint64_t 
     if (h->has_distinct) return fail(h, N1K_UNSUPPORTED, "DISTINCT sets do not travel with partial groups");
     if (!h->layout_fixed) return fail(h, N1K_INVALID, "merge needs the key layout: push a batch (even an empty one) first");
     h->device_clean = false;
-    if (h->pending.count) {
+    if (h->part.pending.count) {
         n1k_status pst = flush_pending(h);
         if (pst != N1K_OK) return pst;
     }
@@ -215,9 +215,9 @@ n1k_status n1k_merge_partials_device(n1k_handle* h, uint32_t nregions, uint64_t 
     h->row_base = saved;
     if (st != N1K_OK) return st;
     uint64_t region_words = 2 + capacity_groups * (1 + (uint64_t)h->prog.glob_words);
-    HIP_TRY(h, launch_merge_partials(h->prog, h->table, nregions, capacity_groups, (const uint64_t*)in, region_words,
-                                     h->d_errp, h->d_counters.p + 1, h->stream));
-    h->merged_groups_bound += (uint64_t)nregions * capacity_groups;
+    HIP_TRY(h, launch_merge_partials(h->prog, h->groups.table, nregions, capacity_groups, (const uint64_t*)in, region_words,
+                                     h->groups.errp, h->groups.counters.p + 1, h->stream));
+    h->groups.merged_bound += (uint64_t)nregions * capacity_groups;
     return N1K_OK;
     });
 }
@@ -230,7 +230,7 @@ n1k_status n1k_export_groups(n1k_handle* h, const void** blob, size_t* len) {
     st = flush_pending(h);
     if (st != N1K_OK) return st;
     unsigned long long ng = 0;
-    HIP_TRY(h, hipMemcpyAsync(&ng, h->d_counters.p + 1, sizeof ng, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(&ng, h->groups.counters.p + 1, sizeof ng, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     uint64_t cap = std::max<uint64_t>(ng, 1);
     uint64_t bytes = n1k_partial_region_bytes(h, cap);
@@ -238,16 +238,15 @@ n1k_status n1k_export_groups(n1k_handle* h, const void** blob, size_t* len) {
     HIP_TRY(h, tmp.ensure(bytes / 8));
     st = n1k_export_partials_device(h, 1, cap, tmp.p);
     if (st == N1K_OK) {
-        h->export_blob.resize(bytes + 16);
+        h->res.export_blob.resize(bytes + 16);
         uint64_t hdr[2] = {0x4e314b5041525431ull /* "N1KPART1" */, cap};
-        memcpy(h->export_blob.data(), hdr, 16);
-        hipError_t e = hipMemcpy(h->export_blob.data() + 16, tmp.p, bytes, hipMemcpyDeviceToHost);
+        memcpy(h->res.export_blob.data(), hdr, 16);
+        hipError_t e = hipMemcpy(h->res.export_blob.data() + 16, tmp.p, bytes, hipMemcpyDeviceToHost);
         if (e != hipSuccess) st = fail(h, N1K_DEVICE_ERROR, "copy of exported groups failed: %s", hipGetErrorString(e));
     }
-    tmp.release();
     if (st != N1K_OK) return st;
-    *blob = h->export_blob.data();
-    *len = h->export_blob.size();
+    *blob = h->res.export_blob.data();
+    *len = h->res.export_blob.size();
     return N1K_OK;
     });
 }
@@ -267,7 +266,6 @@ n1k_status n1k_merge_groups(n1k_handle* h, const void* blob, size_t len) {
     HIP_TRY(h, hipMemcpy(tmp.p, (const char*)blob + 16, len - 16, hipMemcpyHostToDevice));
     st = n1k_merge_partials_device(h, 1, cap, tmp.p);
     if (st == N1K_OK) HIP_TRY(h, hipStreamSynchronize(h->stream));
-    tmp.release();
     return st;
     });
 }
@@ -584,14 +582,7 @@ void n1k_comm_destroy(n1k_comm* c) {
         if (c->comm) (void)ncclCommDestroy(c->comm);
         if (c->ev) (void)hipEventDestroy(c->ev);
         if (c->ev_consumed) (void)hipEventDestroy(c->ev_consumed);
-        c->void_send.release();
-        c->void_recv.release();
-        c->send.release();
-        c->recv.release();
-        c->gsend.release();
-        c->grecv.release();
-        c->scalar.release();
-        delete c;
+        delete c;  // (its buffers with it)
     } catch (...) {
     }
 }
@@ -682,8 +673,8 @@ n1k_status void_regions(n1k_comm* c, n1k_handle* snd, size_t region, size_t head
 
 // test hook (option inject_failure, one shot): pretend that `site` failed on this handle
 bool injected(n1k_handle* h, uint32_t site) {
-    if (h->opt_inject_failure != site) return false;
-    h->opt_inject_failure = 0;
+    if (h->opt.inject_failure != site) return false;
+    h->opt.inject_failure = 0;
     return true;
 }
 
@@ -834,14 +825,14 @@ n1k_status exchange_rows_impl(n1k_comm* c, n1k_handle* sender, const n1k_batch* 
             A.per_dest = 1;
             for (uint32_t d = 0; d < P; d++) A.dest_cap[d] = (uint32_t)cap[d];
         }
-        A.err_flags = sender->d_errp;
+        A.err_flags = sender->groups.errp;
         s = run_partition(sender, batch, A);
         if (s != N1K_OK) return s;
         if (injected(sender, 2)) return fail(sender, N1K_DEVICE_ERROR, "injected failure: the partition");
-        sender->stats.rows_in += batch->nrows;
-        sender->stats.batches += 1;
+        sender->timing.stats.rows_in += batch->nrows;
+        sender->timing.stats.batches += 1;
         // what the partition itself found (rows whose key does not pack, values the Filter cannot order) joins the verdicts
-        HIP_TRY(sender, launch_stamp_verdict((unsigned long long*)c->send.p, P, stride / 8, sender->d_errp, 0, sender->stream));
+        HIP_TRY(sender, launch_stamp_verdict((unsigned long long*)c->send.p, P, stride / 8, sender->groups.errp, 0, sender->stream));
         return N1K_OK;
     };
     if (local == N1K_OK) local = local_part();
@@ -880,7 +871,7 @@ n1k_status exchange_rows_impl(n1k_comm* c, n1k_handle* sender, const n1k_batch* 
     {
         HeaderList H{};
         for (uint32_t sidx = 0; sidx < P; sidx++) H.h[sidx] = (unsigned long long*)src[sidx];
-        HIP_TRY(receiver, launch_exchange_verdict(H, P, receiver->d_errp, receiver->stream));
+        HIP_TRY(receiver, launch_exchange_verdict(H, P, receiver->groups.errp, receiver->stream));
     }
     if (injected(sender, 3)) return fail(sender, N1K_DEVICE_ERROR, "injected failure: the receiving part");
     for (uint32_t sidx = 0; sidx < P; sidx++) {

@@ -288,10 +288,8 @@ n1k_status ensure_match_table(n1k_handle* h) {
             HIP_TRY(h, nb.ensure(std::max(n, M.d_bits.n * 2) + 4));
             hipError_t e = hipStreamSynchronize(h->stream);
             if (e == hipSuccess && first) e = hipMemcpy(nb.p, M.d_bits.p, first, hipMemcpyDeviceToDevice);
-            if (e != hipSuccess) nb.release();
             HIP_TRY(h, e);
-            M.d_bits.release();
-            M.d_bits = nb;
+            M.d_bits = std::move(nb);
         }
         const size_t cnt = n - first;
         std::vector<uint64_t> off(cnt + 1);
@@ -381,9 +379,7 @@ static n1k_status match_alone(int kind, n1k_status (*parse)(const char*, size_t,
                               size_t text_len, uint64_t n, const uint64_t* offsets, const char* bytes, uint8_t* out_bits, uint64_t* out_left_to_host) {
     return guarded(nullptr, [&]() -> n1k_status {
     if (!block_args_ok(text, text_len, n, offsets, bytes, out_bits, on_device)) return N1K_INVALID;
-    struct Table : MatchTable {
-        ~Table() { release(); }
-    } M;
+    MatchTable M;
     const n1k_status st = parse(text, text_len, M);
     if (st != N1K_OK) return st;
     if (out_left_to_host) *out_left_to_host = 0;

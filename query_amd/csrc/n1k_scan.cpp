@@ -26,7 +26,7 @@ bool build_fast_args(n1k_handle* h, uint32_t max_slots, FastArgs& F, bool fuse, 
             }
         F.nderived = nd;
     }
-    if (h->opt_fast == 0 || P.want_rep_row || P.ncols == 0 || (!fuse && P.ncols > (uint32_t)kFastCols)) return false;
+    if (h->opt.fast == 0 || P.want_rep_row || P.ncols == 0 || (!fuse && P.ncols > (uint32_t)kFastCols)) return false;
     if (P.nkeys > (uint32_t)kFastKeys || (!partition_only && (P.naggs > (uint32_t)kFastAggs || P.naggs == 0))) return false;
     // predicate: none, one term, or AND of two terms
     uint32_t term_ix[2] = {0, 0};
@@ -87,7 +87,7 @@ bool build_fast_args(n1k_handle* h, uint32_t max_slots, FastArgs& F, bool fuse, 
         F.lds_slots = (uint32_t)std::max<uint64_t>(domain, 2);
     } else {
         F.hashed = 1;
-        uint32_t slots = (uint32_t)std::min<uint64_t>(h->opt_lds_bytes / (P.lds_words * 8), 1u << 15);
+        uint32_t slots = (uint32_t)std::min<uint64_t>(h->opt.lds_bytes / (P.lds_words * 8), 1u << 15);
         if (slots < 16) return false;
         F.lds_slots = slots;
         F.lds_max_fill = std::max(1u, (uint32_t)((uint64_t)slots * 5 / 8));
@@ -99,7 +99,7 @@ bool build_fast_args(n1k_handle* h, uint32_t max_slots, FastArgs& F, bool fuse, 
         if (ag.distinct) {
             // COUNT(DISTINCT column) whose members leave as one word: the specialised kernels scatter them into hash
             // regions; anything else DISTINCT stays with the interpreter kernel
-            if (ag.kind != AGG_COUNT || !ag.has_operand || ag.src.is_const || !h->layout_fixed || !h->distinct_words[ag.log_index] ||
+            if (ag.kind != AGG_COUNT || !ag.has_operand || ag.src.is_const || !h->layout_fixed || !h->distinct.words[ag.log_index] ||
                 ++ndist > kSpecDistinct)
                 return false;
         }
@@ -164,8 +164,8 @@ n1k_status run_group_batch(n1k_handle* h, const n1k_batch* b) {
     if (h->has_distinct) {
         // every qualifying operand appends one (group key, value, class) pair: at most one per row and aggregate
         uint64_t need = h->row_base + b->nrows;
-        if (need > h->log_capacity) {
-            uint64_t cap = std::max<uint64_t>(need, h->log_capacity * 2);
+        if (need > h->distinct.log_capacity) {
+            uint64_t cap = std::max<uint64_t>(need, h->distinct.log_capacity * 2);
             HIP_TRY(h, hipStreamSynchronize(h->stream));
             for (uint32_t d = 0; d < h->n_distinct; d++) {
                 DevBuf<uint64_t> nk, nv, nw;
@@ -173,49 +173,45 @@ n1k_status run_group_batch(n1k_handle* h, const n1k_batch* b) {
                 HIP_TRY(h, nk.ensure(cap));
                 HIP_TRY(h, nv.ensure(cap));
                 HIP_TRY(h, nc.ensure(cap));
-                if (h->distinct_words[d]) HIP_TRY(h, nw.ensure(cap));
-                if (h->log_capacity) {
-                    HIP_TRY(h, hipMemcpy(nk.p, h->d_log_key[d].p, h->log_capacity * 8, hipMemcpyDeviceToDevice));
-                    HIP_TRY(h, hipMemcpy(nv.p, h->d_log_val[d].p, h->log_capacity * 8, hipMemcpyDeviceToDevice));
-                    HIP_TRY(h, hipMemcpy(nc.p, h->d_log_cls[d].p, h->log_capacity, hipMemcpyDeviceToDevice));
-                    if (h->distinct_words[d])
-                        HIP_TRY(h, hipMemcpy(nw.p, h->d_log_word[d].p, h->log_capacity * 8, hipMemcpyDeviceToDevice));
+                if (h->distinct.words[d]) HIP_TRY(h, nw.ensure(cap));
+                if (h->distinct.log_capacity) {
+                    HIP_TRY(h, hipMemcpy(nk.p, h->distinct.log_key[d].p, h->distinct.log_capacity * 8, hipMemcpyDeviceToDevice));
+                    HIP_TRY(h, hipMemcpy(nv.p, h->distinct.log_val[d].p, h->distinct.log_capacity * 8, hipMemcpyDeviceToDevice));
+                    HIP_TRY(h, hipMemcpy(nc.p, h->distinct.log_cls[d].p, h->distinct.log_capacity, hipMemcpyDeviceToDevice));
+                    if (h->distinct.words[d])
+                        HIP_TRY(h, hipMemcpy(nw.p, h->distinct.log_word[d].p, h->distinct.log_capacity * 8, hipMemcpyDeviceToDevice));
                 }
-                h->d_log_key[d].release();
-                h->d_log_val[d].release();
-                h->d_log_cls[d].release();
-                h->d_log_word[d].release();
-                h->d_log_key[d] = nk;
-                h->d_log_val[d] = nv;
-                h->d_log_cls[d] = nc;
-                h->d_log_word[d] = nw;
+                h->distinct.log_key[d] = std::move(nk);
+                h->distinct.log_val[d] = std::move(nv);
+                h->distinct.log_cls[d] = std::move(nc);
+                h->distinct.log_word[d] = std::move(nw);
             }
-            h->log_capacity = cap;
+            h->distinct.log_capacity = cap;
         }
         for (uint32_t d = 0; d < h->n_distinct; d++) {
-            A.log_key[d] = h->d_log_key[d].p;
-            A.log_val[d] = h->d_log_val[d].p;
-            A.log_cls[d] = h->d_log_cls[d].p;
-            A.log_word[d] = h->distinct_words[d] ? h->d_log_word[d].p : nullptr;
+            A.log_key[d] = h->distinct.log_key[d].p;
+            A.log_val[d] = h->distinct.log_val[d].p;
+            A.log_cls[d] = h->distinct.log_cls[d].p;
+            A.log_word[d] = h->distinct.words[d] ? h->distinct.log_word[d].p : nullptr;
         }
-        A.log_cursor = h->d_counters.p + 8;
-        A.word_cursor = h->d_counters.p + 16;
-        A.log_capacity = h->log_capacity;
-        A.nw_key_bits = h->nw_key_bits;
-        A.nw_val_bits = h->nw_val_bits;
-        if (!h->d_word_hist.p) {
-            HIP_TRY(h, h->d_word_hist.ensure(kMaxDistinct * 256));
-            HIP_TRY(h, hipMemsetAsync(h->d_word_hist.p, 0, kMaxDistinct * 256 * sizeof(unsigned long long), h->stream));
+        A.log_cursor = h->groups.counters.p + 8;
+        A.word_cursor = h->groups.counters.p + 16;
+        A.log_capacity = h->distinct.log_capacity;
+        A.nw_key_bits = h->distinct.nw_key_bits;
+        A.nw_val_bits = h->distinct.nw_val_bits;
+        if (!h->distinct.word_hist.p) {
+            HIP_TRY(h, h->distinct.word_hist.ensure(kMaxDistinct * 256));
+            HIP_TRY(h, hipMemsetAsync(h->distinct.word_hist.p, 0, kMaxDistinct * 256 * sizeof(unsigned long long), h->stream));
         }
-        A.word_hist = h->d_word_hist.p;
+        A.word_hist = h->distinct.word_hist.p;
         bool any_words = false;
-        for (uint32_t d = 0; d < h->n_distinct; d++) any_words |= h->distinct_words[d];
+        for (uint32_t d = 0; d < h->n_distinct; d++) any_words |= h->distinct.words[d];
         A.dcache_aggs = any_words ? h->n_distinct : 0;
         A.dcache_slots = any_words ? 4096u / (h->n_distinct > 2 ? 4u : h->n_distinct) : 0;  // 32 KB of LDS in all
     }
-    uint32_t block = h->opt_block ? h->opt_block : 1024;
-    uint32_t rpl = block == 1024 ? h->opt_rows_per_lane : 4;
-    uint32_t max_slots = h->opt_lds_bytes / (P.lds_words * 8);
+    uint32_t block = h->opt.block ? h->opt.block : 1024;
+    uint32_t rpl = block == 1024 ? h->opt.rows_per_lane : 4;
+    uint32_t max_slots = h->opt.lds_bytes / (P.lds_words * 8);
     max_slots = (uint32_t)std::min<uint64_t>(max_slots, 1u << 15);
     if (max_slots < 2) return fail(h, N1K_UNSUPPORTED, "accumulator row too wide for LDS");
     FastArgs F;
@@ -225,8 +221,8 @@ n1k_status run_group_batch(n1k_handle* h, const n1k_batch* b) {
     // registers (same conditions as the kernel choice below)?  If not they become derived columns now.
     bool fuse = false;
     if (!h->derived_ready) {
-        if (h->opt_fuse_arith && h->opt_agg_mode != N1K_MODE_LDS_HASH && h->opt_spec && h->opt_jit &&
-            (h->opt_jit == 2 || b->nrows >= h->opt_jit_min_rows) && build_fast_args(h, direct_max_slots, F, true)) {
+        if (h->opt.fuse_arith && h->opt.agg_mode != N1K_MODE_LDS_HASH && h->opt.spec && h->opt.jit &&
+            (h->opt.jit == 2 || b->nrows >= h->opt.jit_min_rows) && build_fast_args(h, direct_max_slots, F, true)) {
             bool kh = false;
             for (uint32_t k = 0; k < F.nkeys; k++) kh |= F.keys[k].col >= F.ncols || F.cols[F.keys[k].col].kind != COLK_DICT32;
             if ((size_t)F.lds_slots * P.lds_words * 8 <= 64 * 1024 && kh == (F.hashed != 0)) {
@@ -242,7 +238,7 @@ n1k_status run_group_batch(n1k_handle* h, const n1k_batch* b) {
             if (st != N1K_OK) return st;
         }
     }
-    if (h->opt_agg_mode != N1K_MODE_LDS_HASH && build_fast_args(h, direct_max_slots, F, fuse)) {
+    if (h->opt.agg_mode != N1K_MODE_LDS_HASH && build_fast_args(h, direct_max_slots, F, fuse)) {
         // Shapes with COUNT(DISTINCT): the specialised kernels keep nothing of a DISTINCT aggregate in the workgroup
         // table (its member words go to the hash regions), so they run on a copy of the program with a compact LDS layout
         Program Pc;
@@ -274,28 +270,28 @@ n1k_status run_group_batch(n1k_handle* h, const n1k_batch* b) {
         }
         const uint32_t lds_total = table_bytes + scatter_bytes + ndist * dcache_slots * 8u + match_lds;
         // workgroups per CU that fit: 512 threads x 3 (<= 48 KiB each), x 2 (<= 72 KiB), else 1024 threads x 1
-        uint32_t fblock = h->opt_block == 1024 || h->opt_block == 512 ? h->opt_block : (table_bytes <= 72 * 1024 ? 512u : 1024u);
+        uint32_t fblock = h->opt.block == 1024 || h->opt.block == 512 ? h->opt.block : (table_bytes <= 72 * 1024 ? 512u : 1024u);
         if (ndist) fblock = 512;
         uint32_t per_cu = fblock == 512 ? (lds_total <= 48 * 1024 ? 3u : (lds_total <= 72 * 1024 ? 2u : 1u))
                                         : (lds_total <= 72 * 1024 ? 2u : 1u);
         if (ndist) per_cu = std::max(1u, std::min(3u, 160u * 1024u / (lds_total + 512u)));  // (two workgroups of 80 KiB fit a CU)
-        uint32_t frpl = h->opt_rows_per_lane;
-        uint32_t fgrid = h->opt_grid_blocks ? h->opt_grid_blocks : (uint32_t)(h->num_cus * per_cu);
+        uint32_t frpl = h->opt.rows_per_lane;
+        uint32_t fgrid = h->opt.grid_blocks ? h->opt.grid_blocks : (uint32_t)(h->num_cus * per_cu);
         // slabs + merge kernel pay off once the table is more than a few KiB
-        const bool use_slabs = !F.hashed && (h->opt_slabs == 1 ? table_bytes >= 4096 : h->opt_slabs == 2);
-        F.err_flags = h->d_errp;
-        F.rows_selected = h->d_counters.p + 0;
+        const bool use_slabs = !F.hashed && (h->opt.slabs == 1 ? table_bytes >= 4096 : h->opt.slabs == 2);
+        F.err_flags = h->groups.errp;
+        F.rows_selected = h->groups.counters.p + 0;
         // a prebuilt plan-specialised kernel of exactly this shape?
         // (segmented batches — a received row region — run on the run-time-built variant of the shape only: the prebuilt
         //  kernels carry none of the segment bookkeeping)
         SpecSig sig = make_plan_sig(h, F);
         sig.seg = h->push_nseg > 1 ? 1 : 0;
-        const SpecEntry* spec = h->opt_spec && !sig.seg ? find_spec(sig) : nullptr;
+        const SpecEntry* spec = h->opt.spec && !sig.seg ? find_spec(sig) : nullptr;
         // no prebuilt kernel of this shape: instantiate the same template at run time (large batches, or forced)
         const JitKernel* jit = nullptr;
         bool key_kinds_hashed = false;
         for (uint32_t k = 0; k < F.nkeys; k++) key_kinds_hashed |= F.keys[k].col >= F.ncols || F.cols[F.keys[k].col].kind != COLK_DICT32;  // (a fused node is a TAGGED64 value)
-        if (!spec && h->opt_spec && h->opt_jit && (h->opt_jit == 2 || b->nrows >= h->opt_jit_min_rows) &&
+        if (!spec && h->opt.spec && h->opt.jit && (h->opt.jit == 2 || b->nrows >= h->opt.jit_min_rows) &&
             table_bytes <= 64 * 1024 && key_kinds_hashed == (F.hashed != 0)) {
             jit = jit_get(sig);
             if (jit->failed) {
@@ -306,9 +302,9 @@ n1k_status run_group_batch(n1k_handle* h, const n1k_batch* b) {
         if (jit && fblock != 512) {  // run-time instantiations are built for 512-thread workgroups
             fblock = 512;
             per_cu = table_bytes + match_lds <= 48 * 1024 ? 3u : 2u;
-            fgrid = h->opt_grid_blocks ? h->opt_grid_blocks : (uint32_t)(h->num_cus * per_cu);
+            fgrid = h->opt.grid_blocks ? h->opt.grid_blocks : (uint32_t)(h->num_cus * per_cu);
         }
-        h->stats.spec_kernel = spec ? 1u : (jit ? (F.nderived ? 3u : 2u) : 0u);
+        h->timing.stats.spec_kernel = spec ? 1u : (jit ? (F.nderived ? 3u : 2u) : 0u);
         if (F.nderived && !jit) return fail(h, N1K_DEVICE_ERROR, "fused arithmetic without its kernel");  // (decided above)
         if ((F.hashed || ndist || h->push_nrows_dev || h->push_nseg) && !spec && !jit) goto interpreter;  // the bounded-shape kernel is DIRECT only, no DISTINCT
         F.nrows_dev = h->push_nrows_dev;
@@ -326,14 +322,14 @@ n1k_status run_group_batch(n1k_handle* h, const n1k_batch* b) {
             // pushed so far plus a quarter (mix64 spreads distinct words evenly; many copies of few words overflow into the
             // plain word log)
             const uint64_t rows_total = h->row_base + b->nrows;
-            uint64_t need = h->opt_region_cap ? h->opt_region_cap : (rows_total + rows_total / 4) / kWordSubs + 4096;
+            uint64_t need = h->opt.region_cap ? h->opt.region_cap : (rows_total + rows_total / 4) / kWordSubs + 4096;
             need = (need + 15) / 16 * 16;  // whole 128-byte lines
-            if (!h->d_wcursor.p) {
-                HIP_TRY(h, h->d_wcursor.ensure(kMaxDistinct * kWordSubs * kCursorStride));
-                HIP_TRY(h, hipMemsetAsync(h->d_wcursor.p, 0, kMaxDistinct * kWordSubs * kCursorStride * sizeof(unsigned long long), h->stream));
+            if (!h->distinct.wcursor.p) {
+                HIP_TRY(h, h->distinct.wcursor.ensure(kMaxDistinct * kWordSubs * kCursorStride));
+                HIP_TRY(h, hipMemsetAsync(h->distinct.wcursor.p, 0, kMaxDistinct * kWordSubs * kCursorStride * sizeof(unsigned long long), h->stream));
             }
-            if (need > h->wregion_cap) {
-                const uint64_t ncap = (std::max<uint64_t>(need, h->wregion_cap * 2) + 15) / 16 * 16;
+            if (need > h->distinct.wregion_cap) {
+                const uint64_t ncap = (std::max<uint64_t>(need, h->distinct.wregion_cap * 2) + 15) / 16 * 16;
                 if (ncap >= 0xFFFFFF00ull) return fail(h, N1K_OOM, "COUNT(DISTINCT): more than 2^32 words per hash region");
                 HIP_TRY(h, hipStreamSynchronize(h->stream));
                 for (uint32_t a = 0; a < P.naggs; a++) {
@@ -341,21 +337,20 @@ n1k_status run_group_batch(n1k_handle* h, const n1k_batch* b) {
                     const uint32_t li = P.aggs[a].log_index;
                     DevBuf<uint64_t> nb;
                     HIP_TRY(h, nb.ensure(kWordSubs * ncap));
-                    if (h->wregion_cap && h->wregion_used)
-                        HIP_TRY(h, launch_regrow_regions(h->d_wregion[li].p, kWordSubs, h->wregion_cap, nb.p, ncap,
-                                                         h->d_wcursor.p + (size_t)li * kWordSubs * kCursorStride, h->stream));  // (clamps the cursors of regions that had overflowed)
+                    if (h->distinct.wregion_cap && h->distinct.wregion_used)
+                        HIP_TRY(h, launch_regrow_regions(h->distinct.wregion[li].p, kWordSubs, h->distinct.wregion_cap, nb.p, ncap,
+                                                         h->distinct.wcursor.p + (size_t)li * kWordSubs * kCursorStride, h->stream));  // (clamps the cursors of regions that had overflowed)
                     HIP_TRY(h, hipStreamSynchronize(h->stream));
-                    h->d_wregion[li].release();
-                    h->d_wregion[li] = nb;
+                    h->distinct.wregion[li] = std::move(nb);
                 }
-                h->wregion_cap = ncap;
+                h->distinct.wregion_cap = ncap;
             }
             uint32_t d = 0;
             for (uint32_t a = 0; a < P.naggs; a++) {
                 if (!P.aggs[a].distinct) continue;
                 const uint32_t li = P.aggs[a].log_index;
-                L.region[d] = h->d_wregion[li].p;
-                L.region_cursor[d] = h->d_wcursor.p + (size_t)li * kWordSubs * kCursorStride;
+                L.region[d] = h->distinct.wregion[li].p;
+                L.region_cursor[d] = h->distinct.wcursor.p + (size_t)li * kWordSubs * kCursorStride;
                 L.over_word[d] = A.log_word[li];
                 L.log_key[d] = A.log_key[li];
                 L.log_val[d] = A.log_val[li];
@@ -363,16 +358,16 @@ n1k_status run_group_batch(n1k_handle* h, const n1k_batch* b) {
                 L.log_index[d] = li;
                 d++;
             }
-            L.region_cap = h->wregion_cap;
+            L.region_cap = h->distinct.wregion_cap;
             L.over_cursor = A.word_cursor;
             L.over_hist = A.word_hist;
             L.over_capacity = A.log_capacity;
             L.log_cursor = A.log_cursor;
             L.log_capacity = A.log_capacity;
-            L.nw_key_bits = h->nw_key_bits;
-            L.nw_val_bits = h->nw_val_bits;
+            L.nw_key_bits = h->distinct.nw_key_bits;
+            L.nw_val_bits = h->distinct.nw_val_bits;
             L.dcache_slots = dcache_slots;
-            h->wregion_used = true;
+            h->distinct.wregion_used = true;
         }
         hipEvent_t e0 = get_event(h), e1 = get_event(h);
         if (e0) (void)hipEventRecord(e0, h->stream);
@@ -391,7 +386,7 @@ n1k_status run_group_batch(n1k_handle* h, const n1k_batch* b) {
             }
             if (spec || jit) {
                 // WIDE launch over the even prefix (2 adjacent rows per lane and load), scalar launch for an odd last row
-                bool wide = aligned && h->opt_wide && n >= 2;
+                bool wide = aligned && h->opt.wide && n >= 2;
                 // (a row count that lives on the device may be odd: the kernel masks the last item's second row itself)
                 uint64_t n_main = wide && !h->push_nrows_dev && !h->push_nseg ? (n & ~1ull) : n;
                 F.nrows = (uint32_t)n_main;
@@ -402,14 +397,14 @@ n1k_status run_group_batch(n1k_handle* h, const n1k_batch* b) {
                 uint32_t g = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(fgrid, tiles));
                 F.slabs = nullptr;
                 if (use_slabs && g > 1) {
-                    HIP_TRY(h, h->d_slabs.ensure((size_t)g * P.lds_words * F.lds_slots));
-                    HIP_TRY(h, h->d_block_sel.ensure(g));
-                    F.slabs = h->d_slabs.p;
-                    F.block_selected = h->d_block_sel.p;
+                    HIP_TRY(h, h->groups.slabs.ensure((size_t)g * P.lds_words * F.lds_slots));
+                    HIP_TRY(h, h->groups.block_sel.ensure(g));
+                    F.slabs = h->groups.slabs.p;
+                    F.block_selected = h->groups.block_sel.p;
                 }
-                if (spec) HIP_TRY(h, spec->launch(P, F, h->table, h->d_counters.p + 1, g, fblock, wide, L, h->stream));
-                else HIP_TRY(h, jit_launch(jit, P, F, h->table, h->d_counters.p + 1, g, wide, L, ndist, h->stream));
-                if (F.slabs) HIP_TRY(h, launch_merge_slabs(P, F, h->table, g, h->d_counters.p + 1, h->stream, h->opt_merge_chunks));
+                if (spec) HIP_TRY(h, spec->launch(P, F, h->groups.table, h->groups.counters.p + 1, g, fblock, wide, L, h->stream));
+                else HIP_TRY(h, jit_launch(jit, P, F, h->groups.table, h->groups.counters.p + 1, g, wide, L, ndist, h->stream));
+                if (F.slabs) HIP_TRY(h, launch_merge_slabs(P, F, h->groups.table, g, h->groups.counters.p + 1, h->stream, h->opt.merge_chunks));
                 F.slabs = nullptr;
                 if (n_main < n) {
                     for (uint32_t c = 0; c < F.ncols; c++) {
@@ -419,8 +414,8 @@ n1k_status run_group_batch(n1k_handle* h, const n1k_batch* b) {
                     }
                     F.nrows = (uint32_t)(n - n_main);
                     F.row_base += n_main;
-                    if (spec) HIP_TRY(h, spec->launch(P, F, h->table, h->d_counters.p + 1, 1, fblock, false, L, h->stream));
-                    else HIP_TRY(h, jit_launch(jit, P, F, h->table, h->d_counters.p + 1, 1, false, L, ndist, h->stream));
+                    if (spec) HIP_TRY(h, spec->launch(P, F, h->groups.table, h->groups.counters.p + 1, 1, fblock, false, L, h->stream));
+                    else HIP_TRY(h, jit_launch(jit, P, F, h->groups.table, h->groups.counters.p + 1, 1, false, L, ndist, h->stream));
                 }
                 continue;
             }
@@ -429,23 +424,23 @@ n1k_status run_group_batch(n1k_handle* h, const n1k_batch* b) {
             uint32_t g = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(fgrid, tiles));
             F.slabs = nullptr;
             if (use_slabs && g > 1) {
-                HIP_TRY(h, h->d_slabs.ensure((size_t)g * P.lds_words * F.lds_slots));
-                HIP_TRY(h, h->d_block_sel.ensure(g));
-                F.slabs = h->d_slabs.p;
-                F.block_selected = h->d_block_sel.p;
+                HIP_TRY(h, h->groups.slabs.ensure((size_t)g * P.lds_words * F.lds_slots));
+                HIP_TRY(h, h->groups.block_sel.ensure(g));
+                F.slabs = h->groups.slabs.p;
+                F.block_selected = h->groups.block_sel.p;
             }
-            HIP_TRY(h, launch_scan_fast(P, F, h->table, h->d_counters.p + 1, g, fblock, frpl, h->stream));
-            if (F.slabs) HIP_TRY(h, launch_merge_slabs(P, F, h->table, g, h->d_counters.p + 1, h->stream, h->opt_merge_chunks));
+            HIP_TRY(h, launch_scan_fast(P, F, h->groups.table, h->groups.counters.p + 1, g, fblock, frpl, h->stream));
+            if (F.slabs) HIP_TRY(h, launch_merge_slabs(P, F, h->groups.table, g, h->groups.counters.p + 1, h->stream, h->opt.merge_chunks));
             F.slabs = nullptr;
         }
         if (e1) (void)hipEventRecord(e1, h->stream);
-        h->events.emplace_back(e0, e1);
-        h->stats.agg_mode = F.hashed ? N1K_MODE_LDS_HASH : N1K_MODE_LDS_DIRECT;
+        h->timing.events.emplace_back(e0, e1);
+        h->timing.stats.agg_mode = F.hashed ? N1K_MODE_LDS_HASH : N1K_MODE_LDS_DIRECT;
         return N1K_OK;
     }
 interpreter:
     // DIRECT: every key is dictionary coded and the whole key domain fits the LDS table -> perfect hash
-    bool direct = h->opt_agg_mode != N1K_MODE_LDS_HASH;
+    bool direct = h->opt.agg_mode != N1K_MODE_LDS_HASH;
     uint64_t domain = 1;
     for (uint32_t k = 0; k < P.nkeys && direct; k++) {
         if (P.keys[k].mode != KEYM_DICT) direct = false;
@@ -459,12 +454,12 @@ interpreter:
     if (P.nkeys == 0) slots = 2;
     A.lds_slots = slots;
     A.lds_max_fill = std::max(1u, (uint32_t)((uint64_t)slots * 5 / 8));
-    A.err_flags = h->d_errp;
-    A.rows_selected = h->d_counters.p + 0;
+    A.err_flags = h->groups.errp;
+    A.rows_selected = h->groups.counters.p + 0;
     uint64_t tile_rows = (uint64_t)block * rpl;
     uint64_t ntiles = (b->nrows + tile_rows - 1) / tile_rows;
     uint32_t per_cu = block == 1024 ? 1 : (block == 512 ? 2 : 4);
-    uint32_t grid = h->opt_grid_blocks ? h->opt_grid_blocks : (uint32_t)(h->num_cus * per_cu);
+    uint32_t grid = h->opt.grid_blocks ? h->opt.grid_blocks : (uint32_t)(h->num_cus * per_cu);
     grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(grid, ntiles));
     hipEvent_t e0 = get_event(h), e1 = get_event(h);
     if (e0) (void)hipEventRecord(e0, h->stream);
@@ -484,13 +479,13 @@ interpreter:
             As.nrows_dev = h->push_seg_counts + (size_t)sg * kCursorStride;
             const uint64_t nt = (h->push_seg_rows + tile_rows - 1) / tile_rows;
             const uint32_t g = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(grid, nt));
-            HIP_TRY(h, launch_scan_group(Ps, As, h->table, h->d_counters.p + 1, g, block, rpl, direct, h->stream));
+            HIP_TRY(h, launch_scan_group(Ps, As, h->groups.table, h->groups.counters.p + 1, g, block, rpl, direct, h->stream));
         }
     } else
-        HIP_TRY(h, launch_scan_group(P, A, h->table, h->d_counters.p + 1, grid, block, rpl, direct, h->stream));
+        HIP_TRY(h, launch_scan_group(P, A, h->groups.table, h->groups.counters.p + 1, grid, block, rpl, direct, h->stream));
     if (e1) (void)hipEventRecord(e1, h->stream);
-    h->events.emplace_back(e0, e1);
-    h->stats.agg_mode = direct ? N1K_MODE_LDS_DIRECT : N1K_MODE_LDS_HASH;
+    h->timing.events.emplace_back(e0, e1);
+    h->timing.stats.agg_mode = direct ? N1K_MODE_LDS_DIRECT : N1K_MODE_LDS_HASH;
     return N1K_OK;
 }
 
@@ -502,32 +497,32 @@ n1k_status run_filter_batch(n1k_handle* h, const n1k_batch* b) {
     // ONE pass (filter_stream_kernel): predicate, ordered compaction and the tiles' offsets by a chained scan; the ordinals
     // land in a buffer sized for every row, the host reads the count and copies that many
     const uint64_t ntiles = (b->nrows + kFilterStreamTile - 1) / kFilterStreamTile;
-    HIP_TRY(h, h->d_tile_off.ensure(ntiles + 1));
-    HIP_TRY(h, h->d_sel.ensure(b->nrows));
+    HIP_TRY(h, h->filter.tile_off.ensure(ntiles + 1));
+    HIP_TRY(h, h->filter.sel.ensure(b->nrows));
     uint32_t grid = (uint32_t)std::min<uint64_t>(ntiles, (uint64_t)h->num_cus * 4);  // (124 VGPRs: four 256-thread workgroups per CU)
     // one comparison of a TAGGED64 column with a NUMBER constant, arrays aligned for two rows per load: the wide variant
-    bool fast = h->opt_wide && P.nlogic == 1 && P.logic[0].op == LOGIC_PUSH;
+    bool fast = h->opt.wide && P.nlogic == 1 && P.logic[0].op == LOGIC_PUSH;
     if (fast) {
         const Term& t = P.terms[P.logic[0].arg];
         fast = t.op >= TERM_NUM_LT && t.op <= TERM_NUM_EQ && !t.a.is_const && t.a.col < (uint32_t)h->plan.paths.size() &&
                P.cols[t.a.col].kind == COLK_TAGGED64 && (uintptr_t)P.cols[t.a.col].payload % 16 == 0 && (uintptr_t)P.cols[t.a.col].tags % 2 == 0;
     }
-    if (fast) grid = (uint32_t)std::min<uint64_t>(ntiles, (uint64_t)h->num_cus * (h->opt_grid_blocks ? h->opt_grid_blocks : 5));  // (84 VGPRs; measured 4: 0.43, 5: 0.39, 6: 0.40, 8: 0.40 ms per 100 M rows)
+    if (fast) grid = (uint32_t)std::min<uint64_t>(ntiles, (uint64_t)h->num_cus * (h->opt.grid_blocks ? h->opt.grid_blocks : 5));  // (84 VGPRs; measured 4: 0.43, 5: 0.39, 6: 0.40, 8: 0.40 ms per 100 M rows)
     if (e0) (void)hipEventRecord(e0, h->stream);
-    HIP_TRY(h, launch_filter_stream(P, b->nrows, h->row_base, h->d_sel.p, (unsigned long long*)h->d_tile_off.p,
-                                    (unsigned long long*)h->d_tile_off.p + ntiles, h->d_counters.p + 3, h->d_errp, grid, h->stream, fast));
-    h->stats.spec_kernel = fast ? 1u : 0u;
+    HIP_TRY(h, launch_filter_stream(P, b->nrows, h->row_base, h->filter.sel.p, (unsigned long long*)h->filter.tile_off.p,
+                                    (unsigned long long*)h->filter.tile_off.p + ntiles, h->groups.counters.p + 3, h->groups.errp, grid, h->stream, fast));
+    h->timing.stats.spec_kernel = fast ? 1u : 0u;
     if (e1) (void)hipEventRecord(e1, h->stream);  // device time excludes the PCIe copy of the ordinals
-    HIP_TRY(h, hipMemcpyAsync(&total, h->d_counters.p + 3, sizeof total, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(&total, h->groups.counters.p + 3, sizeof total, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     if (total) {
-        size_t old = h->selected.size();
-        h->selected.resize(old + total);
-        HIP_TRY(h, hipMemcpyAsync(h->selected.data() + old, h->d_sel.p, total * 8, hipMemcpyDeviceToHost, h->stream));
+        size_t old = h->filter.selected.size();
+        h->filter.selected.resize(old + total);
+        HIP_TRY(h, hipMemcpyAsync(h->filter.selected.data() + old, h->filter.sel.p, total * 8, hipMemcpyDeviceToHost, h->stream));
     }
-    h->events.emplace_back(e0, e1);
+    h->timing.events.emplace_back(e0, e1);
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    h->stats.rows_selected += total;
+    h->timing.stats.rows_selected += total;
     return N1K_OK;
 }
 
@@ -604,7 +599,7 @@ n1k_status materialize_derived(n1k_handle* h, const n1k_batch* b) {
         A.out_tags = h->dv_tags[i].p;
         A.out_payload = h->dv_payload[i].p;
         A.str_rank = h->d_rank.p;
-        A.err_flags = h->d_errp;
+        A.err_flags = h->groups.errp;
         HIP_TRY(h, launch_arith(A, h->stream));
         DevCol& d = P.cols[ni + i];
         d.kind = COLK_TAGGED64;
@@ -632,14 +627,14 @@ n1k_status push_device(n1k_handle* h, const n1k_batch* b) {
     // large batch run through the scan kernels; if they bring many new groups, the rest is partitioned (below).
     st = flush_pending(h);  // a region kept from the previous batch joins the table before more rows arrive
     if (st != N1K_OK) return st;
-    const bool first_rows = h->row_base == 0 && h->merged_groups_bound == 0;  // nothing in the handle yet
+    const bool first_rows = h->row_base == 0 && h->groups.merged_bound == 0;  // nothing in the handle yet
     PartitionPlan pp;
     const bool can_partition = h->plan.has_group && !h->push_nrows_dev && !h->push_nseg && partition_eligible(h, pp);
     uint64_t head = b->nrows;
     bool decide = false;
-    if (can_partition && h->opt_agg_mode == N1K_MODE_PARTITIONED) head = 0;
-    else if (can_partition && h->opt_agg_mode == N1K_MODE_AUTO && b->nrows >= h->opt_partition_min_rows && !small_key_domain(h)) {
-        head = std::min<uint64_t>(b->nrows, h->opt_partition_probe_rows);
+    if (can_partition && h->opt.agg_mode == N1K_MODE_PARTITIONED) head = 0;
+    else if (can_partition && h->opt.agg_mode == N1K_MODE_AUTO && b->nrows >= h->opt.partition_min_rows && !small_key_domain(h)) {
+        head = std::min<uint64_t>(b->nrows, h->opt.partition_probe_rows);
         decide = true;
     }
     auto view = [&](uint64_t off, uint64_t n, std::vector<n1k_col>& cols, n1k_batch& v) {
@@ -666,23 +661,23 @@ n1k_status push_device(n1k_handle* h, const n1k_batch* b) {
     if (st != N1K_OK) return st;
     bool partition = can_partition && head == 0 && b->nrows > 0;
     uint64_t groups_est = b->nrows;
-    if (decide && first_rows && h->opt_partition_sticky && h->sticky.valid && b->nrows >= h->sticky.rows / 2 && b->nrows <= h->sticky.rows * 2) {
+    if (decide && first_rows && h->opt.partition_sticky && h->part.sticky.valid && b->nrows >= h->part.sticky.rows / 2 && b->nrows <= h->part.sticky.rows * 2) {
         decide = false;  // as the last execution over a batch of this size went: no probe (see n1k_handle::sticky)
         partition = true;
-        groups_est = std::min<uint64_t>(b->nrows, h->sticky.groups_est * b->nrows / std::max<uint64_t>(h->sticky.rows, 1) + 1024);
+        groups_est = std::min<uint64_t>(b->nrows, h->part.sticky.groups_est * b->nrows / std::max<uint64_t>(h->part.sticky.rows, 1) + 1024);
     }
     if (decide) {
         // probe: Filter + group key of the first `head` rows into the table (keys only), counted before and after
         st = ensure_table(h, head);
         if (st != N1K_OK) return st;
         unsigned long long before = 0, after = 0;
-        HIP_TRY(h, hipMemcpyAsync(&before, h->d_counters.p + 1, sizeof before, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(&before, h->groups.counters.p + 1, sizeof before, hipMemcpyDeviceToHost, h->stream));
         const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)h->num_cus * 4, (head + 1023) / 1024));
-        HIP_TRY(h, launch_probe_keys(h->prog, head, h->table, h->d_errp, h->d_counters.p + 1, grid, h->stream));
-        HIP_TRY(h, hipMemcpyAsync(&after, h->d_counters.p + 1, sizeof after, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, launch_probe_keys(h->prog, head, h->groups.table, h->groups.errp, h->groups.counters.p + 1, grid, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(&after, h->groups.counters.p + 1, sizeof after, hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(h, hipStreamSynchronize(h->stream));
         const uint64_t fresh = after > before ? after - before : 0;
-        partition = fresh >= h->opt_partition_min_groups;
+        partition = fresh >= h->opt.partition_min_groups;
         // how many groups will the batch bring?  If the keys are draws from a universe of U values, m draws show
         // d = U (1 - e^(-m/U)) of them: solve for U from the probe (m = head rows, d = fresh groups) and evaluate at
         // the batch.  (All-distinct probes have no finite U: the row count stays the bound.)  Only the number of
@@ -697,11 +692,11 @@ n1k_status push_device(n1k_handle* h, const n1k_batch* b) {
             const double U = lo, nn = (double)b->nrows;
             groups_est = std::min<uint64_t>(groups_est, (uint64_t)(2.0 * U * (1.0 - std::exp(-nn / U))) + 1024);
         }
-        if (partition && first_rows && h->table.capacity) {
+        if (partition && first_rows && h->groups.table.capacity) {
             // the probe's keys are all the handle holds: drop them, so that the partitioned path's groups can stay in
             // their compact region (no table at all for this query)
-            HIP_TRY(h, launch_init_table(h->prog, h->table, 0, h->table.capacity, nullptr, h->stream));
-            HIP_TRY(h, hipMemsetAsync(h->d_counters.p + 1, 0, sizeof(unsigned long long), h->stream));
+            HIP_TRY(h, launch_init_table(h->prog, h->groups.table, 0, h->groups.table.capacity, nullptr, h->stream));
+            HIP_TRY(h, hipMemsetAsync(h->groups.counters.p + 1, 0, sizeof(unsigned long long), h->stream));
         }
     }
     if (b->nrows) {
@@ -709,39 +704,39 @@ n1k_status push_device(n1k_handle* h, const n1k_batch* b) {
         else if (partition) {
             bool done = false;
             st = run_group_records(h, &v, pp, groups_est, first_rows, &done);
-            h->sticky.valid = st == N1K_OK && done && first_rows && h->opt_agg_mode == N1K_MODE_AUTO;
-            h->sticky.rows = b->nrows;
-            h->sticky.groups_est = groups_est;
+            h->part.sticky.valid = st == N1K_OK && done && first_rows && h->opt.agg_mode == N1K_MODE_AUTO;
+            h->part.sticky.rows = b->nrows;
+            h->part.sticky.groups_est = groups_est;
             if (st == N1K_OK && !done) st = run_group_partitioned(h, &v, pp, groups_est, first_rows);
         } else
             st = run_group_batch(h, &v);
         if (st != N1K_OK) return st;
     }
     h->row_base += b->nrows;
-    h->stats.rows_in += b->nrows;
-    h->stats.batches += 1;
-    h->stats.bytes_scanned += b->nrows * batch_bytes_per_row(h);
+    h->timing.stats.rows_in += b->nrows;
+    h->timing.stats.batches += 1;
+    h->timing.stats.bytes_scanned += b->nrows * batch_bytes_per_row(h);
     return N1K_OK;
 }
 
 // host columns -> the handle's staging buffers on the device (the caller's memory is not retained after return: cgo rule)
 n1k_status stage_host_batch(n1k_handle* h, const n1k_batch* batch, std::vector<n1k_col>& dcols) {
     uint32_t nc = batch->ncols;
-    const int set = h->st_cur;
-    auto& s_tags = h->st_tags[set];
-    auto& s_payload = h->st_payload[set];
-    auto& s_codes = h->st_codes[set];
+    const int set = h->stage.cur;
+    auto& s_tags = h->stage.tags[set];
+    auto& s_payload = h->stage.payload[set];
+    auto& s_codes = h->stage.codes[set];
     s_tags.resize(std::max<size_t>(s_tags.size(), nc));
     s_payload.resize(std::max<size_t>(s_payload.size(), nc));
     s_codes.resize(std::max<size_t>(s_codes.size(), nc));
-    if (!h->copy_stream) {
-        HIP_TRY(h, hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
-        HIP_TRY(h, hipEventCreateWithFlags(&h->st_copied, hipEventDisableTiming));
-        for (int i = 0; i < 2; i++) HIP_TRY(h, hipEventCreateWithFlags(&h->st_free[i], hipEventDisableTiming));
+    if (!h->stage.copy_stream) {
+        HIP_TRY(h, hipStreamCreateWithFlags(&h->stage.copy_stream, hipStreamNonBlocking));
+        HIP_TRY(h, hipEventCreateWithFlags(&h->stage.copied, hipEventDisableTiming));
+        for (int i = 0; i < 2; i++) HIP_TRY(h, hipEventCreateWithFlags(&h->stage.free_ev[i], hipEventDisableTiming));
     }
     // the kernels of the batch before last may still read this set: the COPIES wait for them on the device, the host
     // does not (a buffer that has to grow is freed by hipFree, which waits for the device itself)
-    if (h->st_busy[set]) HIP_TRY(h, hipStreamWaitEvent(h->copy_stream, h->st_free[set], 0));
+    if (h->stage.busy[set]) HIP_TRY(h, hipStreamWaitEvent(h->stage.copy_stream, h->stage.free_ev[set], 0));
     dcols.assign(nc, n1k_col{});
     uint64_t n = batch->nrows;
     for (uint32_t c = 0; c < nc; c++) {
@@ -749,32 +744,32 @@ n1k_status stage_host_batch(n1k_handle* h, const n1k_batch* batch, std::vector<n
         dcols[c] = col;
         if (col.kind == N1K_COL_DICT32) {
             HIP_TRY(h, s_codes[c].ensure(n));
-            if (n) HIP_TRY(h, hipMemcpyAsync(s_codes[c].p, col.codes, n * 4, hipMemcpyHostToDevice, h->copy_stream));
+            if (n) HIP_TRY(h, hipMemcpyAsync(s_codes[c].p, col.codes, n * 4, hipMemcpyHostToDevice, h->stage.copy_stream));
             dcols[c].codes = s_codes[c].p;
         } else {
             HIP_TRY(h, s_tags[c].ensure(n));
             HIP_TRY(h, s_payload[c].ensure(n));
             if (n) {
-                HIP_TRY(h, hipMemcpyAsync(s_tags[c].p, col.tags, n, hipMemcpyHostToDevice, h->copy_stream));
-                HIP_TRY(h, hipMemcpyAsync(s_payload[c].p, col.payload, n * 8, hipMemcpyHostToDevice, h->copy_stream));
+                HIP_TRY(h, hipMemcpyAsync(s_tags[c].p, col.tags, n, hipMemcpyHostToDevice, h->stage.copy_stream));
+                HIP_TRY(h, hipMemcpyAsync(s_payload[c].p, col.payload, n * 8, hipMemcpyHostToDevice, h->stage.copy_stream));
             }
             dcols[c].tags = s_tags[c].p;
             dcols[c].payload = s_payload[c].p;
         }
     }
     // the caller's memory is not retained after return (cgo rule): wait for the copies — not for the compute stream
-    HIP_TRY(h, hipEventRecord(h->st_copied, h->copy_stream));
-    HIP_TRY(h, hipStreamWaitEvent(h->stream, h->st_copied, 0));
-    HIP_TRY(h, hipEventSynchronize(h->st_copied));
+    HIP_TRY(h, hipEventRecord(h->stage.copied, h->stage.copy_stream));
+    HIP_TRY(h, hipStreamWaitEvent(h->stream, h->stage.copied, 0));
+    HIP_TRY(h, hipEventSynchronize(h->stage.copied));
     return N1K_OK;
 }
 
 // behind the kernels of a staged batch: its set may be overwritten once this event has passed
 n1k_status staged_batch_issued(n1k_handle* h) {
-    const int set = h->st_cur;
-    HIP_TRY(h, hipEventRecord(h->st_free[set], h->stream));
-    h->st_busy[set] = true;
-    h->st_cur ^= 1;
+    const int set = h->stage.cur;
+    HIP_TRY(h, hipEventRecord(h->stage.free_ev[set], h->stream));
+    h->stage.busy[set] = true;
+    h->stage.cur ^= 1;
     return N1K_OK;
 }
 

@@ -38,7 +38,7 @@ static bool group_path_index(const n1k_handle* h, const std::string& p, int& out
 // operator and are evaluated on the device by the same element-wise kernel as the arithmetic of WHERE / GROUP BY.
 n1k_status build_projection(n1k_handle* h) {
     auto* f = new n1k_handle();
-    h->project = f;
+    h->tail.project = f;
     std::vector<std::unique_ptr<Expr>> trees;
     PlanError err;
     for (const ProjectTerm& t : h->plan.project) {
@@ -64,7 +64,7 @@ n1k_status build_projection(n1k_handle* h) {
             g_create_error = "a projection term refers to " + p + ", which is neither a group key nor an aggregate of the plan";
             return N1K_UNSUPPORTED;
         }
-        h->project_cols.push_back(idx);
+        h->tail.project_cols.push_back(idx);
     }
     if (f->plan.paths.size() > (size_t)kMaxCols) {
         g_create_error = "projection over more than 16 keys / aggregates";
@@ -80,7 +80,7 @@ n1k_status build_projection(n1k_handle* h) {
             g_create_error = "a string constant as a projection term does not run on the device";
             return N1K_UNSUPPORTED;
         }
-        h->project_ops.push_back(o);
+        h->tail.project_ops.push_back(o);
     }
     for (const auto& d : f->derived)
         if (d.op >= AR_GREATEST) {  // (the inner operator sees this handle's dictionary codes, not its own: no string ranks there)
@@ -163,21 +163,21 @@ static int host_collate(const n1k_handle* h, const n1k_value& a, const n1k_value
 // aggregates are read from the "aggregates" attachment, algebra/aggregate.go:97-118): the final groups become a batch
 // of the inner Filter-only operator — one column per key / aggregate its condition names — and its survivors stay.
 n1k_status having_groups(n1k_handle* h, uint64_t& ng) {
-    n1k_handle* f = h->having;
-    const size_t nk = h->plan.keys.size(), na = h->plan.aggs.size(), nc = h->having_cols.size();
+    n1k_handle* f = h->tail.having;
+    const size_t nk = h->plan.keys.size(), na = h->plan.aggs.size(), nc = h->tail.having_cols.size();
     if (ng == 0) return N1K_OK;
     if (f->device < 0 && !f->device_ready) f->device = h->device;
     std::vector<std::vector<uint8_t>> tags(nc, std::vector<uint8_t>((size_t)ng));
     std::vector<std::vector<uint64_t>> pay(nc, std::vector<uint64_t>((size_t)ng));
-    h->having_codes.resize(h->dict.size(), 0xFFFFFFFFu);
+    h->tail.having_codes.resize(h->dict.size(), 0xFFFFFFFFu);
     for (size_t c = 0; c < nc; c++) {
-        const int src = h->having_cols[c];
+        const int src = h->tail.having_cols[c];
         for (uint64_t g = 0; g < ng; g++) {
-            const n1k_value& v = src >= 0 ? h->r_keys[g * nk + (size_t)src] : h->r_aggs[g * na + (size_t)(-src - 1)];
+            const n1k_value& v = src >= 0 ? h->res.keys[g * nk + (size_t)src] : h->res.aggs[g * na + (size_t)(-src - 1)];
             tags[c][g] = v.tag;
             uint64_t p = v.v.code;
             if (v.tag >= N1K_T_STRING) {  // the inner operator has its own dictionary
-                uint32_t& m = h->having_codes[(size_t)p];
+                uint32_t& m = h->tail.having_codes[(size_t)p];
                 if (m == 0xFFFFFFFFu) m = intern(f, h->dict[(size_t)p]);
                 p = m;
             }
@@ -201,21 +201,21 @@ n1k_status having_groups(n1k_handle* h, uint64_t& ng) {
     if (st != N1K_OK) return fail(h, st, "HAVING: %s", n1k_last_error(f));
     const uint64_t keep = res.nselected;
     std::vector<n1k_value> keys(keep * nk), aggs(keep * na);
-    std::vector<n1k_partial> parts(h->r_parts.empty() ? 0 : keep * na);
+    std::vector<n1k_partial> parts(h->res.parts.empty() ? 0 : keep * na);
     std::vector<uint64_t> rep(keep);
     for (uint64_t i = 0; i < keep; i++) {
         const uint64_t g = res.selected[i];
-        for (size_t k = 0; k < nk; k++) keys[i * nk + k] = h->r_keys[g * nk + k];
+        for (size_t k = 0; k < nk; k++) keys[i * nk + k] = h->res.keys[g * nk + k];
         for (size_t a = 0; a < na; a++) {
-            aggs[i * na + a] = h->r_aggs[g * na + a];
-            if (!parts.empty()) parts[i * na + a] = h->r_parts[g * na + a];
+            aggs[i * na + a] = h->res.aggs[g * na + a];
+            if (!parts.empty()) parts[i * na + a] = h->res.parts[g * na + a];
         }
-        rep[i] = g < h->r_rep.size() ? h->r_rep[g] : ~0ull;
+        rep[i] = g < h->res.rep.size() ? h->res.rep[g] : ~0ull;
     }
-    h->r_keys.swap(keys);
-    h->r_aggs.swap(aggs);
-    h->r_parts.swap(parts);
-    h->r_rep.swap(rep);
+    h->res.keys.swap(keys);
+    h->res.aggs.swap(aggs);
+    h->res.parts.swap(parts);
+    h->res.rep.swap(rep);
     ng = keep;
     return N1K_OK;
 }
@@ -224,13 +224,13 @@ n1k_status having_groups(n1k_handle* h, uint64_t& ng) {
 // group.  Terms that are a key, an aggregate or a constant are copied; the others were compiled into derived columns of
 // the inner operator and are evaluated on the device over the groups as one column batch.
 n1k_status project_groups(n1k_handle* h, uint64_t ng) {
-    n1k_handle* f = h->project;
-    const size_t nk = h->plan.keys.size(), na = h->plan.aggs.size(), nc = h->project_cols.size(), nt = h->project_ops.size();
-    h->r_proj.assign((size_t)ng * nt, n1k_value{});
+    n1k_handle* f = h->tail.project;
+    const size_t nk = h->plan.keys.size(), na = h->plan.aggs.size(), nc = h->tail.project_cols.size(), nt = h->tail.project_ops.size();
+    h->tail.r_proj.assign((size_t)ng * nt, n1k_value{});
     if (ng == 0 || nt == 0) return N1K_OK;
     auto source = [&](size_t c, uint64_t g) -> const n1k_value& {
-        const int src = h->project_cols[c];
-        return src >= 0 ? h->r_keys[g * nk + (size_t)src] : h->r_aggs[g * na + (size_t)(-src - 1)];
+        const int src = h->tail.project_cols[c];
+        return src >= 0 ? h->res.keys[g * nk + (size_t)src] : h->res.aggs[g * na + (size_t)(-src - 1)];
     };
     std::vector<std::vector<uint8_t>> dt(f->derived.size());
     std::vector<std::vector<uint64_t>> dp(f->derived.size());
@@ -273,9 +273,9 @@ n1k_status project_groups(n1k_handle* h, uint64_t ng) {
         HIP_TRY(h, hipStreamSynchronize(f->stream));
     }
     for (size_t t = 0; t < nt; t++) {
-        const Operand& o = h->project_ops[t];
+        const Operand& o = h->tail.project_ops[t];
         for (uint64_t g = 0; g < ng; g++) {
-            n1k_value& v = h->r_proj[g * nt + t];
+            n1k_value& v = h->tail.r_proj[g * nt + t];
             if (o.is_const) {
                 v.tag = (uint8_t)o.ctag;
                 v.v.code = o.cpayload;
@@ -295,17 +295,17 @@ n1k_status project_groups(n1k_handle* h, uint64_t ng) {
 // among rows that tie on every term is unspecified in the reference too; here ties keep table order.
 n1k_status order_groups(n1k_handle* h, uint64_t& ng) {
     const ParsedPlan& pl = h->plan;
-    const size_t nk = pl.keys.size(), na = pl.aggs.size(), np = h->r_proj.empty() ? 0 : h->project_ops.size();
+    const size_t nk = pl.keys.size(), na = pl.aggs.size(), np = h->tail.r_proj.empty() ? 0 : h->tail.project_ops.size();
     std::vector<uint32_t> perm((size_t)ng);
     for (size_t i = 0; i < perm.size(); i++) perm[i] = (uint32_t)i;
     bool unsupported = false;
     if (pl.has_order) {
         auto less = [&](uint32_t x, uint32_t y) {
             for (const OrderTerm& t : pl.order) {
-                const n1k_value& a = t.proj_index >= 0 ? h->r_proj[x * np + t.proj_index]
-                                     : t.key_index >= 0 ? h->r_keys[x * nk + t.key_index] : h->r_aggs[x * na + t.agg_index];
-                const n1k_value& b = t.proj_index >= 0 ? h->r_proj[y * np + t.proj_index]
-                                     : t.key_index >= 0 ? h->r_keys[y * nk + t.key_index] : h->r_aggs[y * na + t.agg_index];
+                const n1k_value& a = t.proj_index >= 0 ? h->tail.r_proj[x * np + t.proj_index]
+                                     : t.key_index >= 0 ? h->res.keys[x * nk + t.key_index] : h->res.aggs[x * na + t.agg_index];
+                const n1k_value& b = t.proj_index >= 0 ? h->tail.r_proj[y * np + t.proj_index]
+                                     : t.key_index >= 0 ? h->res.keys[y * nk + t.key_index] : h->res.aggs[y * na + t.agg_index];
                 const int c = host_collate(h, a, b, &unsupported);
                 if (c) return t.desc ? c > 0 : c < 0;
             }
@@ -326,19 +326,19 @@ n1k_status order_groups(n1k_handle* h, uint64_t& ng) {
     std::vector<n1k_value> proj((last - first) * np);
     for (uint64_t i = first; i < last; i++) {
         const uint32_t g = perm[i];
-        for (size_t t = 0; t < np; t++) proj[(i - first) * np + t] = h->r_proj[g * np + t];
-        for (size_t k = 0; k < nk; k++) keys[(i - first) * nk + k] = h->r_keys[g * nk + k];
+        for (size_t t = 0; t < np; t++) proj[(i - first) * np + t] = h->tail.r_proj[g * np + t];
+        for (size_t k = 0; k < nk; k++) keys[(i - first) * nk + k] = h->res.keys[g * nk + k];
         for (size_t a = 0; a < na; a++) {
-            aggs[(i - first) * na + a] = h->r_aggs[g * na + a];
-            if (!h->r_parts.empty()) parts[(i - first) * na + a] = h->r_parts[g * na + a];
+            aggs[(i - first) * na + a] = h->res.aggs[g * na + a];
+            if (!h->res.parts.empty()) parts[(i - first) * na + a] = h->res.parts[g * na + a];
         }
-        rep[i - first] = g < h->r_rep.size() ? h->r_rep[g] : ~0ull;
+        rep[i - first] = g < h->res.rep.size() ? h->res.rep[g] : ~0ull;
     }
-    h->r_keys.swap(keys);
-    h->r_aggs.swap(aggs);
-    h->r_parts.swap(parts);
-    h->r_rep.swap(rep);
-    if (np) h->r_proj.swap(proj);
+    h->res.keys.swap(keys);
+    h->res.aggs.swap(aggs);
+    h->res.parts.swap(parts);
+    h->res.rep.swap(rep);
+    if (np) h->tail.r_proj.swap(proj);
     ng = last - first;
     return N1K_OK;
 }
@@ -352,17 +352,17 @@ n1k_status array_agg_groups(n1k_handle* h, uint64_t ng, const unsigned long long
     const size_t na = h->plan.aggs.size();
     std::unordered_map<uint64_t, uint64_t> group_of;
     group_of.reserve((size_t)ng * 2);
-    for (uint64_t g = 0; g < ng; g++) group_of.emplace(h->r_rep[g], g);
+    for (uint64_t g = 0; g < ng; g++) group_of.emplace(h->res.rep[g], g);
     for (size_t a = 0; a < na; a++) {
         const AggSpec& ag = h->prog.aggs[a];
         if (ag.kind != AGG_ARRAY) continue;
-        const uint64_t n = std::min<uint64_t>(counters[8 + ag.log_index], h->log_capacity);
+        const uint64_t n = std::min<uint64_t>(counters[8 + ag.log_index], h->distinct.log_capacity);
         std::vector<uint64_t> keys((size_t)n), vals((size_t)n);
         std::vector<uint8_t> tags((size_t)n);
         if (n) {
-            HIP_TRY(h, hipMemcpyAsync(keys.data(), h->d_log_key[ag.log_index].p, n * 8, hipMemcpyDeviceToHost, h->stream));
-            HIP_TRY(h, hipMemcpyAsync(vals.data(), h->d_log_val[ag.log_index].p, n * 8, hipMemcpyDeviceToHost, h->stream));
-            HIP_TRY(h, hipMemcpyAsync(tags.data(), h->d_log_cls[ag.log_index].p, n, hipMemcpyDeviceToHost, h->stream));
+            HIP_TRY(h, hipMemcpyAsync(keys.data(), h->distinct.log_key[ag.log_index].p, n * 8, hipMemcpyDeviceToHost, h->stream));
+            HIP_TRY(h, hipMemcpyAsync(vals.data(), h->distinct.log_val[ag.log_index].p, n * 8, hipMemcpyDeviceToHost, h->stream));
+            HIP_TRY(h, hipMemcpyAsync(tags.data(), h->distinct.log_cls[ag.log_index].p, n, hipMemcpyDeviceToHost, h->stream));
             HIP_TRY(h, hipStreamSynchronize(h->stream));
         }
         std::vector<std::vector<n1k_value>> members((size_t)ng);
@@ -378,7 +378,7 @@ n1k_status array_agg_groups(n1k_handle* h, uint64_t ng, const unsigned long long
         std::string text;
         for (uint64_t g = 0; g < ng; g++) {
             auto& m = members[(size_t)g];
-            n1k_value& out = h->r_aggs[g * na + a];
+            n1k_value& out = h->res.aggs[g * na + a];
             memset(&out, 0, sizeof out);
             out.tag = N1K_T_NULL;  // Default(): NULL (agg_array.go:77); an empty DISTINCT set is NULL too
             if (m.empty()) continue;
@@ -405,7 +405,7 @@ n1k_status array_agg_groups(n1k_handle* h, uint64_t ng, const unsigned long long
         }
         if (unsupported) return fail(h, N1K_UNSUPPORTED_DATA, "array_agg over values whose collation is outside the subset");
     }
-    for (uint64_t g = 0; g < ng; g++) h->r_rep[g] = ~0ull;  // (the slot carried the packed keys)
+    for (uint64_t g = 0; g < ng; g++) h->res.rep[g] = ~0ull;  // (the slot carried the packed keys)
     return N1K_OK;
 }
 
@@ -425,23 +425,23 @@ n1k_status n1k_order_rows(n1k_handle* h, uint64_t ngroups, const n1k_value* keys
         const n1k_value& v = i < ngroups * nk ? keys[i] : aggs[i - ngroups * nk];
         if (v.tag >= N1K_T_STRING && v.v.code >= h->dict.size()) return fail(h, N1K_INVALID, "a value's dictionary code is unknown to this handle");
     }
-    h->r_keys.assign(keys, keys + ngroups * nk);
-    h->r_aggs.assign(aggs, aggs + ngroups * na);
-    h->r_parts.clear();
-    h->r_rep.assign((size_t)ngroups, ~0ull);
-    h->r_proj.clear();
+    h->res.keys.assign(keys, keys + ngroups * nk);
+    h->res.aggs.assign(aggs, aggs + ngroups * na);
+    h->res.parts.clear();
+    h->res.rep.assign((size_t)ngroups, ~0ull);
+    h->tail.r_proj.clear();
     uint64_t ng = ngroups;
     n1k_status st = h->plan.has_project ? project_groups(h, ng) : N1K_OK;  // (sort terms may name projection aliases)
     if (st != N1K_OK) return st;
     st = order_groups(h, ng);
     if (st != N1K_OK) return st;
-    out->nproj = h->plan.has_project ? (uint32_t)h->project_ops.size() : 0;
-    out->proj = out->nproj ? h->r_proj.data() : nullptr;
+    out->nproj = h->plan.has_project ? (uint32_t)h->tail.project_ops.size() : 0;
+    out->proj = out->nproj ? h->tail.r_proj.data() : nullptr;
     out->ngroups = ng;
-    out->keys = h->r_keys.data();
-    out->aggs = h->r_aggs.data();
+    out->keys = h->res.keys.data();
+    out->aggs = h->res.aggs.data();
     out->partials = nullptr;
-    out->rep_row = h->r_rep.data();
+    out->rep_row = h->res.rep.data();
     return N1K_OK;
     });
 }
