@@ -309,6 +309,46 @@ n1k_status n1k_push_device_batch(n1k_handle *h, const n1k_batch *batch);
  * statement executed again over the same resident columns does).  Same results and errors as the three calls. */
 n1k_status n1k_run_device_batch(n1k_handle *h, const n1k_batch *batch, n1k_result *out);
 
+/* ------------------------------------------- Filter-only plans on the device -- */
+
+/*
+ * The answer of a Filter-only plan that stays on the device: what lets the Filter feed the next operator (a projection,
+ * n1k_push_device_batch of a group handle, an exchange) without its ordinals crossing to the host and back.  The three-call
+ * path and n1k_run_device_batch keep returning 64-bit host ordinals in n1k_result.selected.
+ */
+typedef struct n1k_selection {
+    uint64_t nselected;     /* rows whose condition is TRUE */
+    const uint32_t *rows;   /* DEVICE pointer: their ordinals inside the batch, ascending; owned by the handle,
+                               valid until the next n1k_filter_device_batch / n1k_reset / n1k_destroy; NULL when 0 */
+} n1k_selection;
+
+/*
+ * One whole execution of a Filter-only plan over a device-resident batch (≙ reopen() + processItem()* of a Filter,
+ * execution/filter.go:49-61 — the counterpart of n1k_run_device_batch): one launch and one wait, which brings back the
+ * survivor count and the error flags only; no ordinal leaves the device.  Ordinals are local to the batch (its first row
+ * is 0), so batch->nrows must be below 2^32.  N1K_INVALID: a NULL argument, a plan that has a group, 2^32 rows or more, a
+ * batch that does not validate (all checked before a device is touched); N1K_STOPPED: n1k_stop was observed;
+ * N1K_UNSUPPORTED_DATA: as n1k_finish reports it.  Afterwards n1k_get_stats describes this call (rows_in, rows_selected,
+ * batches, device_ms, query_ms, spec_kernel); the handle is otherwise as after n1k_reset: a following n1k_finish returns an
+ * empty selection.  One batch per selection.
+ */
+n1k_status n1k_filter_device_batch(n1k_handle *h, const n1k_batch *batch, n1k_selection *out);
+
+/* The last selection's ordinals to the caller's host buffer (pinned or not) of `capacity` entries: 4 bytes per survivor of
+ * execution/filter.go:49-61, one copy, one wait.  N1K_INVALID: no selection, or capacity below nselected. */
+n1k_status n1k_selected_to_host32(n1k_handle *h, uint32_t *out, uint64_t capacity);
+
+/*
+ * The survivors' rows of any device-resident batch (the items a Filter sends on, execution/filter.go:49-61, column-wise):
+ * for i below nselected, row i of out_cols[c] becomes row rows[i] of src->cols[c].  `src` holds 1 to 16 columns of either
+ * kind — not necessarily the plan's: `asin` and `title` for a plan that filters on `type` — and as many rows as the
+ * filtered batch; out_cols[c] has the kind of src->cols[c] and points to device memory with room for capacity_rows rows.
+ * Exactly nselected rows of every output array are written, nothing else; no pointer needs any alignment.  Asynchronous on
+ * the handle's stream: n1k_sync waits for it.  N1K_INVALID: no selection, a NULL array, more than 16 columns, kinds or row
+ * counts that do not match, capacity_rows below nselected.
+ */
+n1k_status n1k_gather_selected(n1k_handle *h, const n1k_batch *src, uint64_t capacity_rows, const n1k_col *out_cols);
+
 /* Wait for all queued device work of the handle. */
 n1k_status n1k_sync(n1k_handle *h);
 

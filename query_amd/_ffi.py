@@ -64,6 +64,10 @@ class Stats(C.Structure):
                 ("topk_candidates", C.c_uint64), ("json_device_docs", C.c_uint64), ("query_ms", C.c_double)]
 
 
+class Selection(C.Structure):
+    _fields_ = [("nselected", C.c_uint64), ("rows", C.c_void_p)]  # rows: a DEVICE address
+
+
 class SynthSpec(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("first_row", C.c_uint64), ("nrows", C.c_uint64), ("total_rows", C.c_uint64),
                 ("k_cat", C.c_uint32), ("zipf", C.c_uint32), ("cat_cdf", C.c_void_p)]
@@ -87,6 +91,7 @@ SYMBOLS = [
     "n1k_in_match", "n1k_in_match_device", "n1k_in_stats",
     "n1k_strfn_eval", "n1k_strfn_eval_device", "n1k_strfn_stats",
     "n1k_device_bytes_live",
+    "n1k_filter_device_batch", "n1k_selected_to_host32", "n1k_gather_selected",
 ]
 
 _lib = None
@@ -257,6 +262,13 @@ def lib():
     if hasattr(L, "n1k_device_bytes_live"):  # (idem)
         L.n1k_device_bytes_live.restype = C.c_uint64
         L.n1k_device_bytes_live.argtypes = []
+    if hasattr(L, "n1k_filter_device_batch"):  # (idem)
+        L.n1k_filter_device_batch.restype = C.c_int
+        L.n1k_filter_device_batch.argtypes = [H, C.POINTER(Batch), C.POINTER(Selection)]
+        L.n1k_selected_to_host32.restype = C.c_int
+        L.n1k_selected_to_host32.argtypes = [H, C.c_void_p, C.c_uint64]
+        L.n1k_gather_selected.restype = C.c_int
+        L.n1k_gather_selected.argtypes = [H, C.POINTER(Batch), C.c_uint64, C.POINTER(Col)]
     L.n1k_abi_version.restype = C.c_int
     L.n1k_device_count.restype = C.c_int
     _lib = L

@@ -594,6 +594,52 @@ void default_value(const AggDef& d, n1k_value& v, n1k_partial& p) {
         v.tag = N1K_T_NULL;
 }
 
+// n1k_reset; n1k_filter_device_batch runs it with clear_stop false (a stop that came before the call is the call's answer)
+n1k_status reset_handle(n1k_handle* h, bool clear_stop) {
+    if (clear_stop) h->stop_flag.store(0);
+    h->failure_global = false;
+    h->row_base = 0;
+    h->groups.merged_bound = 0;
+    h->filter.selected.clear();
+    h->filter.has_sel32 = false;
+    h->res.keys.clear();
+    h->res.aggs.clear();
+    h->res.parts.clear();
+    h->res.rep.clear();
+    memset(&h->timing.stats, 0, sizeof h->timing.stats);
+    if (h->device_ready) {
+        HIP_TRY(h, hipSetDevice(h->device));
+        if (!h->timing.events.empty()) {  // pushes that were never finished: their events must complete before reuse
+            HIP_TRY(h, hipStreamSynchronize(h->stream));
+            drain_events(h);
+        }
+        h->timing.stats.device_ms = 0;
+        h->part.groups_seen = 0;
+        h->res.out_count_dirty = false;
+        h->part.pending.count = 0;
+        if (!h->timing.ev_q0) {
+            (void)hipEventCreate(&h->timing.ev_q0);
+            (void)hipEventCreate(&h->timing.ev_q1);
+        }
+        h->timing.q1_recorded = false;
+        h->timing.q0_recorded = h->timing.ev_q0 && hipEventRecord(h->timing.ev_q0, h->stream) == hipSuccess;  // the query starts here (stats.query_ms)
+        if (h->device_clean) return N1K_OK;  // the last query's final kernel left the device as the launches below would
+        h->device_clean = true;
+        // one launch, no host synchronisation: table back to empty and all counters / error flags to zero
+        if (h->groups.table.capacity) HIP_TRY(h, launch_init_table(h->prog, h->groups.table, 0, h->groups.table.capacity, h->groups.counters.p, h->stream));
+        else HIP_TRY(h, hipMemsetAsync(h->groups.counters.p, 0, kCounters * sizeof(unsigned long long), h->stream));
+        if (h->distinct.word_hist.p) HIP_TRY(h, hipMemsetAsync(h->distinct.word_hist.p, 0, kMaxDistinct * 256 * sizeof(unsigned long long), h->stream));
+        if (h->distinct.wcursor.p) HIP_TRY(h, hipMemsetAsync(h->distinct.wcursor.p, 0, kMaxDistinct * kWordSubs * kCursorStride * sizeof(unsigned long long), h->stream));
+        h->distinct.wregion_used = false;
+        if (h->prog.wide_int) {
+            const size_t n = (size_t)1 << h->prog.wide_bits;
+            HIP_TRY(h, hipMemsetAsync(h->groups.wide_int.p, 0xFF, n * 8, h->stream));
+            HIP_TRY(h, hipMemsetAsync(h->groups.wide_flt.p, 0xFF, n * 8, h->stream));
+        }
+    }
+    return N1K_OK;
+}
+
 }  // namespace n1k_eng
 
 // ================================================================== C ABI
@@ -727,47 +773,7 @@ static void destroy_handle(n1k_handle* h) {
 n1k_status n1k_reset(n1k_handle* h) {
     return guarded(h, [&]() -> n1k_status {
     if (!h) return N1K_INVALID;
-    h->stop_flag.store(0);
-    h->failure_global = false;
-    h->row_base = 0;
-    h->groups.merged_bound = 0;
-    h->filter.selected.clear();
-    h->res.keys.clear();
-    h->res.aggs.clear();
-    h->res.parts.clear();
-    h->res.rep.clear();
-    memset(&h->timing.stats, 0, sizeof h->timing.stats);
-    if (h->device_ready) {
-        HIP_TRY(h, hipSetDevice(h->device));
-        if (!h->timing.events.empty()) {  // pushes that were never finished: their events must complete before reuse
-            HIP_TRY(h, hipStreamSynchronize(h->stream));
-            drain_events(h);
-        }
-        h->timing.stats.device_ms = 0;
-        h->part.groups_seen = 0;
-        h->res.out_count_dirty = false;
-        h->part.pending.count = 0;
-        if (!h->timing.ev_q0) {
-            (void)hipEventCreate(&h->timing.ev_q0);
-            (void)hipEventCreate(&h->timing.ev_q1);
-        }
-        h->timing.q1_recorded = false;
-        h->timing.q0_recorded = h->timing.ev_q0 && hipEventRecord(h->timing.ev_q0, h->stream) == hipSuccess;  // the query starts here (stats.query_ms)
-        if (h->device_clean) return N1K_OK;  // the last query's final kernel left the device as the launches below would
-        h->device_clean = true;
-        // one launch, no host synchronisation: table back to empty and all counters / error flags to zero
-        if (h->groups.table.capacity) HIP_TRY(h, launch_init_table(h->prog, h->groups.table, 0, h->groups.table.capacity, h->groups.counters.p, h->stream));
-        else HIP_TRY(h, hipMemsetAsync(h->groups.counters.p, 0, kCounters * sizeof(unsigned long long), h->stream));
-        if (h->distinct.word_hist.p) HIP_TRY(h, hipMemsetAsync(h->distinct.word_hist.p, 0, kMaxDistinct * 256 * sizeof(unsigned long long), h->stream));
-        if (h->distinct.wcursor.p) HIP_TRY(h, hipMemsetAsync(h->distinct.wcursor.p, 0, kMaxDistinct * kWordSubs * kCursorStride * sizeof(unsigned long long), h->stream));
-        h->distinct.wregion_used = false;
-        if (h->prog.wide_int) {
-            const size_t n = (size_t)1 << h->prog.wide_bits;
-            HIP_TRY(h, hipMemsetAsync(h->groups.wide_int.p, 0xFF, n * 8, h->stream));
-            HIP_TRY(h, hipMemsetAsync(h->groups.wide_flt.p, 0xFF, n * 8, h->stream));
-        }
-    }
-    return N1K_OK;
+    return reset_handle(h, true);
     });
 }
 

@@ -193,6 +193,7 @@ uint32_t lookup_code(const n1k_handle* h, const char* s);
 bool to_operand(n1k_handle* h, const Expr* e, Operand& o, PlanError& err);
 bool compile_plan(n1k_handle* h, PlanError& err);
 n1k_status ensure_device(n1k_handle* h);
+n1k_status reset_handle(n1k_handle* h, bool clear_stop);  // n1k_reset (clear_stop: and forget an earlier n1k_stop, as reopen() does)
 n1k_status ensure_rank(n1k_handle* h);
 n1k_status fix_layout(n1k_handle* h, const n1k_batch* b);
 n1k_status ensure_table(n1k_handle* h, uint64_t incoming_rows);
@@ -254,10 +255,17 @@ struct Staging {
     int cur = 0;
 };
 // The Filter-only path: run_filter_batch fills them, n1k_finish reads `selected`.
+// n1k_filter_device_batch (n1k_select.cpp) leaves its selection in `sel32` instead: 32-bit batch-local ordinals that stay on the
+// device, for n1k_selected_to_host32 and n1k_gather_selected.  Both paths use tile_off, one after the other on the stream.
 struct FilterOnly {
     DevBuf<uint64_t> tile_off, sel;
     std::vector<uint64_t> selected;
+    DevBuf<uint32_t> sel32;
+    bool has_sel32 = false;               // a selection exists: until the next n1k_filter_device_batch / n1k_reset
+    uint64_t sel32_count = 0, sel32_rows = 0;  // its survivors; the rows of the batch it was taken from
 };
+bool filter_stream_fast(const n1k_handle* h);  // the condition and the bound columns take filter_stream_kernel's FAST variant
+uint32_t filter_stream_grid(const n1k_handle* h, uint64_t ntiles, bool fast);
 bool build_fast_args(n1k_handle* h, uint32_t max_slots, FastArgs& F, bool fuse = false, bool partition_only = false);
 SpecSig make_plan_sig(const n1k_handle* h, const FastArgs& F);
 const SpecEntry* find_spec(const SpecSig& g);

@@ -131,6 +131,29 @@ hipError_t launch_finalize_small(const Program& P, const GlobalTable& G, OutValu
 hipError_t launch_filter_stream(const Program& P, uint64_t nrows, uint64_t row_base, uint64_t* out_rows, unsigned long long* tile_state,
                                 unsigned long long* tile_counter, unsigned long long* total, uint32_t* err_flags, uint32_t grid,
                                 hipStream_t st, bool fast = false);  // fast: ONE TERM_NUM_* comparison of a TAGGED64 column, wide loads
+// ... with 32-bit batch-local ordinals (the first row of the batch is 0; nrows < 2^32): the selection that stays on the device
+hipError_t launch_filter_stream(const Program& P, uint64_t nrows, uint32_t* out_rows, unsigned long long* tile_state,
+                                unsigned long long* tile_counter, unsigned long long* total, uint32_t* err_flags, uint32_t grid,
+                                hipStream_t st, bool fast);
+// The rows a selection names, of up to kGatherMaxCols columns of either kind, in one launch: row i of dst = row rows[i] of src,
+// i < n (n < 2^32; `rows` 16-byte aligned; no requirement on any column pointer)
+constexpr uint32_t kGatherMaxCols = 16;
+struct GatherCol {
+    uint32_t kind, pad;  // COLK_*
+    const uint8_t* src_tags;
+    const uint64_t* src_payload;
+    const uint32_t* src_codes;
+    uint8_t* dst_tags;
+    uint64_t* dst_payload;
+    uint32_t* dst_codes;
+};
+struct GatherArgs {
+    const uint32_t* rows;
+    uint64_t n;
+    uint32_t ncols, pad;
+    GatherCol cols[kGatherMaxCols];
+};
+hipError_t launch_gather_rows(const GatherArgs& A, hipStream_t st);
 // ---- raw JSON documents -> leaf columns on the device (n1k_jsondev.hip)
 constexpr uint32_t kJsonMaxSteps = 4;  // field names of a leaf path below the keyspace alias
 struct JsonDevPath {

@@ -8,6 +8,7 @@
 //                       execution/group_intermediate.go:56-104 + CumulateIntermediate).
 //   finalize_kernel     K5: FinalGroup (execution/group_final.go:55-98 + ComputeFinal).
 //   filter_stream_kernel  Filter alone (execution/filter.go:49-61): predicate and ordered compaction in one pass.
+//   gather_rows_kernel    the survivors' rows of any resident columns, by the 32-bit selection that stayed on the device.
 //
 // All of it is HBM-bound integer/byte work (no MFMA): wave64, coalesced column loads, LDS atomics,
 // scalar (wave-uniform) interpretation of the plan program.
@@ -2662,7 +2663,7 @@ __global__ void topk_compact_kernel(const uint32_t* cand, uint64_t ncand, uint32
 //     tiles 0..t (inclusive prefix).  The word is the whole message — relaxed agent-scope store / load, nothing to order;
 //   * wave 0 looks back 64 tiles at a time: it adds aggregates until it meets an inclusive prefix;
 //   * survivors leave in row order: lane-private ranks from ballots, per-(j, wave) counts in LDS.
-// Algorithmic traffic: the predicate's columns once + 8 B per survivor.
+// Algorithmic traffic: the predicate's columns once + 8 B per survivor (4 B in the 32-bit form, ORD below).
 constexpr unsigned long long kTileAgg = 1ull << 62, kTilePrefix = 2ull << 62, kTileValue = (1ull << 62) - 1ull;
 
 // Tried and measured (100 M rows, 0.38 ms as it stands): all of a tile's loads issued at once — 179 registers, two workgroups
@@ -2699,8 +2700,10 @@ N1K_DEV bool num_term_true(uint32_t op, uint32_t tg, uint64_t p, uint32_t ct, ui
            : (c == 0 && (tg == T_INT || tg == T_FLOAT));
 }
 
-template <int R, int BLOCK, int SUB, bool FAST>
-__global__ __launch_bounds__(BLOCK) void filter_stream_kernel(const Program P, uint64_t nrows, uint64_t row_base, uint64_t* out_rows,
+// ORD: the ordinals' type — uint64_t for the host landing (global ordinals: row_base + row), uint32_t for the selection that stays
+// on the device (n1k_filter_device_batch: batch-local, row_base 0, fewer than 2^32 rows): half the bytes written, nothing else differs.
+template <typename ORD, int R, int BLOCK, int SUB, bool FAST>
+__global__ __launch_bounds__(BLOCK) void filter_stream_kernel(const Program P, uint64_t nrows, uint64_t row_base, ORD* out_rows,
                                                              unsigned long long* tile_state, unsigned long long* tile_counter,
                                                              unsigned long long* total, uint32_t* err_flags, const FilterFast F) {
     constexpr int NW = BLOCK / 64;
@@ -2813,13 +2816,13 @@ __global__ __launch_bounds__(BLOCK) void filter_stream_kernel(const Program P, u
                     const unsigned long long m0 = __ballot(p0), m1 = __ballot(p1);
                     const uint64_t r0 = tile * tile_rows + (uint64_t)u * pass_rows + ((uint64_t)j * BLOCK + tid) * 2;
                     const uint32_t mine = (uint32_t)(__popcll(m0 & lt) + __popcll(m1 & lt));  // survivors of the lanes below, both rows
-                    if (p0) out_rows[at + before + mine] = row_base + r0;
-                    if (p1) out_rows[at + before + mine + (p0 ? 1u : 0u)] = row_base + r0 + 1;
+                    if (p0) out_rows[at + before + mine] = (ORD)(row_base + r0);
+                    if (p1) out_rows[at + before + mine + (p0 ? 1u : 0u)] = (ORD)(row_base + r0 + 1);
                 } else {
                     const bool p = (bits[u] >> j) & 1u;
                     const unsigned long long m = __ballot(p);
                     if (p) out_rows[at + before + (uint32_t)__popcll(m & lt)] =
-                               row_base + tile * tile_rows + (uint64_t)u * pass_rows + (uint64_t)j * BLOCK + tid;
+                               (ORD)(row_base + tile * tile_rows + (uint64_t)u * pass_rows + (uint64_t)j * BLOCK + tid);
                 }
                 at += all;
             }
@@ -2829,9 +2832,10 @@ __global__ __launch_bounds__(BLOCK) void filter_stream_kernel(const Program P, u
     if (unsupported) atomicOr(err_flags, (uint32_t)ERR_UNSUPPORTED_VALUE);
 }
 
-hipError_t launch_filter_stream(const Program& P, uint64_t nrows, uint64_t row_base, uint64_t* out_rows, unsigned long long* tile_state,
-                                unsigned long long* tile_counter, unsigned long long* total, uint32_t* err_flags, uint32_t grid,
-                                hipStream_t st, bool fast) {
+template <typename ORD>
+static hipError_t launch_filter_stream_as(const Program& P, uint64_t nrows, uint64_t row_base, ORD* out_rows, unsigned long long* tile_state,
+                                          unsigned long long* tile_counter, unsigned long long* total, uint32_t* err_flags, uint32_t grid,
+                                          hipStream_t st, bool fast) {
     const uint64_t ntiles = (nrows + kFilterStreamTile - 1) / kFilterStreamTile;
     hipError_t e = hipMemsetAsync(tile_state, 0, (size_t)(ntiles + 1) * sizeof(unsigned long long), st);  // (+1: the tile counter behind it)
     if (e != hipSuccess) return e;
@@ -2844,11 +2848,101 @@ hipError_t launch_filter_stream(const Program& P, uint64_t nrows, uint64_t row_b
         F.op = t.op;
         F.ctag = t.b.ctag;
         F.cpayload = t.b.cpayload;
-        hipLaunchKernelGGL((filter_stream_kernel<8, 256, 4, true>), dim3(grid), dim3(256), 0, st, P, nrows, row_base, out_rows, tile_state,
+        hipLaunchKernelGGL((filter_stream_kernel<ORD, 8, 256, 4, true>), dim3(grid), dim3(256), 0, st, P, nrows, row_base, out_rows, tile_state,
                            tile_counter, total, err_flags, F);
     } else
-        hipLaunchKernelGGL((filter_stream_kernel<8, 256, 4, false>), dim3(grid), dim3(256), 0, st, P, nrows, row_base, out_rows, tile_state,
+        hipLaunchKernelGGL((filter_stream_kernel<ORD, 8, 256, 4, false>), dim3(grid), dim3(256), 0, st, P, nrows, row_base, out_rows, tile_state,
                            tile_counter, total, err_flags, F);
+    return hipGetLastError();
+}
+
+hipError_t launch_filter_stream(const Program& P, uint64_t nrows, uint64_t row_base, uint64_t* out_rows, unsigned long long* tile_state,
+                                unsigned long long* tile_counter, unsigned long long* total, uint32_t* err_flags, uint32_t grid,
+                                hipStream_t st, bool fast) {
+    return launch_filter_stream_as<uint64_t>(P, nrows, row_base, out_rows, tile_state, tile_counter, total, err_flags, grid, st, fast);
+}
+
+// the 32-bit form: batch-local ordinals (row_base 0) of a batch of fewer than 2^32 rows
+hipError_t launch_filter_stream(const Program& P, uint64_t nrows, uint32_t* out_rows, unsigned long long* tile_state,
+                                unsigned long long* tile_counter, unsigned long long* total, uint32_t* err_flags, uint32_t grid,
+                                hipStream_t st, bool fast) {
+    if (nrows >> 32) return hipErrorInvalidValue;
+    return launch_filter_stream_as<uint32_t>(P, nrows, 0, out_rows, tile_state, tile_counter, total, err_flags, grid, st, fast);
+}
+
+// ------------------------------------------------------------------ the survivors' rows (n1k_gather_selected)
+//
+// Row i of every output column = row rows[i] of its source column, for i < n (execution/filter.go:49-61: the items a Filter sends
+// on, here column-wise).  The ordinals ascend, so a wave's reads fall into a few neighbouring lines; the writes are dense.  A lane
+// takes 4 consecutive output rows: their ordinals in one 16-byte load (the selection buffer is the handle's own allocation), per
+// column 4 element loads, then — where the output array is aligned for it — one 4-byte store of tags, two 16-byte stores of
+// payloads, one 16-byte store of codes; an output array that is not so aligned gets element stores, and so do the 1 to 3 rows
+// behind the last full four.  (4 rows of an array are a multiple of its vector store, so whether the wide store applies is a
+// property of the array: uniform over the launch.)  All columns in one launch, their descriptors in the kernel arguments.
+N1K_DEV void gather_col4(const GatherCol& c, const uint32_t (&r)[4], uint64_t i0) {
+    if (c.kind == COLK_DICT32) {
+        uint32_t v[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) v[k] = c.src_codes[r[k]];
+        uint32_t* d = c.dst_codes + i0;
+        if (((uintptr_t)d & 15) == 0) *(uint4*)d = make_uint4(v[0], v[1], v[2], v[3]);
+        else {
+#pragma unroll
+            for (int k = 0; k < 4; k++) d[k] = v[k];
+        }
+    } else {
+        uint32_t t[4];
+        uint64_t p[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            t[k] = c.src_tags[r[k]];
+            p[k] = c.src_payload[r[k]];
+        }
+        uint8_t* dt = c.dst_tags + i0;
+        if (((uintptr_t)dt & 3) == 0) *(uint32_t*)dt = t[0] | t[1] << 8 | t[2] << 16 | t[3] << 24;
+        else {
+#pragma unroll
+            for (int k = 0; k < 4; k++) dt[k] = (uint8_t)t[k];
+        }
+        uint64_t* dp = c.dst_payload + i0;
+        if (((uintptr_t)dp & 15) == 0) {
+            typedef unsigned long long n1k_u64x2 __attribute__((ext_vector_type(2)));
+            ((n1k_u64x2*)dp)[0] = n1k_u64x2{p[0], p[1]};
+            ((n1k_u64x2*)dp)[1] = n1k_u64x2{p[2], p[3]};
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; k++) dp[k] = p[k];
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void gather_rows_kernel(const GatherArgs A) {
+    const uint64_t i0 = ((uint64_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (i0 >= A.n) return;
+    if (i0 + 4 <= A.n) {
+        const uint4 q = *(const uint4*)(A.rows + i0);
+        const uint32_t r[4] = {q.x, q.y, q.z, q.w};
+        for (uint32_t c = 0; c < A.ncols; c++) gather_col4(A.cols[c], r, i0);
+        return;
+    }
+    for (uint64_t i = i0; i < A.n; i++) {  // the rows behind the last full four
+        const uint32_t r = A.rows[i];
+        for (uint32_t c = 0; c < A.ncols; c++) {
+            const GatherCol& g = A.cols[c];
+            if (g.kind == COLK_DICT32) g.dst_codes[i] = g.src_codes[r];
+            else {
+                g.dst_tags[i] = g.src_tags[r];
+                g.dst_payload[i] = g.src_payload[r];
+            }
+        }
+    }
+}
+
+hipError_t launch_gather_rows(const GatherArgs& A, hipStream_t st) {
+    if (A.n == 0 || A.ncols == 0) return hipSuccess;
+    if (A.ncols > kGatherMaxCols || (A.n >> 32) || ((uintptr_t)A.rows & 15)) return hipErrorInvalidValue;
+    const uint64_t lanes = (A.n + 3) / 4;
+    hipLaunchKernelGGL(gather_rows_kernel, dim3((uint32_t)((lanes + 255) / 256)), dim3(256), 0, st, A);
     return hipGetLastError();
 }
 

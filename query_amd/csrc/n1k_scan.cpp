@@ -489,6 +489,21 @@ interpreter:
     return N1K_OK;
 }
 
+// one comparison of a TAGGED64 column with a NUMBER constant, arrays aligned for two rows per load: the wide variant
+bool filter_stream_fast(const n1k_handle* h) {
+    const Program& P = h->prog;
+    if (!(h->opt.wide && P.nlogic == 1 && P.logic[0].op == LOGIC_PUSH)) return false;
+    const Term& t = P.terms[P.logic[0].arg];
+    return t.op >= TERM_NUM_LT && t.op <= TERM_NUM_EQ && !t.a.is_const && t.a.col < (uint32_t)h->plan.paths.size() &&
+           P.cols[t.a.col].kind == COLK_TAGGED64 && (uintptr_t)P.cols[t.a.col].payload % 16 == 0 && (uintptr_t)P.cols[t.a.col].tags % 2 == 0;
+}
+
+uint32_t filter_stream_grid(const n1k_handle* h, uint64_t ntiles, bool fast) {
+    if (fast)  // (84 VGPRs; measured 4: 0.43, 5: 0.39, 6: 0.40, 8: 0.40 ms per 100 M rows)
+        return (uint32_t)std::min<uint64_t>(ntiles, (uint64_t)h->num_cus * (h->opt.grid_blocks ? h->opt.grid_blocks : 5));
+    return (uint32_t)std::min<uint64_t>(ntiles, (uint64_t)h->num_cus * 4);  // (124 VGPRs: four 256-thread workgroups per CU)
+}
+
 n1k_status run_filter_batch(n1k_handle* h, const n1k_batch* b) {
     Program& P = h->prog;
     if (b->nrows == 0) return N1K_OK;
@@ -499,15 +514,8 @@ n1k_status run_filter_batch(n1k_handle* h, const n1k_batch* b) {
     const uint64_t ntiles = (b->nrows + kFilterStreamTile - 1) / kFilterStreamTile;
     HIP_TRY(h, h->filter.tile_off.ensure(ntiles + 1));
     HIP_TRY(h, h->filter.sel.ensure(b->nrows));
-    uint32_t grid = (uint32_t)std::min<uint64_t>(ntiles, (uint64_t)h->num_cus * 4);  // (124 VGPRs: four 256-thread workgroups per CU)
-    // one comparison of a TAGGED64 column with a NUMBER constant, arrays aligned for two rows per load: the wide variant
-    bool fast = h->opt.wide && P.nlogic == 1 && P.logic[0].op == LOGIC_PUSH;
-    if (fast) {
-        const Term& t = P.terms[P.logic[0].arg];
-        fast = t.op >= TERM_NUM_LT && t.op <= TERM_NUM_EQ && !t.a.is_const && t.a.col < (uint32_t)h->plan.paths.size() &&
-               P.cols[t.a.col].kind == COLK_TAGGED64 && (uintptr_t)P.cols[t.a.col].payload % 16 == 0 && (uintptr_t)P.cols[t.a.col].tags % 2 == 0;
-    }
-    if (fast) grid = (uint32_t)std::min<uint64_t>(ntiles, (uint64_t)h->num_cus * (h->opt.grid_blocks ? h->opt.grid_blocks : 5));  // (84 VGPRs; measured 4: 0.43, 5: 0.39, 6: 0.40, 8: 0.40 ms per 100 M rows)
+    const bool fast = filter_stream_fast(h);
+    const uint32_t grid = filter_stream_grid(h, ntiles, fast);
     if (e0) (void)hipEventRecord(e0, h->stream);
     HIP_TRY(h, launch_filter_stream(P, b->nrows, h->row_base, h->filter.sel.p, (unsigned long long*)h->filter.tile_off.p,
                                     (unsigned long long*)h->filter.tile_off.p + ntiles, h->groups.counters.p + 3, h->groups.errp, grid, h->stream, fast));

@@ -174,6 +174,38 @@ class GpuFilterGroup:
     def process_device_batch(self, batch):
         self._check(self._lib.n1k_push_device_batch(self._h, C.byref(batch[0])))
 
+    # ------------------------------------------------- Filter-only on the device
+    def filter_device_batch(self, batch):
+        """n1k_filter_device_batch: one whole execution of a Filter-only plan over a device-resident batch (as
+        make_device_batch builds it).  Returns (nselected, device address of the ascending uint32 batch-local ordinals; None
+        when nothing passed): the ordinals stay in the handle's device memory until the next call / reopen / done."""
+        sel = _ffi.Selection()
+        self._nselected = 0
+        self._check(self._lib.n1k_filter_device_batch(self._h, C.byref(batch[0]), C.byref(sel)))
+        self._nselected = int(sel.nselected)
+        return self._nselected, sel.rows
+
+    def selected_host32(self, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """n1k_selected_to_host32: the last selection's ordinals as a numpy uint32 array (`out`: a caller's buffer, a
+        view of pinned memory for instance, filled from its start and returned cut to the selection)."""
+        n = getattr(self, "_nselected", 0)
+        buf = np.empty(n, dtype=np.uint32) if out is None else out
+        assert buf.dtype == np.uint32 and buf.flags["C_CONTIGUOUS"]
+        self._check(self._lib.n1k_selected_to_host32(self._h, buf.ctypes.data, buf.size))
+        return buf[:n]
+
+    def gather_selected(self, src_batch, capacity_rows: int, out_cols: Sequence[tuple]):
+        """n1k_gather_selected: the selected rows of `src_batch` (device-resident, 1 to 16 columns of either kind, the row
+        count of the filtered batch) into out_cols = [(kind, tags_ptr, payload_ptr, codes_ptr)] device addresses with room
+        for capacity_rows rows.  Asynchronous on the handle's stream: sync() waits for it."""
+        arr = (_ffi.Col * max(len(out_cols), 1))()
+        for i, (kind, tags, payload, codes) in enumerate(out_cols):
+            arr[i].kind = kind
+            arr[i].tags = tags
+            arr[i].payload = payload
+            arr[i].codes = codes
+        self._check(self._lib.n1k_gather_selected(self._h, C.byref(src_batch[0]), int(capacity_rows), arr))
+
     # ------------------------------------------------------------ raw documents
     @staticmethod
     def _pack_docs(docs: Sequence[bytes]):
