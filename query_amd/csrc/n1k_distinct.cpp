@@ -1,10 +1,117 @@
-// n1k_distinct.cpp — the sets of the DISTINCT aggregates at finish (value/set.go:65-110, algebra/agg_count_distinct.go:84-126).
+// n1k_distinct.cpp — the DISTINCT aggregates: the pair and word logs and the hash regions the scan fills, grown before each
+// batch, and the sets built of them at finish (value/set.go:65-110, algebra/agg_count_distinct.go:84-126).
 #include "n1k_engine.h"
 
 using namespace n1k;
 using namespace n1k_eng;
 
 namespace n1k_eng {
+
+// The pair and word logs with room for every row up to row_base + nrows, and A's log fields.
+n1k_status distinct_grow_logs(n1k_handle* h, uint64_t nrows, ScanArgs& A) {
+    // every qualifying operand appends one (group key, value, class) pair: at most one per row and aggregate
+    uint64_t need = h->row_base + nrows;
+    if (need > h->distinct.log_capacity) {
+        uint64_t cap = std::max<uint64_t>(need, h->distinct.log_capacity * 2);
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        for (uint32_t d = 0; d < h->n_distinct; d++) {
+            DevBuf<uint64_t> nk, nv, nw;
+            DevBuf<uint8_t> nc;
+            HIP_TRY(h, nk.ensure(cap));
+            HIP_TRY(h, nv.ensure(cap));
+            HIP_TRY(h, nc.ensure(cap));
+            if (h->distinct.words[d]) HIP_TRY(h, nw.ensure(cap));
+            if (h->distinct.log_capacity) {
+                HIP_TRY(h, hipMemcpy(nk.p, h->distinct.log_key[d].p, h->distinct.log_capacity * 8, hipMemcpyDeviceToDevice));
+                HIP_TRY(h, hipMemcpy(nv.p, h->distinct.log_val[d].p, h->distinct.log_capacity * 8, hipMemcpyDeviceToDevice));
+                HIP_TRY(h, hipMemcpy(nc.p, h->distinct.log_cls[d].p, h->distinct.log_capacity, hipMemcpyDeviceToDevice));
+                if (h->distinct.words[d])
+                    HIP_TRY(h, hipMemcpy(nw.p, h->distinct.log_word[d].p, h->distinct.log_capacity * 8, hipMemcpyDeviceToDevice));
+            }
+            h->distinct.log_key[d] = std::move(nk);
+            h->distinct.log_val[d] = std::move(nv);
+            h->distinct.log_cls[d] = std::move(nc);
+            h->distinct.log_word[d] = std::move(nw);
+        }
+        h->distinct.log_capacity = cap;
+    }
+    for (uint32_t d = 0; d < h->n_distinct; d++) {
+        A.log_key[d] = h->distinct.log_key[d].p;
+        A.log_val[d] = h->distinct.log_val[d].p;
+        A.log_cls[d] = h->distinct.log_cls[d].p;
+        A.log_word[d] = h->distinct.words[d] ? h->distinct.log_word[d].p : nullptr;
+    }
+    A.log_cursor = h->groups.counters.p + 8;
+    A.word_cursor = h->groups.counters.p + 16;
+    A.log_capacity = h->distinct.log_capacity;
+    A.nw_key_bits = h->distinct.nw_key_bits;
+    A.nw_val_bits = h->distinct.nw_val_bits;
+    if (!h->distinct.word_hist.p) {
+        HIP_TRY(h, h->distinct.word_hist.ensure(kMaxDistinct * 256));
+        HIP_TRY(h, hipMemsetAsync(h->distinct.word_hist.p, 0, kMaxDistinct * 256 * sizeof(unsigned long long), h->stream));
+    }
+    A.word_hist = h->distinct.word_hist.p;
+    bool any_words = false;
+    for (uint32_t d = 0; d < h->n_distinct; d++) any_words |= h->distinct.words[d];
+    A.dcache_aggs = any_words ? h->n_distinct : 0;
+    A.dcache_slots = any_words ? 4096u / (h->n_distinct > 2 ? 4u : h->n_distinct) : 0;  // 32 KB of LDS in all
+    return N1K_OK;
+}
+
+// The hash regions of the plan-specialised scan's COUNT(DISTINCT), sized or regrown for nrows more rows, and L.
+n1k_status distinct_grow_regions(n1k_handle* h, const Program& P, uint64_t nrows, const ScanArgs& A, uint32_t dcache_slots, WordLogArgs& L) {
+    // hash regions: 256 x kRecSubs sub-regions per DISTINCT aggregate, each with room for its share of all rows
+    // pushed so far plus a quarter (mix64 spreads distinct words evenly; many copies of few words overflow into the
+    // plain word log)
+    const uint64_t rows_total = h->row_base + nrows;
+    uint64_t need = h->opt.region_cap ? h->opt.region_cap : (rows_total + rows_total / 4) / kWordSubs + 4096;
+    need = (need + 15) / 16 * 16;  // whole 128-byte lines
+    if (!h->distinct.wcursor.p) {
+        HIP_TRY(h, h->distinct.wcursor.ensure(kMaxDistinct * kWordSubs * kCursorStride));
+        HIP_TRY(h, hipMemsetAsync(h->distinct.wcursor.p, 0, kMaxDistinct * kWordSubs * kCursorStride * sizeof(unsigned long long), h->stream));
+    }
+    if (need > h->distinct.wregion_cap) {
+        const uint64_t ncap = (std::max<uint64_t>(need, h->distinct.wregion_cap * 2) + 15) / 16 * 16;
+        if (ncap >= 0xFFFFFF00ull) return fail(h, N1K_OOM, "COUNT(DISTINCT): more than 2^32 words per hash region");
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        for (uint32_t a = 0; a < P.naggs; a++) {
+            if (!P.aggs[a].distinct) continue;
+            const uint32_t li = P.aggs[a].log_index;
+            DevBuf<uint64_t> nb;
+            HIP_TRY(h, nb.ensure(kWordSubs * ncap));
+            if (h->distinct.wregion_cap && h->distinct.wregion_used)
+                HIP_TRY(h, launch_regrow_regions(h->distinct.wregion[li].p, kWordSubs, h->distinct.wregion_cap, nb.p, ncap,
+                                                 h->distinct.wcursor.p + (size_t)li * kWordSubs * kCursorStride, h->stream));  // (clamps the cursors of regions that had overflowed)
+            HIP_TRY(h, hipStreamSynchronize(h->stream));
+            h->distinct.wregion[li] = std::move(nb);
+        }
+        h->distinct.wregion_cap = ncap;
+    }
+    uint32_t d = 0;
+    for (uint32_t a = 0; a < P.naggs; a++) {
+        if (!P.aggs[a].distinct) continue;
+        const uint32_t li = P.aggs[a].log_index;
+        L.region[d] = h->distinct.wregion[li].p;
+        L.region_cursor[d] = h->distinct.wcursor.p + (size_t)li * kWordSubs * kCursorStride;
+        L.over_word[d] = A.log_word[li];
+        L.log_key[d] = A.log_key[li];
+        L.log_val[d] = A.log_val[li];
+        L.log_cls[d] = A.log_cls[li];
+        L.log_index[d] = li;
+        d++;
+    }
+    L.region_cap = h->distinct.wregion_cap;
+    L.over_cursor = A.word_cursor;
+    L.over_hist = A.word_hist;
+    L.over_capacity = A.log_capacity;
+    L.log_cursor = A.log_cursor;
+    L.log_capacity = A.log_capacity;
+    L.nw_key_bits = h->distinct.nw_key_bits;
+    L.nw_val_bits = h->distinct.nw_val_bits;
+    L.dcache_slots = dcache_slots;
+    h->distinct.wregion_used = true;
+    return N1K_OK;
+}
 
 // where the de-duplication kernel counts the new members of each group: by the packed key itself when the plan has one
 // dictionary key of a small domain, in an LDS hash table while the group table is small, else per member in HBM

@@ -1128,18 +1128,13 @@ n1k_status n1k_jit_check(n1k_handle* h, const uint32_t* col_kinds, uint32_t ncol
     for (uint32_t c = ncols; c < h->prog.ncols; c++) h->prog.cols[c].kind = COLK_TAGGED64;
     FastArgs F;
     const uint32_t max_slots = (uint32_t)std::min<uint64_t>((156u * 1024u) / (h->prog.lds_words * 8), 1u << 15);
-    // (plans with arithmetic: the shape that evaluates the nodes in registers, as run_group_batch would choose it)
+    // (plans with arithmetic: the shape that evaluates the nodes in registers, the one choose_scan tries first)
     const bool fuse = !h->derived.empty() && h->opt.fuse_arith;
     if (!build_fast_args(h, max_slots, F, fuse)) return fail(h, N1K_UNSUPPORTED, "the plan shape is outside the bounded family");
-    SpecSig sig = make_plan_sig(h, F);
     std::string l;
-    bool ok = jit_compile_check(sig, &l);
-    if (ok && build_fast_args(h, 1u << 15, F, fuse, true)) {  // the same shape's partition kernels (multi-GPU row exchange)
-        SpecSig ps = make_plan_sig(h, F);
-        ps.mode = 1;
-        ps.hashed = 0;
-        ok = jit_compile_check(ps, &l);
-    }
+    bool ok = shape_compiles(h, F, ShapeUse::Scan, &l);
+    // the same shape's partition kernels (multi-GPU row exchange)
+    if (ok && build_fast_args(h, 1u << 15, F, fuse, true)) ok = shape_compiles(h, F, ShapeUse::Partition, &l);
     if (log && loglen) snprintf(log, loglen, "%s", l.c_str());
     return ok ? N1K_OK : fail(h, N1K_DEVICE_ERROR, "run-time compilation failed: %s", l.substr(0, 300).c_str());
     });

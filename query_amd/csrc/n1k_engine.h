@@ -267,8 +267,32 @@ struct FilterOnly {
 bool filter_stream_fast(const n1k_handle* h);  // the condition and the bound columns take filter_stream_kernel's FAST variant
 uint32_t filter_stream_grid(const n1k_handle* h, uint64_t ntiles, bool fast);
 bool build_fast_args(n1k_handle* h, uint32_t max_slots, FastArgs& F, bool fuse = false, bool partition_only = false);
-SpecSig make_plan_sig(const n1k_handle* h, const FastArgs& F);
-const SpecEntry* find_spec(const SpecSig& g);
+// Columns (DevCol or n1k_col) from row `off` on: an array a column does not have stays null.
+template <class Col> inline void advance_cols(Col* cols, uint32_t n, uint64_t off) {
+    for (uint32_t c = 0; c < n; c++) {
+        if (cols[c].tags) cols[c].tags += off;
+        if (cols[c].payload) cols[c].payload += off;
+        if (cols[c].codes) cols[c].codes += off;
+    }
+}
+// Every array aligned for the WIDE form of the plan-specialised kernels (two adjacent rows per lane and load)?
+template <class Col> inline bool cols_wide_aligned(const Col* cols, uint32_t n) {
+    for (uint32_t c = 0; c < n; c++)
+        if ((uintptr_t)cols[c].tags % 2 || (uintptr_t)cols[c].payload % 16 || (uintptr_t)cols[c].codes % 8) return false;
+    return true;
+}
+// The plan-specialised kernel of a plan shape, for one of its three uses: the scan (run_group_batch), the records front end
+// of the partitioned GROUP BY (run_group_records), the hash partition of the row exchange (run_partition).
+enum class ShapeUse { Scan, Records, Partition };
+struct ShapeKernel {
+    const SpecEntry* spec = nullptr;  // instantiated ahead of time (n1k_spec.h), or
+    const JitKernel* jit = nullptr;   // the same template built at run time (n1k_jit.h)
+    uint32_t stat = 0;                // stats.spec_kernel: 0 none, 1 prebuilt, 2 built at run time, 3 ... with the arithmetic nodes in registers
+    explicit operator bool() const { return spec || jit; }
+};
+// table_bytes (Scan): the workgroup's LDS table as the kernel would lay it out
+ShapeKernel shape_kernel(n1k_handle* h, const FastArgs& F, ShapeUse use, uint64_t nrows, size_t table_bytes = 0);
+bool shape_compiles(const n1k_handle* h, const FastArgs& F, ShapeUse use, std::string* log);  // n1k_jit_check: compiles only, no device
 n1k_status run_group_batch(n1k_handle* h, const n1k_batch* b);
 n1k_status run_filter_batch(n1k_handle* h, const n1k_batch* b);
 n1k_status bind_columns(n1k_handle* h, const n1k_batch* b, bool defer = false);
@@ -308,7 +332,7 @@ n1k_status flush_pending(n1k_handle* h);
 n1k_status run_group_partitioned(n1k_handle* h, const n1k_batch* b, const PartitionPlan& pp, uint64_t groups_est, bool may_keep_region);
 n1k_status run_group_records(n1k_handle* h, const n1k_batch* b, const PartitionPlan& pp, uint64_t groups_est, bool may_keep_region, bool* done);
 
-// ---- n1k_distinct.cpp: the sets of the DISTINCT aggregates at finish (the scan fills the logs and regions: n1k_scan.cpp)
+// ---- n1k_distinct.cpp: the logs and hash regions the scan fills for the DISTINCT aggregates, and their sets at finish
 struct Distinct {
     // the (key, value, class) pair logs and the global sets n1k_finish builds of them
     DevBuf<uint64_t> log_key[kMaxDistinct], log_val[kMaxDistinct], regions, set_table;
@@ -327,6 +351,10 @@ struct Distinct {
     uint32_t path = 0;  // how the last finish built the sets: bit 0 global pair sets, bit 1 LDS word sets, bit 2 global word set
     uint64_t log_capacity = 0;
 };
+// before a batch of nrows rows is scanned: room for its pairs in the logs (A's log fields) / for its member words in the hash
+// regions of the plan-specialised scan (L; P: the program that scan runs on)
+n1k_status distinct_grow_logs(n1k_handle* h, uint64_t nrows, ScanArgs& A);
+n1k_status distinct_grow_regions(n1k_handle* h, const Program& P, uint64_t nrows, const ScanArgs& A, uint32_t dcache_slots, WordLogArgs& L);
 n1k_status distinct_words_finish(n1k_handle* h, const AggSpec& ag, uint64_t nwords, bool hist_counted = true, const uint64_t* log = nullptr);
 n1k_status distinct_regions_finish(n1k_handle* h, const AggSpec& ag, uint64_t nover, bool force_exact, bool* deferred);
 

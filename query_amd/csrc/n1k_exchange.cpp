@@ -21,33 +21,15 @@ static n1k_status run_partition(n1k_handle* h, const n1k_batch* b, PartArgs& A) 
     }
     const uint64_t n = b->nrows;
     FastArgs F;
-    const JitKernel* jit = nullptr;
+    ShapeKernel K;
     const bool fuse = !h->derived.empty() && !h->derived_ready;
-    if (h->opt.spec && h->opt.jit && (h->opt.jit == 2 || n >= h->opt.jit_min_rows) && n < (1ull << 31) && (!fuse || h->opt.fuse_arith) &&
-        sizeof(Program) + sizeof(FastArgs) + sizeof(PartArgs) + 64 <= 4096 && build_fast_args(h, 1u << 15, F, fuse, true)) {
-        // what the staging needs in LDS (n1k_spec.h PartLds: 2048 rows x (9 B per TAGGED64 column, 4 B per DICT32 column, 1))
-        size_t lds = 2048 + 2048 + 4096;  // (+ the per-destination tables of PartLds)
-        for (uint32_t c = 0; c < F.ncols; c++) lds += 2048u * (F.cols[c].kind == COLK_DICT32 ? 4u : 9u);
-        lds += match_lds_bytes(F);
-        if (lds <= 60 * 1024) {
-            SpecSig sig = make_plan_sig(h, F);
-            sig.mode = 1;
-            sig.hashed = 0;  // (no table in this mode)
-            jit = jit_get(sig);
-            if (jit->failed || !jit->part_wide) {
-                h->jit_log = jit->log;
-                jit = nullptr;
-            }
-        }
-    }
+    if (n < (1ull << 31) && (!fuse || h->opt.fuse_arith) && sizeof(Program) + sizeof(FastArgs) + sizeof(PartArgs) + 64 <= 4096 &&
+        build_fast_args(h, 1u << 15, F, fuse, true))
+        K = shape_kernel(h, F, ShapeUse::Partition, n);
     hipEvent_t e0 = get_event(h), e1 = get_event(h);
-    if (jit) {
-        bool aligned = true;
-        for (uint32_t c = 0; c < F.ncols; c++) {
-            F.cols[c] = h->prog.cols[c];
-            aligned &= ((uintptr_t)F.cols[c].tags % 2 == 0) && ((uintptr_t)F.cols[c].payload % 16 == 0) && ((uintptr_t)F.cols[c].codes % 8 == 0);
-        }
-        const bool wide = aligned && h->opt.wide && n >= 2;
+    if (K) {
+        std::copy_n(h->prog.cols, F.ncols, F.cols);
+        const bool wide = cols_wide_aligned(F.cols, F.ncols) && h->opt.wide && n >= 2;
         F.nrows = (uint32_t)n;
         F.row_base = h->row_base;
         F.err_flags = h->groups.errp;
@@ -69,8 +51,8 @@ static n1k_status run_partition(n1k_handle* h, const n1k_batch* b, PartArgs& A) 
             grid = (grid + kRowSubs - 1) / kRowSubs * kRowSubs;
         }
         if (e0) (void)hipEventRecord(e0, h->stream);
-        HIP_TRY(h, jit_launch_partition(jit, h->prog, F, A, grid, wide, pblock, h->stream));
-        h->timing.stats.spec_kernel = F.nderived ? 3u : 2u;
+        HIP_TRY(h, jit_launch_partition(K.jit, h->prog, F, A, grid, wide, pblock, h->stream));
+        h->timing.stats.spec_kernel = K.stat;
     } else {
         n1k_status st = materialize_derived(h, b);
         if (st != N1K_OK) return st;

@@ -216,17 +216,8 @@ n1k_status run_group_records(n1k_handle* h, const n1k_batch* b, const PartitionP
     FastArgs F;
     const uint32_t direct_max_slots = (uint32_t)std::min<uint64_t>((156u * 1024u) / (P.lds_words * 8), 1u << 15);
     if (!build_fast_args(h, direct_max_slots, F)) return N1K_OK;
-    const SpecSig sig = make_plan_sig(h, F);
-    const SpecEntry* spec = find_spec(sig);
-    const JitKernel* jit = nullptr;
-    if (!spec && h->opt.jit) {
-        jit = jit_get(sig);
-        if (jit->failed || !jit->rec_wide) {
-            h->jit_log = jit->log;
-            jit = nullptr;
-        }
-    }
-    if (!spec && !jit) return N1K_OK;
+    const ShapeKernel K = shape_kernel(h, F, ShapeUse::Records, n);
+    if (!K) return N1K_OK;
     n1k_status st = ensure_table(h, 0);
     if (st != N1K_OK) return st;
     // the scan: tiles of 2048 rows, a grid that is a multiple of 8 (sub-region = workgroup label, n1k_spec.h)
@@ -263,12 +254,8 @@ n1k_status run_group_records(n1k_handle* h, const n1k_batch* b, const PartitionP
     HIP_TRY(h, hipMemsetAsync(d_flags, 0, 8, h->stream));
     HIP_TRY(h, hipMemcpyAsync(h->groups.counters.p + 25, h->groups.counters.p + 0, 8, hipMemcpyDeviceToDevice, h->stream));  // rows_selected, to undo
     // (1) Filter + packed key + operand -> records in the hash regions
-    bool aligned = true;
-    for (uint32_t c = 0; c < P.ncols; c++) {
-        F.cols[c] = P.cols[c];
-        aligned &= ((uintptr_t)F.cols[c].tags % 2 == 0) && ((uintptr_t)F.cols[c].payload % 16 == 0) && ((uintptr_t)F.cols[c].codes % 8 == 0);
-    }
-    const bool wide = aligned && h->opt.wide && n >= 2;
+    std::copy_n(P.cols, P.ncols, F.cols);
+    const bool wide = cols_wide_aligned(F.cols, P.ncols) && h->opt.wide && n >= 2;
     F.nrows = (uint32_t)n;
     F.row_base = h->row_base;
     F.err_flags = h->groups.errp;
@@ -279,8 +266,8 @@ n1k_status run_group_records(n1k_handle* h, const n1k_batch* b, const PartitionP
     L.region_cursor[0] = h->part.rcursor.p;
     L.region_cap = cap;
     L.rec_overflow = d_flags;
-    if (spec) HIP_TRY(h, spec->launch_records(P, F, grid, wide, L, h->stream));
-    else HIP_TRY(h, jit_launch_records(jit, P, F, grid, wide, L, h->stream));
+    if (K.spec) HIP_TRY(h, K.spec->launch_records(P, F, grid, wide, L, h->stream));
+    else HIP_TRY(h, jit_launch_records(K.jit, P, F, grid, wide, L, h->stream));
     // (2) the second partition pass: the regions' 8 sub-regions into `bps` bins of fixed capacity per region
     BinAggArgs B{};
     B.nsrc = pp.nsrc;
@@ -351,7 +338,7 @@ n1k_status run_group_records(n1k_handle* h, const n1k_batch* b, const PartitionP
     *done = true;
     emitted = std::min<unsigned long long>(emitted, ecap);
     h->timing.stats.agg_mode = N1K_MODE_PARTITIONED;
-    h->timing.stats.spec_kernel = spec ? 1u : 2u;
+    h->timing.stats.spec_kernel = K.stat;
     if (may_keep_region && have == 0 && singletons == 0) {
         h->part.pending.count = emitted;
         h->part.pending.cap = ecap;

@@ -1,5 +1,7 @@
-// n1k_scan.cpp — one column batch through Filter + InitialGroup: which kernel family runs it (plan-specialised ahead of
-// time or at run time, bounded-shape, interpreter), Filter-only batches, derived columns, staging of host batches.
+// n1k_scan.cpp — one column batch through Filter + InitialGroup: the one lookup from a plan shape to its plan-specialised
+// kernel, prebuilt or built at run time (shape_kernel: for the scan, the records front end and the row exchange's partition);
+// which kernel family runs a batch (choose_scan: specialised, bounded-shape, interpreter) and its launches (run_group_batch);
+// Filter-only batches, derived columns, staging of host batches.
 #include "n1k_engine.h"
 
 using namespace n1k;
@@ -113,8 +115,8 @@ bool build_fast_args(n1k_handle* h, uint32_t max_slots, FastArgs& F, bool fuse, 
     return true;
 }
 
-// shape of the compiled plan (what a plan-specialised kernel is instantiated for)
-SpecSig make_plan_sig(const n1k_handle* h, const FastArgs& F) {
+// shape of the compiled plan (what a plan-specialised kernel is instantiated for), as the use's kernels are built for it
+static SpecSig make_plan_sig(const n1k_handle* h, const FastArgs& F, ShapeUse use) {
     const Program& P = h->prog;
     SpecSig g{};
     g.ncols = (int)F.ncols; g.nterms = (int)F.nterms; g.nkeys = (int)F.nkeys; g.naggs = (int)F.naggs;
@@ -143,322 +145,234 @@ SpecSig make_plan_sig(const n1k_handle* h, const FastArgs& F) {
             g.derived[d].ops[k].v = o.is_const ? o.ctag : o.col;
         }
     }
+    // (segmented batches — a received row region — have their own variant of the scan kernels)
+    if (use == ShapeUse::Scan) g.seg = h->push_nseg > 1 ? 1 : 0;
+    if (use == ShapeUse::Partition) {
+        g.mode = 1;
+        g.hashed = 0;  // (no table in this mode)
+    }
     return g;
 }
 
-// exact-shape lookup among the ahead-of-time instantiated plan shapes (n1k_spec.h)
-const SpecEntry* find_spec(const SpecSig& g) {
-    for (const SpecEntry& e : spec_registry())
-        if (memcmp(&e.sig, &g, sizeof g) == 0) return &e;
-    return nullptr;
+bool shape_compiles(const n1k_handle* h, const FastArgs& F, ShapeUse use, std::string* log) {
+    return jit_compile_check(make_plan_sig(h, F, use), log);
 }
 
-n1k_status run_group_batch(n1k_handle* h, const n1k_batch* b) {
-    Program& P = h->prog;
-    n1k_status st = ensure_table(h, b->nrows);
-    if (st != N1K_OK) return st;
-    ScanArgs A{};
-    A.nrows = b->nrows;
-    A.nrows_dev = h->push_nrows_dev;
-    A.row_base = h->row_base;
-    if (h->has_distinct) {
-        // every qualifying operand appends one (group key, value, class) pair: at most one per row and aggregate
-        uint64_t need = h->row_base + b->nrows;
-        if (need > h->distinct.log_capacity) {
-            uint64_t cap = std::max<uint64_t>(need, h->distinct.log_capacity * 2);
-            HIP_TRY(h, hipStreamSynchronize(h->stream));
-            for (uint32_t d = 0; d < h->n_distinct; d++) {
-                DevBuf<uint64_t> nk, nv, nw;
-                DevBuf<uint8_t> nc;
-                HIP_TRY(h, nk.ensure(cap));
-                HIP_TRY(h, nv.ensure(cap));
-                HIP_TRY(h, nc.ensure(cap));
-                if (h->distinct.words[d]) HIP_TRY(h, nw.ensure(cap));
-                if (h->distinct.log_capacity) {
-                    HIP_TRY(h, hipMemcpy(nk.p, h->distinct.log_key[d].p, h->distinct.log_capacity * 8, hipMemcpyDeviceToDevice));
-                    HIP_TRY(h, hipMemcpy(nv.p, h->distinct.log_val[d].p, h->distinct.log_capacity * 8, hipMemcpyDeviceToDevice));
-                    HIP_TRY(h, hipMemcpy(nc.p, h->distinct.log_cls[d].p, h->distinct.log_capacity, hipMemcpyDeviceToDevice));
-                    if (h->distinct.words[d])
-                        HIP_TRY(h, hipMemcpy(nw.p, h->distinct.log_word[d].p, h->distinct.log_capacity * 8, hipMemcpyDeviceToDevice));
-                }
-                h->distinct.log_key[d] = std::move(nk);
-                h->distinct.log_val[d] = std::move(nv);
-                h->distinct.log_cls[d] = std::move(nc);
-                h->distinct.log_word[d] = std::move(nw);
-            }
-            h->distinct.log_capacity = cap;
-        }
-        for (uint32_t d = 0; d < h->n_distinct; d++) {
-            A.log_key[d] = h->distinct.log_key[d].p;
-            A.log_val[d] = h->distinct.log_val[d].p;
-            A.log_cls[d] = h->distinct.log_cls[d].p;
-            A.log_word[d] = h->distinct.words[d] ? h->distinct.log_word[d].p : nullptr;
-        }
-        A.log_cursor = h->groups.counters.p + 8;
-        A.word_cursor = h->groups.counters.p + 16;
-        A.log_capacity = h->distinct.log_capacity;
-        A.nw_key_bits = h->distinct.nw_key_bits;
-        A.nw_val_bits = h->distinct.nw_val_bits;
-        if (!h->distinct.word_hist.p) {
-            HIP_TRY(h, h->distinct.word_hist.ensure(kMaxDistinct * 256));
-            HIP_TRY(h, hipMemsetAsync(h->distinct.word_hist.p, 0, kMaxDistinct * 256 * sizeof(unsigned long long), h->stream));
-        }
-        A.word_hist = h->distinct.word_hist.p;
-        bool any_words = false;
-        for (uint32_t d = 0; d < h->n_distinct; d++) any_words |= h->distinct.words[d];
-        A.dcache_aggs = any_words ? h->n_distinct : 0;
-        A.dcache_slots = any_words ? 4096u / (h->n_distinct > 2 ? 4u : h->n_distinct) : 0;  // 32 KB of LDS in all
-    }
-    uint32_t block = h->opt.block ? h->opt.block : 1024;
-    uint32_t rpl = block == 1024 ? h->opt.rows_per_lane : 4;
-    uint32_t max_slots = h->opt.lds_bytes / (P.lds_words * 8);
-    max_slots = (uint32_t)std::min<uint64_t>(max_slots, 1u << 15);
-    if (max_slots < 2) return fail(h, N1K_UNSUPPORTED, "accumulator row too wide for LDS");
-    FastArgs F;
-    // DIRECT tables may take (almost) the whole 160 KiB LDS of a CU: occupancy is chosen from the table size
-    const uint32_t direct_max_slots = (uint32_t)std::min<uint64_t>((156u * 1024u) / (P.lds_words * 8), 1u << 15);
-    // Arithmetic nodes not materialised yet: is there a run-time-built kernel of this shape that evaluates them in
-    // registers (same conditions as the kernel choice below)?  If not they become derived columns now.
-    bool fuse = false;
-    if (!h->derived_ready) {
-        if (h->opt.fuse_arith && h->opt.agg_mode != N1K_MODE_LDS_HASH && h->opt.spec && h->opt.jit &&
-            (h->opt.jit == 2 || b->nrows >= h->opt.jit_min_rows) && build_fast_args(h, direct_max_slots, F, true)) {
-            bool kh = false;
-            for (uint32_t k = 0; k < F.nkeys; k++) kh |= F.keys[k].col >= F.ncols || F.cols[F.keys[k].col].kind != COLK_DICT32;
-            if ((size_t)F.lds_slots * P.lds_words * 8 <= 64 * 1024 && kh == (F.hashed != 0)) {
-                SpecSig fs = make_plan_sig(h, F);
-                fs.seg = h->push_nseg > 1 ? 1 : 0;
-                const JitKernel* k = jit_get(fs);
-                if (k->failed) h->jit_log = k->log;
-                else fuse = true;
-            }
-        }
-        if (!fuse) {
-            st = materialize_derived(h, b);
-            if (st != N1K_OK) return st;
-        }
-    }
-    if (h->opt.agg_mode != N1K_MODE_LDS_HASH && build_fast_args(h, direct_max_slots, F, fuse)) {
-        // Shapes with COUNT(DISTINCT): the specialised kernels keep nothing of a DISTINCT aggregate in the workgroup
-        // table (its member words go to the hash regions), so they run on a copy of the program with a compact LDS layout
-        Program Pc;
-        uint32_t ndist = 0;
-        for (uint32_t a = 0; a < P.naggs; a++) ndist += P.aggs[a].distinct ? 1u : 0u;
-        if (ndist) {
-            Pc = P;
-            uint32_t w = 1;
-            for (uint32_t a = 0; a < Pc.naggs; a++) {
-                AggSpec& ag = Pc.aggs[a];
-                ag.lds_off = w;
-                if (ag.distinct) ag.lds_n = 0;
-                else w += (ag.kind == AGG_COUNT || ag.kind == AGG_COUNTN) ? 1u : (ag.kind == AGG_SUM ? kLdsWordsSum : (ag.kind == AGG_AVG ? kLdsWordsAvg : kWordsMinMax));
-            }
-            Pc.lds_words = w;
-        }
-        const Program& P = ndist ? Pc : h->prog;  // (shadows the handle's program for the launches below)
-        const uint32_t table_bytes = F.lds_slots * P.lds_words * 8;
-        const uint32_t match_lds = match_lds_bytes(F);  // static LDS of the staged match table: part of every budget below
-        // the word scatter's LDS (per DISTINCT aggregate one ScatterLds<uint64_t, 512, 4>, n1k_scatter.h: 2048 staged words,
-        // counters, run starts) and, in what is left of the workgroup's share of the CU, its "already logged" caches
-        const uint32_t scatter_bytes = ndist * (2048u * 8u + 2u * 256u * 4u + 256u * 4u + 256u * 8u + 2048u) + (ndist ? 64u : 0u);
-        uint32_t dcache_slots = 0;
-        if (ndist) {
-            const uint32_t without = table_bytes + scatter_bytes + match_lds;
-            const uint32_t share = 160u * 1024u / std::max(1u, std::min(3u, 160u * 1024u / (without + 512u)));
-            for (uint32_t sl = 4096; sl >= 64; sl >>= 1)
-                if (without + ndist * sl * 8u + 512u <= share) { dcache_slots = sl; break; }
-        }
-        const uint32_t lds_total = table_bytes + scatter_bytes + ndist * dcache_slots * 8u + match_lds;
-        // workgroups per CU that fit: 512 threads x 3 (<= 48 KiB each), x 2 (<= 72 KiB), else 1024 threads x 1
-        uint32_t fblock = h->opt.block == 1024 || h->opt.block == 512 ? h->opt.block : (table_bytes <= 72 * 1024 ? 512u : 1024u);
-        if (ndist) fblock = 512;
-        uint32_t per_cu = fblock == 512 ? (lds_total <= 48 * 1024 ? 3u : (lds_total <= 72 * 1024 ? 2u : 1u))
-                                        : (lds_total <= 72 * 1024 ? 2u : 1u);
-        if (ndist) per_cu = std::max(1u, std::min(3u, 160u * 1024u / (lds_total + 512u)));  // (two workgroups of 80 KiB fit a CU)
-        uint32_t frpl = h->opt.rows_per_lane;
-        uint32_t fgrid = h->opt.grid_blocks ? h->opt.grid_blocks : (uint32_t)(h->num_cus * per_cu);
-        // slabs + merge kernel pay off once the table is more than a few KiB
-        const bool use_slabs = !F.hashed && (h->opt.slabs == 1 ? table_bytes >= 4096 : h->opt.slabs == 2);
-        F.err_flags = h->groups.errp;
-        F.rows_selected = h->groups.counters.p + 0;
-        // a prebuilt plan-specialised kernel of exactly this shape?
-        // (segmented batches — a received row region — run on the run-time-built variant of the shape only: the prebuilt
-        //  kernels carry none of the segment bookkeeping)
-        SpecSig sig = make_plan_sig(h, F);
-        sig.seg = h->push_nseg > 1 ? 1 : 0;
-        const SpecEntry* spec = h->opt.spec && !sig.seg ? find_spec(sig) : nullptr;
-        // no prebuilt kernel of this shape: instantiate the same template at run time (large batches, or forced)
-        const JitKernel* jit = nullptr;
+// The one place that knows which plan-specialised kernel serves a shape.  Prebuilt kernels exist for the scan and the
+// records front end only, and carry none of the segment bookkeeping; otherwise the same template is instantiated at run
+// time — for the scan and the partition from jit_min_rows rows on (or forced: jit = 2), for the records at any row count.
+ShapeKernel shape_kernel(n1k_handle* h, const FastArgs& F, ShapeUse use, uint64_t nrows, size_t table_bytes) {
+    if (!h->opt.spec) return {};
+    const SpecSig g = make_plan_sig(h, F, use);
+    // exact-shape lookup among the ahead-of-time instantiated plan shapes (n1k_spec.h)
+    if (use != ShapeUse::Partition && !g.seg)
+        for (const SpecEntry& e : spec_registry())
+            if (memcmp(&e.sig, &g, sizeof g) == 0) return {&e, nullptr, 1u};
+    bool build = h->opt.jit && (use == ShapeUse::Records || h->opt.jit == 2 || nrows >= h->opt.jit_min_rows);
+    if (use == ShapeUse::Scan) {
+        // run-time instantiations take tables of at most 64 KiB, and hash exactly when some key is not a DICT32 input column
         bool key_kinds_hashed = false;
         for (uint32_t k = 0; k < F.nkeys; k++) key_kinds_hashed |= F.keys[k].col >= F.ncols || F.cols[F.keys[k].col].kind != COLK_DICT32;  // (a fused node is a TAGGED64 value)
-        if (!spec && h->opt.spec && h->opt.jit && (h->opt.jit == 2 || b->nrows >= h->opt.jit_min_rows) &&
-            table_bytes <= 64 * 1024 && key_kinds_hashed == (F.hashed != 0)) {
-            jit = jit_get(sig);
-            if (jit->failed) {
-                h->jit_log = jit->log;
-                jit = nullptr;
-            }
-        }
-        if (jit && fblock != 512) {  // run-time instantiations are built for 512-thread workgroups
-            fblock = 512;
-            per_cu = table_bytes + match_lds <= 48 * 1024 ? 3u : 2u;
-            fgrid = h->opt.grid_blocks ? h->opt.grid_blocks : (uint32_t)(h->num_cus * per_cu);
-        }
-        h->timing.stats.spec_kernel = spec ? 1u : (jit ? (F.nderived ? 3u : 2u) : 0u);
-        if (F.nderived && !jit) return fail(h, N1K_DEVICE_ERROR, "fused arithmetic without its kernel");  // (decided above)
-        if ((F.hashed || ndist || h->push_nrows_dev || h->push_nseg) && !spec && !jit) goto interpreter;  // the bounded-shape kernel is DIRECT only, no DISTINCT
-        F.nrows_dev = h->push_nrows_dev;
-        if (h->push_nseg > 1) {
-            if (h->push_nseg > kMaxSegments || b->nrows >= (1ull << 31)) return fail(h, N1K_INVALID, "segmented batch too large");
-            F.nseg = h->push_nseg;
-            F.seg_rows = (uint32_t)h->push_seg_rows;
-            F.seg_count_stride = kCursorStride;
-            F.seg_counts = h->push_seg_counts;
-        }
-        WordLogArgs L;
-        memset(&L, 0, sizeof L);
-        if (ndist) {
-            // hash regions: 256 x kRecSubs sub-regions per DISTINCT aggregate, each with room for its share of all rows
-            // pushed so far plus a quarter (mix64 spreads distinct words evenly; many copies of few words overflow into the
-            // plain word log)
-            const uint64_t rows_total = h->row_base + b->nrows;
-            uint64_t need = h->opt.region_cap ? h->opt.region_cap : (rows_total + rows_total / 4) / kWordSubs + 4096;
-            need = (need + 15) / 16 * 16;  // whole 128-byte lines
-            if (!h->distinct.wcursor.p) {
-                HIP_TRY(h, h->distinct.wcursor.ensure(kMaxDistinct * kWordSubs * kCursorStride));
-                HIP_TRY(h, hipMemsetAsync(h->distinct.wcursor.p, 0, kMaxDistinct * kWordSubs * kCursorStride * sizeof(unsigned long long), h->stream));
-            }
-            if (need > h->distinct.wregion_cap) {
-                const uint64_t ncap = (std::max<uint64_t>(need, h->distinct.wregion_cap * 2) + 15) / 16 * 16;
-                if (ncap >= 0xFFFFFF00ull) return fail(h, N1K_OOM, "COUNT(DISTINCT): more than 2^32 words per hash region");
-                HIP_TRY(h, hipStreamSynchronize(h->stream));
-                for (uint32_t a = 0; a < P.naggs; a++) {
-                    if (!P.aggs[a].distinct) continue;
-                    const uint32_t li = P.aggs[a].log_index;
-                    DevBuf<uint64_t> nb;
-                    HIP_TRY(h, nb.ensure(kWordSubs * ncap));
-                    if (h->distinct.wregion_cap && h->distinct.wregion_used)
-                        HIP_TRY(h, launch_regrow_regions(h->distinct.wregion[li].p, kWordSubs, h->distinct.wregion_cap, nb.p, ncap,
-                                                         h->distinct.wcursor.p + (size_t)li * kWordSubs * kCursorStride, h->stream));  // (clamps the cursors of regions that had overflowed)
-                    HIP_TRY(h, hipStreamSynchronize(h->stream));
-                    h->distinct.wregion[li] = std::move(nb);
-                }
-                h->distinct.wregion_cap = ncap;
-            }
-            uint32_t d = 0;
-            for (uint32_t a = 0; a < P.naggs; a++) {
-                if (!P.aggs[a].distinct) continue;
-                const uint32_t li = P.aggs[a].log_index;
-                L.region[d] = h->distinct.wregion[li].p;
-                L.region_cursor[d] = h->distinct.wcursor.p + (size_t)li * kWordSubs * kCursorStride;
-                L.over_word[d] = A.log_word[li];
-                L.log_key[d] = A.log_key[li];
-                L.log_val[d] = A.log_val[li];
-                L.log_cls[d] = A.log_cls[li];
-                L.log_index[d] = li;
-                d++;
-            }
-            L.region_cap = h->distinct.wregion_cap;
-            L.over_cursor = A.word_cursor;
-            L.over_hist = A.word_hist;
-            L.over_capacity = A.log_capacity;
-            L.log_cursor = A.log_cursor;
-            L.log_capacity = A.log_capacity;
-            L.nw_key_bits = h->distinct.nw_key_bits;
-            L.nw_val_bits = h->distinct.nw_val_bits;
-            L.dcache_slots = dcache_slots;
-            h->distinct.wregion_used = true;
-        }
-        hipEvent_t e0 = get_event(h), e1 = get_event(h);
-        if (e0) (void)hipEventRecord(e0, h->stream);
-        const uint64_t chunk = 1ull << 31;  // 32-bit row indices inside one launch
-        for (uint64_t off = 0; off < b->nrows; off += chunk) {
-            uint64_t n = std::min<uint64_t>(chunk, b->nrows - off);
-            F.row_base = h->row_base + off;
-            bool aligned = true;
-            for (uint32_t c = 0; c < F.ncols; c++) {
-                F.cols[c] = P.cols[c];
-                if (F.cols[c].tags) F.cols[c].tags += off;
-                if (F.cols[c].payload) F.cols[c].payload += off;
-                if (F.cols[c].codes) F.cols[c].codes += off;
-                aligned &= ((uintptr_t)F.cols[c].tags % 2 == 0) && ((uintptr_t)F.cols[c].payload % 16 == 0) &&
-                           ((uintptr_t)F.cols[c].codes % 8 == 0);
-            }
-            if (spec || jit) {
-                // WIDE launch over the even prefix (2 adjacent rows per lane and load), scalar launch for an odd last row
-                bool wide = aligned && h->opt.wide && n >= 2;
-                // (a row count that lives on the device may be odd: the kernel masks the last item's second row itself)
-                uint64_t n_main = wide && !h->push_nrows_dev && !h->push_nseg ? (n & ~1ull) : n;
-                F.nrows = (uint32_t)n_main;
-                uint64_t items = wide ? (n_main + 1) / 2 : n_main;
-                uint32_t rpl = wide ? 2 : 4;
-                uint64_t tiles = (items + (uint64_t)fblock * rpl - 1) / ((uint64_t)fblock * rpl);
-                if (ndist) tiles = (tiles + 3) / 4;  // a workgroup reserves chunks in every hash region: give it a few tiles to fill them
-                uint32_t g = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(fgrid, tiles));
-                F.slabs = nullptr;
-                if (use_slabs && g > 1) {
-                    HIP_TRY(h, h->groups.slabs.ensure((size_t)g * P.lds_words * F.lds_slots));
-                    HIP_TRY(h, h->groups.block_sel.ensure(g));
-                    F.slabs = h->groups.slabs.p;
-                    F.block_selected = h->groups.block_sel.p;
-                }
-                if (spec) HIP_TRY(h, spec->launch(P, F, h->groups.table, h->groups.counters.p + 1, g, fblock, wide, L, h->stream));
-                else HIP_TRY(h, jit_launch(jit, P, F, h->groups.table, h->groups.counters.p + 1, g, wide, L, ndist, h->stream));
-                if (F.slabs) HIP_TRY(h, launch_merge_slabs(P, F, h->groups.table, g, h->groups.counters.p + 1, h->stream, h->opt.merge_chunks));
-                F.slabs = nullptr;
-                if (n_main < n) {
-                    for (uint32_t c = 0; c < F.ncols; c++) {
-                        if (F.cols[c].tags) F.cols[c].tags += n_main;
-                        if (F.cols[c].payload) F.cols[c].payload += n_main;
-                        if (F.cols[c].codes) F.cols[c].codes += n_main;
-                    }
-                    F.nrows = (uint32_t)(n - n_main);
-                    F.row_base += n_main;
-                    if (spec) HIP_TRY(h, spec->launch(P, F, h->groups.table, h->groups.counters.p + 1, 1, fblock, false, L, h->stream));
-                    else HIP_TRY(h, jit_launch(jit, P, F, h->groups.table, h->groups.counters.p + 1, 1, false, L, ndist, h->stream));
-                }
-                continue;
-            }
-            F.nrows = (uint32_t)n;
-            uint64_t tiles = (n + (uint64_t)fblock * frpl - 1) / ((uint64_t)fblock * frpl);
-            uint32_t g = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(fgrid, tiles));
-            F.slabs = nullptr;
-            if (use_slabs && g > 1) {
-                HIP_TRY(h, h->groups.slabs.ensure((size_t)g * P.lds_words * F.lds_slots));
-                HIP_TRY(h, h->groups.block_sel.ensure(g));
-                F.slabs = h->groups.slabs.p;
-                F.block_selected = h->groups.block_sel.p;
-            }
-            HIP_TRY(h, launch_scan_fast(P, F, h->groups.table, h->groups.counters.p + 1, g, fblock, frpl, h->stream));
-            if (F.slabs) HIP_TRY(h, launch_merge_slabs(P, F, h->groups.table, g, h->groups.counters.p + 1, h->stream, h->opt.merge_chunks));
-            F.slabs = nullptr;
-        }
-        if (e1) (void)hipEventRecord(e1, h->stream);
-        h->timing.events.emplace_back(e0, e1);
-        h->timing.stats.agg_mode = F.hashed ? N1K_MODE_LDS_HASH : N1K_MODE_LDS_DIRECT;
-        return N1K_OK;
+        build = build && table_bytes <= 64 * 1024 && key_kinds_hashed == (F.hashed != 0);
+    } else if (use == ShapeUse::Partition) {
+        // what the staging needs in LDS (n1k_spec.h PartLds: 2048 rows x (9 B per TAGGED64 column, 4 B per DICT32 column, 1))
+        size_t lds = 2048 + 2048 + 4096;  // (+ the per-destination tables of PartLds)
+        for (uint32_t c = 0; c < F.ncols; c++) lds += 2048u * (F.cols[c].kind == COLK_DICT32 ? 4u : 9u);
+        build = build && lds + match_lds_bytes(F) <= 60 * 1024;
     }
-interpreter:
-    // DIRECT: every key is dictionary coded and the whole key domain fits the LDS table -> perfect hash
-    bool direct = h->opt.agg_mode != N1K_MODE_LDS_HASH;
-    uint64_t domain = 1;
-    for (uint32_t k = 0; k < P.nkeys && direct; k++) {
-        if (P.keys[k].mode != KEYM_DICT) direct = false;
-        uint64_t radix = (uint64_t)h->dict.size() + 2;
-        A.direct_stride[k] = (uint32_t)domain;
-        A.direct_radix[k] = (uint32_t)std::min<uint64_t>(radix, 0xFFFFFFFFull);
-        domain *= radix;
-        if (domain > max_slots) direct = false;
+    if (!build) return {};
+    const JitKernel* k = jit_get(g);
+    if (k->failed || !(use == ShapeUse::Scan ? k->wide : (use == ShapeUse::Records ? k->rec_wide : k->part_wide))) {
+        h->jit_log = k->log;
+        return {};
     }
-    uint32_t slots = direct ? (uint32_t)std::max<uint64_t>(domain, 2) : max_slots;
-    if (P.nkeys == 0) slots = 2;
-    A.lds_slots = slots;
-    A.lds_max_fill = std::max(1u, (uint32_t)((uint64_t)slots * 5 / 8));
+    return {nullptr, k, F.nderived ? 3u : 2u};
+}
+
+// What run_group_batch decided for a batch, before it allocates or launches anything.
+struct ScanChoice {
+    bool interpreter = true;  // the family: the interpreter, else `kernel` (prebuilt or built at run time), else the bounded-shape kernel
+    bool shaped = false;  // the plan is of the bounded shape: F, kernel and the LDS sums below are set
+    bool fuse = false;    // the kernel evaluates the arithmetic nodes in registers: no derived columns
+    ShapeKernel kernel;
+    FastArgs F;
+    uint32_t ndist = 0;   // DISTINCT aggregates ...
+    Program compact;      // ... and the program the specialised kernels run on then (compact LDS layout)
+    uint32_t fblock = 0, per_cu = 0, grid_cap = 0;
+    bool use_slabs = false;
+    uint32_t table_bytes = 0, scatter_bytes = 0, match_lds = 0, dcache_slots = 0, lds_total = 0;
+    // the interpreter
+    uint32_t max_slots = 0, slots = 0, block = 0, rpl = 0, direct_stride[kMaxKeys] = {}, direct_radix[kMaxKeys] = {};
+    bool direct = false;
+};
+
+// No allocation, no launch: the only side effects are shape_kernel's (a run-time build, h->jit_log).
+static ScanChoice choose_scan(n1k_handle* h, uint64_t nrows) {
+    const Program& P = h->prog;
+    ScanChoice c;
+    FastArgs& F = c.F;
+    c.block = h->opt.block ? h->opt.block : 1024;
+    c.rpl = c.block == 1024 ? h->opt.rows_per_lane : 4;
+    c.max_slots = (uint32_t)std::min<uint64_t>(h->opt.lds_bytes / (P.lds_words * 8), 1u << 15);
+    if (c.max_slots < 2) return c;
+    // DIRECT tables may take (almost) the whole 160 KiB LDS of a CU: occupancy is chosen from the table size
+    const uint32_t direct_max_slots = (uint32_t)std::min<uint64_t>((156u * 1024u) / (P.lds_words * 8), 1u << 15);
+    // Shapes with COUNT(DISTINCT): the specialised kernels keep nothing of a DISTINCT aggregate in the workgroup
+    // table (its member words go to the hash regions), so they run on a copy of the program with a compact LDS layout
+    for (uint32_t a = 0; a < P.naggs; a++) c.ndist += P.aggs[a].distinct ? 1u : 0u;
+    if (c.ndist) {
+        c.compact = P;
+        uint32_t w = 1;
+        for (uint32_t a = 0; a < c.compact.naggs; a++) {
+            AggSpec& ag = c.compact.aggs[a];
+            ag.lds_off = w;
+            if (ag.distinct) ag.lds_n = 0;
+            else w += (ag.kind == AGG_COUNT || ag.kind == AGG_COUNTN) ? 1u : (ag.kind == AGG_SUM ? kLdsWordsSum : (ag.kind == AGG_AVG ? kLdsWordsAvg : kWordsMinMax));
+        }
+        c.compact.lds_words = w;
+    }
+    const uint32_t ndist = c.ndist, lds_words = ndist ? c.compact.lds_words : P.lds_words;
+    if (h->opt.agg_mode != N1K_MODE_LDS_HASH) {
+        // Arithmetic nodes not materialised yet: first the shape that evaluates them in registers, which exists built at
+        // run time only.  Its table is bounded as the handle's program lays it out, compacted or not.  With no such kernel
+        // the nodes become derived columns, and the choice is made for the shape that reads them as inputs.
+        if (!h->derived_ready && h->opt.fuse_arith && build_fast_args(h, direct_max_slots, F, true)) {
+            c.kernel = shape_kernel(h, F, ShapeUse::Scan, nrows, (size_t)F.lds_slots * P.lds_words * 8);
+            c.fuse = c.shaped = (bool)c.kernel;
+        }
+        if (!c.fuse && (c.shaped = build_fast_args(h, direct_max_slots, F, false)))
+            c.kernel = shape_kernel(h, F, ShapeUse::Scan, nrows, (size_t)F.lds_slots * lds_words * 8);
+    }
+    // the bounded-shape kernel is DIRECT only, no DISTINCT, and reads its row count from its arguments
+    c.interpreter = !c.shaped || (!c.kernel && (F.hashed || ndist || h->push_nrows_dev || h->push_nseg));
+    if (c.interpreter) {
+        // DIRECT: every key is dictionary coded and the whole key domain fits the LDS table -> perfect hash
+        c.direct = h->opt.agg_mode != N1K_MODE_LDS_HASH;
+        uint64_t domain = 1;
+        for (uint32_t k = 0; k < P.nkeys && c.direct; k++) {
+            if (P.keys[k].mode != KEYM_DICT) c.direct = false;
+            uint64_t radix = (uint64_t)h->dict.size() + 2;
+            c.direct_stride[k] = (uint32_t)domain;
+            c.direct_radix[k] = (uint32_t)std::min<uint64_t>(radix, 0xFFFFFFFFull);
+            domain *= radix;
+            if (domain > c.max_slots) c.direct = false;
+        }
+        c.slots = c.direct ? (uint32_t)std::max<uint64_t>(domain, 2) : c.max_slots;
+        if (P.nkeys == 0) c.slots = 2;
+        return c;
+    }
+    c.table_bytes = F.lds_slots * lds_words * 8;
+    c.match_lds = match_lds_bytes(F);  // static LDS of the staged match table: part of every budget below
+    // the word scatter's LDS (per DISTINCT aggregate one ScatterLds<uint64_t, 512, 4>, n1k_scatter.h: 2048 staged words,
+    // counters, run starts) and, in what is left of the workgroup's share of the CU, its "already logged" caches
+    c.scatter_bytes = ndist * (2048u * 8u + 2u * 256u * 4u + 256u * 4u + 256u * 8u + 2048u) + (ndist ? 64u : 0u);
+    if (ndist) {
+        const uint32_t without = c.table_bytes + c.scatter_bytes + c.match_lds;
+        const uint32_t share = 160u * 1024u / std::max(1u, std::min(3u, 160u * 1024u / (without + 512u)));
+        for (uint32_t sl = 4096; sl >= 64; sl >>= 1)
+            if (without + ndist * sl * 8u + 512u <= share) { c.dcache_slots = sl; break; }
+    }
+    c.lds_total = c.table_bytes + c.scatter_bytes + ndist * c.dcache_slots * 8u + c.match_lds;
+    // workgroups per CU that fit: 512 threads x 3 (<= 48 KiB each), x 2 (<= 72 KiB), else 1024 threads x 1
+    c.fblock = h->opt.block == 1024 || h->opt.block == 512 ? h->opt.block : (c.table_bytes <= 72 * 1024 ? 512u : 1024u);
+    if (ndist) c.fblock = 512;
+    c.per_cu = c.fblock == 512 ? (c.lds_total <= 48 * 1024 ? 3u : (c.lds_total <= 72 * 1024 ? 2u : 1u))
+                               : (c.lds_total <= 72 * 1024 ? 2u : 1u);
+    if (ndist) c.per_cu = std::max(1u, std::min(3u, 160u * 1024u / (c.lds_total + 512u)));  // (two workgroups of 80 KiB fit a CU)
+    if (c.kernel.jit && c.fblock != 512) {  // run-time instantiations are built for 512-thread workgroups
+        c.fblock = 512;
+        c.per_cu = c.table_bytes + c.match_lds <= 48 * 1024 ? 3u : 2u;
+    }
+    c.grid_cap = h->opt.grid_blocks ? h->opt.grid_blocks : (uint32_t)(h->num_cus * c.per_cu);
+    // slabs + merge kernel pay off once the table is more than a few KiB
+    c.use_slabs = !F.hashed && (h->opt.slabs == 1 ? c.table_bytes >= 4096 : h->opt.slabs == 2);
+    return c;
+}
+
+// Rows [off, off + n) of the bound columns through the chosen kernel on program P: slabs for the grid, the launch, the
+// merge.  A specialised kernel takes its WIDE form (2 adjacent rows per lane and load) over the even prefix of aligned
+// columns, and an odd last row through a second, scalar launch.
+static n1k_status launch_chunk(n1k_handle* h, const ScanChoice& c, const Program& P, FastArgs& F, const WordLogArgs& L, uint64_t off, uint64_t n) {
+    unsigned long long* ngroups = h->groups.counters.p + 1;
+    auto launch = [&](uint32_t g, bool wide) {
+        if (c.kernel.spec) return c.kernel.spec->launch(P, F, h->groups.table, ngroups, g, c.fblock, wide, L, h->stream);
+        if (c.kernel.jit) return jit_launch(c.kernel.jit, P, F, h->groups.table, ngroups, g, wide, L, c.ndist, h->stream);
+        return launch_scan_fast(P, F, h->groups.table, ngroups, g, c.fblock, h->opt.rows_per_lane, h->stream);
+    };
+    F.row_base = h->row_base + off;
+    std::copy_n(P.cols, F.ncols, F.cols);
+    advance_cols(F.cols, F.ncols, off);
+    const bool wide = c.kernel && cols_wide_aligned(F.cols, F.ncols) && h->opt.wide && n >= 2;
+    // (a row count that lives on the device may be odd: the kernel masks the last item's second row itself)
+    const uint64_t n_main = wide && !h->push_nrows_dev && !h->push_nseg ? (n & ~1ull) : n;
+    F.nrows = (uint32_t)n_main;
+    const uint64_t items = wide ? (n_main + 1) / 2 : n_main;
+    const uint32_t rpl = !c.kernel ? h->opt.rows_per_lane : (wide ? 2 : 4);
+    uint64_t tiles = (items + (uint64_t)c.fblock * rpl - 1) / ((uint64_t)c.fblock * rpl);
+    if (c.ndist) tiles = (tiles + 3) / 4;  // a workgroup reserves chunks in every hash region: give it a few tiles to fill them
+    const uint32_t g = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(c.grid_cap, tiles));
+    if (c.use_slabs && g > 1) {  // (F.slabs is null here: build_fast_args, and below)
+        HIP_TRY(h, h->groups.slabs.ensure((size_t)g * P.lds_words * F.lds_slots));
+        HIP_TRY(h, h->groups.block_sel.ensure(g));
+        F.slabs = h->groups.slabs.p;
+        F.block_selected = h->groups.block_sel.p;
+    }
+    HIP_TRY(h, launch(g, wide));
+    if (F.slabs) HIP_TRY(h, launch_merge_slabs(P, F, h->groups.table, g, ngroups, h->stream, h->opt.merge_chunks));
+    F.slabs = nullptr;
+    if (n_main < n) {
+        advance_cols(F.cols, F.ncols, n_main);
+        F.nrows = (uint32_t)(n - n_main);
+        F.row_base += n_main;
+        HIP_TRY(h, launch(1, false));
+    }
+    return N1K_OK;
+}
+
+// The batch through the chosen specialised or bounded-shape kernel, in launches of at most 2^31 rows.
+static n1k_status run_shaped(n1k_handle* h, ScanChoice& c, const ScanArgs& A, uint64_t nrows) {
+    const Program& P = c.ndist ? c.compact : h->prog;
+    FastArgs& F = c.F;
+    F.err_flags = h->groups.errp;
+    F.rows_selected = h->groups.counters.p + 0;
+    F.nrows_dev = h->push_nrows_dev;
+    if (h->push_nseg > 1) {
+        if (h->push_nseg > kMaxSegments || nrows >= (1ull << 31)) return fail(h, N1K_INVALID, "segmented batch too large");
+        F.nseg = h->push_nseg;
+        F.seg_rows = (uint32_t)h->push_seg_rows;
+        F.seg_count_stride = kCursorStride;
+        F.seg_counts = h->push_seg_counts;
+    }
+    WordLogArgs L{};
+    if (c.ndist) {
+        n1k_status st = distinct_grow_regions(h, P, nrows, A, c.dcache_slots, L);
+        if (st != N1K_OK) return st;
+    }
+    hipEvent_t e0 = get_event(h), e1 = get_event(h);
+    if (e0) (void)hipEventRecord(e0, h->stream);
+    const uint64_t chunk = 1ull << 31;  // 32-bit row indices inside one launch
+    for (uint64_t off = 0; off < nrows; off += chunk) {
+        n1k_status st = launch_chunk(h, c, P, F, L, off, std::min<uint64_t>(chunk, nrows - off));
+        if (st != N1K_OK) return st;
+    }
+    if (e1) (void)hipEventRecord(e1, h->stream);
+    h->timing.events.emplace_back(e0, e1);
+    h->timing.stats.agg_mode = F.hashed ? N1K_MODE_LDS_HASH : N1K_MODE_LDS_DIRECT;
+    return N1K_OK;
+}
+
+// The batch through the interpreter kernel.
+static n1k_status run_interpreter(n1k_handle* h, const ScanChoice& c, ScanArgs& A, uint64_t nrows) {
+    const Program& P = h->prog;
+    memcpy(A.direct_stride, c.direct_stride, sizeof A.direct_stride);
+    memcpy(A.direct_radix, c.direct_radix, sizeof A.direct_radix);
+    A.lds_slots = c.slots;
+    A.lds_max_fill = std::max(1u, (uint32_t)((uint64_t)c.slots * 5 / 8));
     A.err_flags = h->groups.errp;
     A.rows_selected = h->groups.counters.p + 0;
-    uint64_t tile_rows = (uint64_t)block * rpl;
-    uint64_t ntiles = (b->nrows + tile_rows - 1) / tile_rows;
-    uint32_t per_cu = block == 1024 ? 1 : (block == 512 ? 2 : 4);
+    uint64_t tile_rows = (uint64_t)c.block * c.rpl;
+    uint64_t ntiles = (nrows + tile_rows - 1) / tile_rows;
+    uint32_t per_cu = c.block == 1024 ? 1 : (c.block == 512 ? 2 : 4);
     uint32_t grid = h->opt.grid_blocks ? h->opt.grid_blocks : (uint32_t)(h->num_cus * per_cu);
     grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(grid, ntiles));
     hipEvent_t e0 = get_event(h), e1 = get_event(h);
@@ -467,26 +381,45 @@ interpreter:
         // a segmented batch on the interpreter: one launch per segment, its row count read on the device
         Program Ps = P;
         for (uint32_t sg = 0; sg < h->push_nseg; sg++) {
-            const uint64_t off = (uint64_t)sg * h->push_seg_rows;
-            for (uint32_t c = 0; c < P.ncols; c++) {
-                Ps.cols[c] = P.cols[c];  // (derived columns too: they were evaluated over the whole capacity, row for row)
-                if (Ps.cols[c].tags) Ps.cols[c].tags += off;
-                if (Ps.cols[c].payload) Ps.cols[c].payload += off;
-                if (Ps.cols[c].codes) Ps.cols[c].codes += off;
-            }
+            std::copy_n(P.cols, P.ncols, Ps.cols);  // (derived columns too: they were evaluated over the whole capacity, row for row)
+            advance_cols(Ps.cols, P.ncols, (uint64_t)sg * h->push_seg_rows);
             ScanArgs As = A;
             As.nrows = h->push_seg_rows;
             As.nrows_dev = h->push_seg_counts + (size_t)sg * kCursorStride;
             const uint64_t nt = (h->push_seg_rows + tile_rows - 1) / tile_rows;
             const uint32_t g = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(grid, nt));
-            HIP_TRY(h, launch_scan_group(Ps, As, h->groups.table, h->groups.counters.p + 1, g, block, rpl, direct, h->stream));
+            HIP_TRY(h, launch_scan_group(Ps, As, h->groups.table, h->groups.counters.p + 1, g, c.block, c.rpl, c.direct, h->stream));
         }
     } else
-        HIP_TRY(h, launch_scan_group(P, A, h->groups.table, h->groups.counters.p + 1, grid, block, rpl, direct, h->stream));
+        HIP_TRY(h, launch_scan_group(P, A, h->groups.table, h->groups.counters.p + 1, grid, c.block, c.rpl, c.direct, h->stream));
     if (e1) (void)hipEventRecord(e1, h->stream);
     h->timing.events.emplace_back(e0, e1);
-    h->timing.stats.agg_mode = direct ? N1K_MODE_LDS_DIRECT : N1K_MODE_LDS_HASH;
+    h->timing.stats.agg_mode = c.direct ? N1K_MODE_LDS_DIRECT : N1K_MODE_LDS_HASH;
     return N1K_OK;
+}
+
+// One batch through Filter + InitialGroup: room in the table and the DISTINCT logs, the choice, derived columns unless the
+// chosen kernel evaluates the arithmetic nodes itself, the launches.
+n1k_status run_group_batch(n1k_handle* h, const n1k_batch* b) {
+    n1k_status st = ensure_table(h, b->nrows);
+    if (st != N1K_OK) return st;
+    ScanArgs A{};
+    A.nrows = b->nrows;
+    A.nrows_dev = h->push_nrows_dev;
+    A.row_base = h->row_base;
+    if (h->has_distinct) {
+        st = distinct_grow_logs(h, b->nrows, A);
+        if (st != N1K_OK) return st;
+    }
+    ScanChoice c = choose_scan(h, b->nrows);
+    if (c.max_slots < 2) return fail(h, N1K_UNSUPPORTED, "accumulator row too wide for LDS");
+    if (!c.fuse) {
+        st = materialize_derived(h, b);
+        if (st != N1K_OK) return st;
+        if (c.ndist) std::copy_n(h->prog.cols, h->prog.ncols, c.compact.cols);  // (copied before the derived columns were bound)
+    }
+    if (c.shaped) h->timing.stats.spec_kernel = c.kernel.stat;
+    return c.interpreter ? run_interpreter(h, c, A, b->nrows) : run_shaped(h, c, A, b->nrows);
 }
 
 // one comparison of a TAGGED64 column with a NUMBER constant, arrays aligned for two rows per load: the wide variant
@@ -647,11 +580,7 @@ n1k_status push_device(n1k_handle* h, const n1k_batch* b) {
     }
     auto view = [&](uint64_t off, uint64_t n, std::vector<n1k_col>& cols, n1k_batch& v) {
         cols.assign(b->cols, b->cols + b->ncols);
-        for (auto& c : cols) {
-            if (c.tags) c.tags += off;
-            if (c.payload) c.payload += off;
-            if (c.codes) c.codes += off;
-        }
+        advance_cols(cols.data(), b->ncols, off);
         v.nrows = n;
         v.ncols = b->ncols;
         v.cols = cols.data();

@@ -67,12 +67,12 @@ PRICE = D("price")
 SCAN_SHAPES = {
     # prebuilt Spec_gt_sum, DIRECT: 1002 slots x 4 LDS words (key + kLdsWordsSum) = 32 KB >= 4096: slabs on when automatic
     "direct": ("(50 < %s)" % PRICE, [D("cat")], ["sum(%s)" % PRICE], dict(k_cat=1000, zipf=True)),
-    # the same shape over 37 categories: 1.2 KB, slabs off when automatic (n1k_scan.cpp:272)
+    # the same shape over 37 categories: 1.2 KB, slabs off when automatic (choose_scan's use_slabs)
     "direct-small": ("(50 < %s)" % PRICE, [D("cat")], ["sum(%s)" % PRICE], dict(k_cat=37, zipf=True)),
     # prebuilt Spec_ik_sum, HASHED: user_id in [0, 100 000) gives ~63 k groups, more than the 2048 LDS slots
     "hashed": (None, [D("user_id")], ["sum(%s)" % PRICE], dict(k_cat=37, total_rows=1_000_000)),
     # no prebuilt kernel (built at run time); 1 + 4 + 4 LDS words per slot: 1024 bytes hold 14 slots, fewer than the 16
-    # build_fast_args needs (n1k_scan.cpp:78-79)
+    # build_fast_args needs of a hashed table
     "hashed-jit": (None, [D("user_id")], sorted(["avg(%s)" % PRICE, "max(%s)" % PRICE]), dict(k_cat=37, total_rows=1_000_000)),
     "direct-jit": ("(%s < 30)" % PRICE, [D("cat")], sorted(["count(*)", "min(%s)" % PRICE]), dict(k_cat=1000, zipf=True)),
 }
@@ -91,19 +91,19 @@ def _scan_cases():
         add(s, {}, mode[s], 1)
         for b in G["block"]:  # the interpreter at every workgroup size (tile block x rows per lane; 4 below 1024)
             add(s, {"fast": 0, "block": b}, mode[s], 0)
-        for b in (512, 1024):  # the specialised kernel's two sizes (256 is not one of them: auto, n1k_scan.cpp:264)
+        for b in (512, 1024):  # the specialised kernel's two sizes (256 is not one of them: auto, choose_scan's fblock)
             add(s, {"block": b}, mode[s], 1)
-        for r in G["rows_per_lane"]:  # rows per lane: the interpreter at 1024 threads (n1k_scan.cpp:205)
+        for r in G["rows_per_lane"]:  # rows per lane: the interpreter at 1024 threads (choose_scan's rpl)
             add(s, {"fast": 0, "block": 1024, "rows_per_lane": r}, mode[s], 0)
-        # grid_blocks: the grid itself, clipped to the tiles (n1k_scan.cpp:390, :485); 100 000 exceeds the 25 / 49 tiles
+        # grid_blocks: the grid itself, clipped to the tiles (launch_chunk, run_interpreter); 100 000 exceeds the 25 / 49 tiles
         for g in G["grid_blocks"]:
             add(s, {"grid_blocks": g}, mode[s], 1)
             add(s, {"fast": 0, "grid_blocks": g}, mode[s], 0)
-        for rep in G["rep_row"]:  # representative rows: the interpreter only (n1k_scan.cpp:29)
+        for rep in G["rep_row"]:  # representative rows: the interpreter only (build_fast_args refuses want_rep_row)
             add(s, {"rep_row": rep}, mode[s], 0 if rep else 1)
     for r in G["rows_per_lane"]:  # the bounded-shape kernel (spec off): tile 512 threads x rows per lane
         add("direct", {"spec": 0, "rows_per_lane": r}, DIRECT, 0)
-    for sl in G["slabs"]:  # 0 off, 1 from 4096 table bytes on, 2 always (n1k_scan.cpp:272)
+    for sl in G["slabs"]:  # 0 off, 1 from 4096 table bytes on, 2 always (option slabs, choose_scan's use_slabs)
         add("direct", {"slabs": sl}, DIRECT, 1)
         add("direct", {"spec": 0, "slabs": sl}, DIRECT, 0)
     add("direct-small", {"slabs": 2}, DIRECT, 1)  # forced where the automatic choice is off
@@ -114,11 +114,11 @@ def _scan_cases():
         # 32 .. 2048 slots of 32 bytes.  163840 is clamped to 64 KiB (n1k_set_option): it used to ask the prebuilt kernel for
         # a 160 KiB table on top of its own LDS, and the launch failed
         add("hashed", {"lds_bytes": lb}, HASH, 1)
-        # 1024: 14 slots of 72 bytes, the interpreter (n1k_scan.cpp:78-79)
+        # 1024: 14 slots of 72 bytes, the interpreter (build_fast_args: fewer than 16 slots)
         add("hashed-jit", {"jit": 2, "lds_bytes": lb}, HASH, 0 if lb == 1024 else 2)
         # the interpreter's DIRECT table takes 1002 x 32 bytes: below that the key domain does not fit, HASHED
         add("direct", {"fast": 0, "lds_bytes": lb}, DIRECT if lb >= 1002 * 32 else HASH, 0)
-    for jm in G["jit_min_rows"]:  # jit=1: built at run time from jit_min_rows rows on (n1k_scan.cpp:285)
+    for jm in G["jit_min_rows"]:  # jit=1: built at run time from jit_min_rows rows on (shape_kernel)
         add("direct-jit", {"jit": 1, "jit_min_rows": jm}, DIRECT, 2 if jm <= N_SCAN else 0)
         add("hashed-jit", {"jit": 1, "jit_min_rows": jm}, HASH, 2 if jm <= N_SCAN else 0)
     return cases
@@ -219,7 +219,7 @@ def test_scan_tails_unaligned_columns(geom):
 
 
 # Filter-only plans: here grid_blocks is a factor per CU, not a grid — the one-comparison kernel runs
-# min(tiles, CUs x grid_blocks) workgroups of 8192-row tiles (n1k_scan.cpp:533).  At 2.2 M rows there are 269 tiles: 1 gives
+# min(tiles, CUs x grid_blocks) workgroups of 8192-row tiles (filter_stream_grid).  At 2.2 M rows there are 269 tiles: 1 gives
 # 256 workgroups where the default 5 gives 269; 3 and 100 000 are clipped to the tiles.
 @pytest.mark.parametrize("gb", G["grid_blocks"])
 def test_filter_only_grid_blocks_is_per_cu(gb):

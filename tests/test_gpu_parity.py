@@ -363,6 +363,29 @@ def test_arithmetic_fused_into_the_runtime_built_scan(case, resident):
     assert st["spec_kernel"] != 3
 
 
+# (key domain, stats.spec_kernel).  The plan's LDS slot is 7 words as the handle lays it out (key, 3 of the DISTINCT
+# aggregate, 3 of the SUM) and 4 as the specialised kernels do (nothing of a DISTINCT aggregate in LDS); a table has one slot
+# per dictionary code + 2, and a run-time-built kernel takes 64 KiB of table.  12 categories fit either way; 1500 make 82 KiB
+# in the handle's layout and 47 KiB compacted, and arithmetic is fused only where the handle's layout fits.
+# The expected kernels are what the commit before choose_scan reported for this same test.
+FUSED_DISTINCT = [(12, 3), (1500, 0)]
+
+
+@pytest.mark.parametrize("k_cat,spec_kernel", FUSED_DISTINCT, ids=["table-fits", "only-compacted-fits"])
+def test_arithmetic_fused_beside_count_distinct(k_cat, spec_kernel):
+    """Arithmetic nodes and COUNT(DISTINCT column) in one plan: the choice between arithmetic in registers and derived
+    columns is bounded by the table of the handle's program, the launch by the compacted one.  4097 rows in two batches: one
+    row past two 2048-row tiles (the WIDE form's odd last row), and the DISTINCT logs grow between the batches."""
+    cond = "(100 < (%s + %s))" % (D("price"), D("region_id"))
+    aggs = sorted(["count(distinct %s)" % D("region_id"), "sum((%s * %s))" % (D("price"), D("region_id"))])
+    t = n1o.synth_table(4097, k_cat=k_cat)
+    ora = n1o.run(t, cond, [D("cat")], aggs)
+    gpu, st = pu.run_gpu(t, cond, [D("cat")], aggs, batches=2, jit=2)
+    print("k_cat %d: spec_kernel %d agg_mode %d" % (k_cat, st["spec_kernel"], st["agg_mode"]))
+    pu.assert_same_groups(gpu, ora, aggs=aggs)
+    assert st["spec_kernel"] == spec_kernel, st
+
+
 @pytest.mark.parametrize("opts", [{}, {"jit": 2}], ids=["derived-columns", "fused"])
 def test_int64_multiplication_overflow_corners(opts):
     """intValue.Mult (value/integer.go:318-329) keeps the int64 when `x == 0 || rv / x == y`, else multiplies as floats;
