@@ -41,8 +41,8 @@ n1k_status distinct_grow_logs(n1k_handle* h, uint64_t nrows, ScanArgs& A) {
         A.log_cls[d] = h->distinct.log_cls[d].p;
         A.log_word[d] = h->distinct.words[d] ? h->distinct.log_word[d].p : nullptr;
     }
-    A.log_cursor = h->groups.counters.p + 8;
-    A.word_cursor = h->groups.counters.p + 16;
+    A.log_cursor = h->groups.counters.p + CTR_PAIR_LOG_CURSORS;
+    A.word_cursor = h->groups.counters.p + CTR_WORD_LOG_CURSORS;
     A.log_capacity = h->distinct.log_capacity;
     A.nw_key_bits = h->distinct.nw_key_bits;
     A.nw_val_bits = h->distinct.nw_val_bits;
@@ -179,7 +179,7 @@ n1k_status distinct_words_finish(n1k_handle* h, const AggSpec& ag, uint64_t nwor
         bin_start = R.out_start;
         nbins *= 256;
     }
-    uint32_t* d_overflow = (uint32_t*)(h->groups.counters.p + 24);
+    uint32_t* d_overflow = (uint32_t*)(h->groups.counters.p + CTR_EXACT_OVERFLOW);
     HIP_TRY(h, hipMemsetAsync(h->distinct.dcounts.p, 0, (h->groups.table.capacity + 2) * sizeof(unsigned long long), h->stream));
     HIP_TRY(h, hipMemsetAsync(d_overflow, 0, 8, h->stream));
     DedupeArgs D{};
@@ -225,7 +225,7 @@ n1k_status distinct_regions_finish(n1k_handle* h, const AggSpec& ag, uint64_t no
     const uint32_t set_slots = h->opt.distinct_set_slots;
     const uint64_t per_bin = std::max<uint64_t>((uint64_t)set_slots * h->opt.distinct_fill_pct / 100, 16);
     const bool exact = force_exact || nover > 0 || h->opt.distinct_levels == 0;
-    uint32_t* d_overflow = (uint32_t*)(h->groups.counters.p + 20);  // [0] an LDS set overflowed, [1] a bin of the second pass
+    uint32_t* d_overflow = (uint32_t*)(h->groups.counters.p + CTR_OPTIMISTIC_OVERFLOW);  // [0] an LDS set overflowed, [1] a bin of the second pass
     if (!exact) {
         // Optimistic: the member counts are only added to the groups when neither flag came up (the kernel checks), and
         // n1k_finish reads the flags together with the results (*deferred).  The rows pushed bound the words.

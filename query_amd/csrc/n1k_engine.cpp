@@ -380,7 +380,7 @@ n1k_status ensure_device(n1k_handle* h) {
         h->own_stream = true;
     }
     HIP_TRY(h, h->groups.counters.ensure(kCounters));
-    h->groups.errp = (uint32_t*)(h->groups.counters.p + 12);
+    h->groups.errp = (uint32_t*)(h->groups.counters.p + CTR_ERR_FLAGS);
     HIP_TRY(h, hipMemsetAsync(h->groups.counters.p, 0, kCounters * sizeof(unsigned long long), h->stream));
     h->device_ready = true;
     return N1K_OK;
@@ -439,7 +439,7 @@ n1k_status fix_layout(n1k_handle* h, const n1k_batch* b) {
     // value tables for the numbers a TAGGED field cannot hold itself (n1k_device.h: wide_code)
     P.wide_int = P.wide_flt = nullptr;
     P.wide_bits = 0;
-    P.wide_count = h->groups.counters.p + 13;
+    P.wide_count = h->groups.counters.p + CTR_WIDE_VALUES;
     if (n_tag && h->opt.wide_values) {
         uint32_t wb = 4;
         while ((1ull << wb) < h->opt.wide_values * 2 && wb < 30) wb++;
@@ -481,6 +481,23 @@ n1k_status alloc_table(n1k_handle* h, uint64_t capacity, GlobalTable& t, DevBuf<
     return N1K_OK;
 }
 
+// The table with at least `cap` slots: allocated if there is none, else every occupied slot rehashed into a bigger one (keys
+// keep their packed form); the old buffers are released once the rehash is behind the stream.
+static n1k_status grow_table(n1k_handle* h, uint64_t cap) {
+    if (cap <= h->groups.table.capacity) return N1K_OK;
+    if (!h->groups.table.capacity) return alloc_table(h, cap, h->groups.table, h->groups.keys, h->groups.acc, h->groups.rep);
+    GlobalTable nt{};
+    DevBuf<uint64_t> nk, na, nr;
+    ST_TRY(alloc_table(h, cap, nt, nk, na, nr));
+    HIP_TRY(h, launch_rehash(h->prog, h->groups.table, nt, h->groups.errp, h->groups.counters.p + CTR_REHASH_SCRATCH, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    h->groups.keys = std::move(nk);
+    h->groups.acc = std::move(na);
+    h->groups.rep = std::move(nr);
+    h->groups.table = nt;
+    return N1K_OK;
+}
+
 // Make sure the global table can take `incoming_rows` more rows worth of new groups (bounded by max_groups).
 n1k_status ensure_table(n1k_handle* h, uint64_t incoming_rows) {
     // groups <= rows pushed so far: an upper bound that needs no device round trip
@@ -496,41 +513,14 @@ n1k_status ensure_table(n1k_handle* h, uint64_t incoming_rows) {
         }
         if (all_dict && dom < (long double)want_groups) want_groups = (uint64_t)dom;
     }
-    uint64_t cap = next_pow2(std::max<uint64_t>(want_groups * 2, 1024));
-    if (cap <= h->groups.table.capacity) return N1K_OK;
-    if (!h->groups.table.capacity) return alloc_table(h, cap, h->groups.table, h->groups.keys, h->groups.acc, h->groups.rep);
-    // grow: rehash every occupied slot into a bigger table (keys keep their packed form)
-    GlobalTable nt{};
-    DevBuf<uint64_t> nk, na, nr;
-    n1k_status st = alloc_table(h, cap, nt, nk, na, nr);
-    if (st != N1K_OK) return st;
-    HIP_TRY(h, launch_rehash(h->prog, h->groups.table, nt, h->groups.errp, h->groups.counters.p + 4, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    h->groups.keys = std::move(nk);
-    h->groups.acc = std::move(na);
-    h->groups.rep = std::move(nr);
-    h->groups.table = nt;
-    return N1K_OK;
+    return grow_table(h, next_pow2(std::max<uint64_t>(want_groups * 2, 1024)));
 }
 
 // the same for a known number of groups (the partitioned path counts its groups before it inserts them)
 n1k_status ensure_table_groups(n1k_handle* h, uint64_t groups) {
     if (groups > h->opt.max_groups)
         return fail(h, N1K_OOM, "group table capacity exceeded: raise the max_groups option (now %llu)", (unsigned long long)h->opt.max_groups);
-    uint64_t cap = next_pow2(std::max<uint64_t>(groups * 2, 1024));
-    if (cap <= h->groups.table.capacity) return N1K_OK;
-    if (!h->groups.table.capacity) return alloc_table(h, cap, h->groups.table, h->groups.keys, h->groups.acc, h->groups.rep);
-    GlobalTable nt{};
-    DevBuf<uint64_t> nk, na, nr;
-    n1k_status st = alloc_table(h, cap, nt, nk, na, nr);
-    if (st != N1K_OK) return st;
-    HIP_TRY(h, launch_rehash(h->prog, h->groups.table, nt, h->groups.errp, h->groups.counters.p + 4, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    h->groups.keys = std::move(nk);
-    h->groups.acc = std::move(na);
-    h->groups.rep = std::move(nr);
-    h->groups.table = nt;
-    return N1K_OK;
+    return grow_table(h, next_pow2(std::max<uint64_t>(groups * 2, 1024)));
 }
 
 n1k_status ensure_pinned_counters(n1k_handle* h) {
@@ -1099,10 +1089,10 @@ n1k_status n1k_sync(n1k_handle* h) {
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     drain_events(h);
     if (h->plan.has_group && !h->device_clean) {  // (clean: the query was finished and its counters zeroed behind the result)
-        h->timing.stats.rows_selected = counters[0];
-        h->timing.stats.groups_out = h->part.pending.count ? h->part.pending.count : counters[1];  // groups so far (in the table, or in the kept region)
+        h->timing.stats.rows_selected = counters[CTR_ROWS_SELECTED];
+        h->timing.stats.groups_out = h->part.pending.count ? h->part.pending.count : counters[CTR_GROUPS];  // groups so far (in the table, or in the kept region)
     }
-    if (!h->device_clean) h->timing.stats.wide_key_values = counters[13];
+    if (!h->device_clean) h->timing.stats.wide_key_values = counters[CTR_WIDE_VALUES];
     return N1K_OK;
     });
 }

@@ -124,6 +124,9 @@ n1k_status fail(n1k_handle* h, n1k_status st, const char* fmt, ...);
                         hipGetErrorString(_e));                                                           \
     } while (0)
 
+// the same for a callee that has reported its failure itself
+#define ST_TRY(expr) do { n1k_status _st = (expr); if (_st != N1K_OK) return _st; } while (0)
+
 constexpr uint32_t kPinScratch = 16;
 constexpr uint64_t kWordSubs = 256ull * kRecSubs;  // sub-regions of a DISTINCT aggregate's member words
 
@@ -176,15 +179,42 @@ struct Options {
 };
 
 // ---- n1k_engine.cpp: plan binding, device and table management
+// The words of GroupTable::counters, on the device and in their host copies.  Device code is handed pointers to single words
+// and fixes only the distance from the error flags to the peer status (kPeerStatusFromErr).
+enum Counter : uint32_t {
+    CTR_ROWS_SELECTED = 0,
+    CTR_GROUPS = 1,              // groups in the table
+    CTR_OUT_COUNT = 2,           // FinalGroup's output position (Results::out_count_dirty)
+    CTR_FILTER_TOTAL = 3,        // survivors of a Filter-only batch
+    CTR_REHASH_SCRATCH = 4,
+    CTR_DISTINCT_REGION_WORDS = 5,  // K6: set-table words the layout kernel asks for
+    CTR_PAIR_LOG_CURSORS = 8,    // + log_index (kMaxDistinct words): the (key, value, class) pair logs
+    CTR_ERR_FLAGS = 12,          // ERR_* (n1k_types.h), low 32 bits: GroupTable::errp
+    CTR_WIDE_VALUES = 13,        // distinct wide key values met so far (Program::wide_count)
+    CTR_WORD_LOG_CURSORS = 16,   // + log_index (kMaxDistinct words): the COUNT(DISTINCT) member-word logs
+    // two 32-bit overflow flags of an optimistic path ([0] a hash region / an LDS set, [1] a bin).  Two users: the records front
+    // end of the partitioned GROUP BY (run_group_records) and the optimistic COUNT(DISTINCT) sets (distinct_regions_finish).
+    // They never meet in one query: partition_eligible refuses plans with DISTINCT aggregates.
+    CTR_OPTIMISTIC_OVERFLOW = 20,
+    CTR_PART_RECORDS = 21,       // records of the partitioned path
+    CTR_SINGLETONS = 22,         // ... its singleton partial groups
+    CTR_EXACT_OVERFLOW = 24,     // COUNT(DISTINCT) exact path: an LDS set overflowed
+    CTR_SAVED_ROWS_SELECTED = 25,  // CTR_ROWS_SELECTED before the optimistic records path, to undo it
+    CTR_REGION_GROUPS = 26,      // ... its region's group count, copied beside the others for the host
+    CTR_PEER_STATUS = 27         // the n1k_status a peer's verdict carried (ERR_PEER_FAILED)
+};
+static_assert(CTR_ERR_FLAGS + kPeerStatusFromErr == CTR_PEER_STATUS, "the verdict kernel writes the peer status this far behind the flags");
+static_assert(CTR_PEER_STATUS < kCounters, "every counter word lies inside the buffer (CTR_PEER_STATUS is the last)");
+static_assert(CTR_PAIR_LOG_CURSORS + kMaxDistinct <= CTR_ERR_FLAGS && CTR_WORD_LOG_CURSORS + kMaxDistinct <= CTR_OPTIMISTIC_OVERFLOW, "cursor words overlap their neighbours");
+
 // The group table and the device words every stage reports through.
 struct GroupTable {
     GlobalTable table{};
-    DevBuf<uint64_t> keys, acc, rep;        // (n1k_engine.cpp alone: alloc_table, the rehash of ensure_table)
+    DevBuf<uint64_t> keys, acc, rep;        // (n1k_engine.cpp alone: alloc_table, grow_table)
     DevBuf<uint64_t> slabs;                 // (n1k_scan.cpp)
     DevBuf<unsigned long long> block_sel;   // (n1k_scan.cpp)
-    uint32_t* errp = nullptr;  // lives inside counters ([12]) so one copy reads counters and flags
-    DevBuf<unsigned long long> counters;  // [0] rows_selected [1] ngroups [2] out_count [3] filter total [4] rehash scratch
-                                          // [5] distinct region words [8..11] pair-log cursors
+    uint32_t* errp = nullptr;  // lives inside counters (CTR_ERR_FLAGS) so one copy reads counters and flags
+    DevBuf<unsigned long long> counters;  // kCounters words, named by Counter (above)
     DevBuf<uint64_t> wide_int, wide_flt;  // the wide key value tables, Options::wide_values entries (n1k_engine.cpp alone)
     uint64_t merged_bound = 0;  // groups that may have arrived through merges (bounds the table like rows do)
 };
@@ -398,6 +428,8 @@ n1k_status having_groups(n1k_handle* h, uint64_t& ng);
 n1k_status project_groups(n1k_handle* h, uint64_t ng);
 n1k_status order_groups(n1k_handle* h, uint64_t& ng);
 n1k_status array_agg_groups(n1k_handle* h, uint64_t ng, const unsigned long long* counters);
+// the ng groups of h->res (and the projection of h->tail) into the caller's n1k_result; partials only where FinalGroup made them
+void publish_result(n1k_handle* h, uint64_t ng, bool partials, n1k_result* out);
 
 }  // namespace n1k_eng
 

@@ -159,8 +159,8 @@ n1k_status n1k_export_partials_device(n1k_handle* h, uint32_t nparts, uint64_t c
     uint32_t err_flags = 0;
     unsigned long long sel = 0, wide = 0;
     HIP_TRY(h, hipMemcpyAsync(&err_flags, h->groups.errp, 4, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(&sel, h->groups.counters.p, sizeof sel, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(&wide, h->groups.counters.p + 13, sizeof wide, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(&sel, h->groups.counters.p + CTR_ROWS_SELECTED, sizeof sel, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(&wide, h->groups.counters.p + CTR_WIDE_VALUES, sizeof wide, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     h->timing.stats.rows_selected = sel;
     h->timing.stats.wide_key_values = wide;
@@ -198,7 +198,7 @@ n1k_status n1k_merge_partials_device(n1k_handle* h, uint32_t nregions, uint64_t 
     if (st != N1K_OK) return st;
     uint64_t region_words = 2 + capacity_groups * (1 + (uint64_t)h->prog.glob_words);
     HIP_TRY(h, launch_merge_partials(h->prog, h->groups.table, nregions, capacity_groups, (const uint64_t*)in, region_words,
-                                     h->groups.errp, h->groups.counters.p + 1, h->stream));
+                                     h->groups.errp, h->groups.counters.p + CTR_GROUPS, h->stream));
     h->groups.merged_bound += (uint64_t)nregions * capacity_groups;
     return N1K_OK;
     });
@@ -212,7 +212,7 @@ n1k_status n1k_export_groups(n1k_handle* h, const void** blob, size_t* len) {
     st = flush_pending(h);
     if (st != N1K_OK) return st;
     unsigned long long ng = 0;
-    HIP_TRY(h, hipMemcpyAsync(&ng, h->groups.counters.p + 1, sizeof ng, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(&ng, h->groups.counters.p + CTR_GROUPS, sizeof ng, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     uint64_t cap = std::max<uint64_t>(ng, 1);
     uint64_t bytes = n1k_partial_region_bytes(h, cap);

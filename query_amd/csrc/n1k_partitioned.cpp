@@ -40,13 +40,13 @@ bool small_key_domain(const n1k_handle* h) {
 n1k_status flush_pending(n1k_handle* h) {
     if (!h->part.pending.count) return N1K_OK;
     unsigned long long have = 0;
-    HIP_TRY(h, hipMemcpyAsync(&have, h->groups.counters.p + 1, sizeof have, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(&have, h->groups.counters.p + CTR_GROUPS, sizeof have, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     n1k_status st = ensure_table_groups(h, have + h->part.pending.count);
     if (st != N1K_OK) return st;
     const uint64_t region_words = 2 + h->part.pending.cap * (1 + (uint64_t)h->prog.glob_words);
     HIP_TRY(h, launch_merge_partials(h->prog, h->groups.table, 1, h->part.pending.cap, h->part.emit.p, region_words, h->groups.errp,
-                                     h->groups.counters.p + 1, h->stream, h->part.pending.count, true));
+                                     h->groups.counters.p + CTR_GROUPS, h->stream, h->part.pending.count, true));
     h->part.pending.count = 0;
     return N1K_OK;
 }
@@ -89,7 +89,7 @@ n1k_status run_group_partitioned(n1k_handle* h, const n1k_batch* b, const Partit
     hipEvent_t e0 = get_event(h), e1 = get_event(h);
     if (e0) (void)hipEventRecord(e0, h->stream);
     // (1) Filter + key + operands -> records
-    unsigned long long* d_nrec = h->groups.counters.p + 21;
+    unsigned long long* d_nrec = h->groups.counters.p + CTR_PART_RECORDS;
     HIP_TRY(h, hipMemsetAsync(d_nrec, 0, sizeof(unsigned long long), h->stream));
     ProjectArgs A{};
     A.nrows = n;
@@ -111,7 +111,7 @@ n1k_status run_group_partitioned(n1k_handle* h, const n1k_batch* b, const Partit
     HIP_TRY(h, hipMemcpyAsync(&nrec, d_nrec, sizeof nrec, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     nrec = std::min<unsigned long long>(nrec, n);
-    HIP_TRY(h, launch_add_counter(h->groups.counters.p + 0, nrec, h->stream));  // rows_selected
+    HIP_TRY(h, launch_add_counter(h->groups.counters.p + CTR_ROWS_SELECTED, nrec, h->stream));
     if (nrec) {
         const uint64_t seg0[2] = {0, nrec};
         HIP_TRY(h, hipMemcpyAsync(h->distinct.seg[0].p, seg0, sizeof seg0, hipMemcpyHostToDevice, h->stream));
@@ -167,17 +167,17 @@ n1k_status run_group_partitioned(n1k_handle* h, const n1k_batch* b, const Partit
         HIP_TRY(h, hipMemsetAsync(h->part.emit.p, 0, 16, h->stream));
         B.emit = h->part.emit.p;
         B.emit_cap = ecap;
-        B.emit_singletons = h->groups.counters.p + 22;
-        HIP_TRY(h, hipMemsetAsync(h->groups.counters.p + 22, 0, sizeof(unsigned long long), h->stream));
+        B.emit_singletons = h->groups.counters.p + CTR_SINGLETONS;
+        HIP_TRY(h, hipMemsetAsync(h->groups.counters.p + CTR_SINGLETONS, 0, sizeof(unsigned long long), h->stream));
         const size_t shmem = (size_t)bslots * P.lds_words * 8 + 1024;
         const uint32_t per_cu = (uint32_t)std::max<size_t>(1, std::min<size_t>(4, (160 * 1024) / shmem));
         uint32_t grid = (uint32_t)std::min<uint64_t>(nbins, (uint64_t)h->num_cus * per_cu);
-        HIP_TRY(h, launch_agg_bins(P, B, h->groups.table, h->groups.counters.p + 1, grid, h->stream));
+        HIP_TRY(h, launch_agg_bins(P, B, h->groups.table, h->groups.counters.p + CTR_GROUPS, grid, h->stream));
         // how many partial groups, how many groups already: the table grows to hold both, then the merge
         unsigned long long emitted = 0, have = 0, singletons = 0;
-        HIP_TRY(h, hipMemcpyAsync(&singletons, h->groups.counters.p + 22, sizeof singletons, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(&singletons, h->groups.counters.p + CTR_SINGLETONS, sizeof singletons, hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(h, hipMemcpyAsync(&emitted, h->part.emit.p, sizeof emitted, hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(h, hipMemcpyAsync(&have, h->groups.counters.p + 1, sizeof have, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(&have, h->groups.counters.p + CTR_GROUPS, sizeof have, hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(h, hipStreamSynchronize(h->stream));
         emitted = std::min<unsigned long long>(emitted, ecap);
         if (may_keep_region && have == 0 && singletons == 0) {
@@ -193,7 +193,7 @@ n1k_status run_group_partitioned(n1k_handle* h, const n1k_batch* b, const Partit
         st = ensure_table_groups(h, have + emitted);
         if (st != N1K_OK) return st;
         // every key of the region is unique unless rows left the bins on their own: new groups are then plain copies
-        HIP_TRY(h, launch_merge_partials(P, h->groups.table, 1, ecap, h->part.emit.p, region_words, h->groups.errp, h->groups.counters.p + 1,
+        HIP_TRY(h, launch_merge_partials(P, h->groups.table, 1, ecap, h->part.emit.p, region_words, h->groups.errp, h->groups.counters.p + CTR_GROUPS,
                                          h->stream, emitted, singletons == 0));
     }
     if (e1) (void)hipEventRecord(e1, h->stream);
@@ -247,19 +247,19 @@ n1k_status run_group_records(n1k_handle* h, const n1k_batch* b, const PartitionP
     HIP_TRY(h, h->part.rcursor.ensure(nsub * kCursorStride));
     HIP_TRY(h, h->part.rbins.ensure(2 * nbins * bin_cap));
     HIP_TRY(h, h->distinct.cursor.ensure(65536));
-    uint32_t* d_flags = (uint32_t*)(h->groups.counters.p + 20);  // [0] a hash region overflowed, [1] a bin
+    uint32_t* d_flags = (uint32_t*)(h->groups.counters.p + CTR_OPTIMISTIC_OVERFLOW);  // [0] a hash region overflowed, [1] a bin
     hipEvent_t e0 = get_event(h), e1 = get_event(h);
     if (e0) (void)hipEventRecord(e0, h->stream);
     HIP_TRY(h, hipMemsetAsync(h->part.rcursor.p, 0, nsub * kCursorStride * sizeof(unsigned long long), h->stream));
     HIP_TRY(h, hipMemsetAsync(d_flags, 0, 8, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(h->groups.counters.p + 25, h->groups.counters.p + 0, 8, hipMemcpyDeviceToDevice, h->stream));  // rows_selected, to undo
+    HIP_TRY(h, hipMemcpyAsync(h->groups.counters.p + CTR_SAVED_ROWS_SELECTED, h->groups.counters.p + CTR_ROWS_SELECTED, 8, hipMemcpyDeviceToDevice, h->stream));  // rows_selected, to undo
     // (1) Filter + packed key + operand -> records in the hash regions
     std::copy_n(P.cols, P.ncols, F.cols);
     const bool wide = cols_wide_aligned(F.cols, P.ncols) && h->opt.wide && n >= 2;
     F.nrows = (uint32_t)n;
     F.row_base = h->row_base;
     F.err_flags = h->groups.errp;
-    F.rows_selected = h->groups.counters.p + 0;
+    F.rows_selected = h->groups.counters.p + CTR_ROWS_SELECTED;
     WordLogArgs L;
     memset(&L, 0, sizeof L);
     L.region[0] = h->part.rregion.p;
@@ -307,8 +307,8 @@ n1k_status run_group_records(n1k_handle* h, const n1k_batch* b, const PartitionP
     HIP_TRY(h, hipMemsetAsync(h->part.emit.p, 0, 16, h->stream));
     B.emit = h->part.emit.p;
     B.emit_cap = ecap;
-    B.emit_singletons = h->groups.counters.p + 22;
-    HIP_TRY(h, hipMemsetAsync(h->groups.counters.p + 22, 0, sizeof(unsigned long long), h->stream));
+    B.emit_singletons = h->groups.counters.p + CTR_SINGLETONS;
+    HIP_TRY(h, hipMemsetAsync(h->groups.counters.p + CTR_SINGLETONS, 0, sizeof(unsigned long long), h->stream));
     {
         const uint32_t block = h->opt.rec_block ? h->opt.rec_block : 256u;
         const size_t shmem = agg_bins16_lds_bytes(P, slots) + 1024;
@@ -317,20 +317,17 @@ n1k_status run_group_records(n1k_handle* h, const n1k_batch* b, const PartitionP
         HIP_TRY(h, launch_agg_bins16(P, B, bgrid, block, h->opt.rec_unroll ? h->opt.rec_unroll : 2u /* (2 records per thread and chunk: 554-586 us against 566-589 with 4, three boxes) */, h->stream, h->opt.agg_spec != 0));
     }
     // one copy of the counters into pinned memory (the region's group count joins them first): one host round trip
-    {
-        n1k_status pst = ensure_pinned_counters(h);
-        if (pst != N1K_OK) return pst;
-    }
-    HIP_TRY(h, hipMemcpyAsync(h->groups.counters.p + 26, h->part.emit.p, 8, hipMemcpyDeviceToDevice, h->stream));
+    ST_TRY(ensure_pinned_counters(h));
+    HIP_TRY(h, hipMemcpyAsync(h->groups.counters.p + CTR_REGION_GROUPS, h->part.emit.p, 8, hipMemcpyDeviceToDevice, h->stream));
     HIP_TRY(h, hipMemcpyAsync(h->res.pin_counters.p, h->groups.counters.p, kCounters * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    unsigned long long emitted = h->res.pin_counters.p[26];
-    const unsigned long long have = h->res.pin_counters.p[1], singletons = h->res.pin_counters.p[22];
+    unsigned long long emitted = h->res.pin_counters.p[CTR_REGION_GROUPS];
+    const unsigned long long have = h->res.pin_counters.p[CTR_GROUPS], singletons = h->res.pin_counters.p[CTR_SINGLETONS];
     uint32_t flags[2];
-    memcpy(flags, &h->res.pin_counters.p[20], 8);
+    memcpy(flags, &h->res.pin_counters.p[CTR_OPTIMISTIC_OVERFLOW], 8);
     if (flags[0] | flags[1]) {
         // a region or a bin overflowed: nothing was merged anywhere yet — forget the records and the survivor count
-        HIP_TRY(h, hipMemcpyAsync(h->groups.counters.p + 0, h->groups.counters.p + 25, 8, hipMemcpyDeviceToDevice, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(h->groups.counters.p + CTR_ROWS_SELECTED, h->groups.counters.p + CTR_SAVED_ROWS_SELECTED, 8, hipMemcpyDeviceToDevice, h->stream));
         if (e0) h->timing.event_pool.push_back(e0);
         if (e1) h->timing.event_pool.push_back(e1);
         return N1K_OK;
@@ -348,7 +345,7 @@ n1k_status run_group_records(n1k_handle* h, const n1k_batch* b, const PartitionP
     }
     st = ensure_table_groups(h, have + emitted);
     if (st != N1K_OK) return st;
-    HIP_TRY(h, launch_merge_partials(P, h->groups.table, 1, ecap, h->part.emit.p, region_words, h->groups.errp, h->groups.counters.p + 1, h->stream, emitted,
+    HIP_TRY(h, launch_merge_partials(P, h->groups.table, 1, ecap, h->part.emit.p, region_words, h->groups.errp, h->groups.counters.p + CTR_GROUPS, h->stream, emitted,
                                      singletons == 0));
     if (e1) (void)hipEventRecord(e1, h->stream);
     h->timing.events.emplace_back(e0, e1);

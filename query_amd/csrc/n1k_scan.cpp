@@ -293,7 +293,7 @@ static ScanChoice choose_scan(n1k_handle* h, uint64_t nrows) {
 // merge.  A specialised kernel takes its WIDE form (2 adjacent rows per lane and load) over the even prefix of aligned
 // columns, and an odd last row through a second, scalar launch.
 static n1k_status launch_chunk(n1k_handle* h, const ScanChoice& c, const Program& P, FastArgs& F, const WordLogArgs& L, uint64_t off, uint64_t n) {
-    unsigned long long* ngroups = h->groups.counters.p + 1;
+    unsigned long long* ngroups = h->groups.counters.p + CTR_GROUPS;
     auto launch = [&](uint32_t g, bool wide) {
         if (c.kernel.spec) return c.kernel.spec->launch(P, F, h->groups.table, ngroups, g, c.fblock, wide, L, h->stream);
         if (c.kernel.jit) return jit_launch(c.kernel.jit, P, F, h->groups.table, ngroups, g, wide, L, c.ndist, h->stream);
@@ -334,7 +334,7 @@ static n1k_status run_shaped(n1k_handle* h, ScanChoice& c, const ScanArgs& A, ui
     const Program& P = c.ndist ? c.compact : h->prog;
     FastArgs& F = c.F;
     F.err_flags = h->groups.errp;
-    F.rows_selected = h->groups.counters.p + 0;
+    F.rows_selected = h->groups.counters.p + CTR_ROWS_SELECTED;
     F.nrows_dev = h->push_nrows_dev;
     if (h->push_nseg > 1) {
         if (h->push_nseg > kMaxSegments || nrows >= (1ull << 31)) return fail(h, N1K_INVALID, "segmented batch too large");
@@ -369,7 +369,7 @@ static n1k_status run_interpreter(n1k_handle* h, const ScanChoice& c, ScanArgs& 
     A.lds_slots = c.slots;
     A.lds_max_fill = std::max(1u, (uint32_t)((uint64_t)c.slots * 5 / 8));
     A.err_flags = h->groups.errp;
-    A.rows_selected = h->groups.counters.p + 0;
+    A.rows_selected = h->groups.counters.p + CTR_ROWS_SELECTED;
     uint64_t tile_rows = (uint64_t)c.block * c.rpl;
     uint64_t ntiles = (nrows + tile_rows - 1) / tile_rows;
     uint32_t per_cu = c.block == 1024 ? 1 : (c.block == 512 ? 2 : 4);
@@ -388,10 +388,10 @@ static n1k_status run_interpreter(n1k_handle* h, const ScanChoice& c, ScanArgs& 
             As.nrows_dev = h->push_seg_counts + (size_t)sg * kCursorStride;
             const uint64_t nt = (h->push_seg_rows + tile_rows - 1) / tile_rows;
             const uint32_t g = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(grid, nt));
-            HIP_TRY(h, launch_scan_group(Ps, As, h->groups.table, h->groups.counters.p + 1, g, c.block, c.rpl, c.direct, h->stream));
+            HIP_TRY(h, launch_scan_group(Ps, As, h->groups.table, h->groups.counters.p + CTR_GROUPS, g, c.block, c.rpl, c.direct, h->stream));
         }
     } else
-        HIP_TRY(h, launch_scan_group(P, A, h->groups.table, h->groups.counters.p + 1, grid, c.block, c.rpl, c.direct, h->stream));
+        HIP_TRY(h, launch_scan_group(P, A, h->groups.table, h->groups.counters.p + CTR_GROUPS, grid, c.block, c.rpl, c.direct, h->stream));
     if (e1) (void)hipEventRecord(e1, h->stream);
     h->timing.events.emplace_back(e0, e1);
     h->timing.stats.agg_mode = c.direct ? N1K_MODE_LDS_DIRECT : N1K_MODE_LDS_HASH;
@@ -451,10 +451,10 @@ n1k_status run_filter_batch(n1k_handle* h, const n1k_batch* b) {
     const uint32_t grid = filter_stream_grid(h, ntiles, fast);
     if (e0) (void)hipEventRecord(e0, h->stream);
     HIP_TRY(h, launch_filter_stream(P, b->nrows, h->row_base, h->filter.sel.p, (unsigned long long*)h->filter.tile_off.p,
-                                    (unsigned long long*)h->filter.tile_off.p + ntiles, h->groups.counters.p + 3, h->groups.errp, grid, h->stream, fast));
+                                    (unsigned long long*)h->filter.tile_off.p + ntiles, h->groups.counters.p + CTR_FILTER_TOTAL, h->groups.errp, grid, h->stream, fast));
     h->timing.stats.spec_kernel = fast ? 1u : 0u;
     if (e1) (void)hipEventRecord(e1, h->stream);  // device time excludes the PCIe copy of the ordinals
-    HIP_TRY(h, hipMemcpyAsync(&total, h->groups.counters.p + 3, sizeof total, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(&total, h->groups.counters.p + CTR_FILTER_TOTAL, sizeof total, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     if (total) {
         size_t old = h->filter.selected.size();
@@ -608,10 +608,10 @@ n1k_status push_device(n1k_handle* h, const n1k_batch* b) {
         st = ensure_table(h, head);
         if (st != N1K_OK) return st;
         unsigned long long before = 0, after = 0;
-        HIP_TRY(h, hipMemcpyAsync(&before, h->groups.counters.p + 1, sizeof before, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(&before, h->groups.counters.p + CTR_GROUPS, sizeof before, hipMemcpyDeviceToHost, h->stream));
         const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)h->num_cus * 4, (head + 1023) / 1024));
-        HIP_TRY(h, launch_probe_keys(h->prog, head, h->groups.table, h->groups.errp, h->groups.counters.p + 1, grid, h->stream));
-        HIP_TRY(h, hipMemcpyAsync(&after, h->groups.counters.p + 1, sizeof after, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, launch_probe_keys(h->prog, head, h->groups.table, h->groups.errp, h->groups.counters.p + CTR_GROUPS, grid, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(&after, h->groups.counters.p + CTR_GROUPS, sizeof after, hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(h, hipStreamSynchronize(h->stream));
         const uint64_t fresh = after > before ? after - before : 0;
         partition = fresh >= h->opt.partition_min_groups;
@@ -633,7 +633,7 @@ n1k_status push_device(n1k_handle* h, const n1k_batch* b) {
             // the probe's keys are all the handle holds: drop them, so that the partitioned path's groups can stay in
             // their compact region (no table at all for this query)
             HIP_TRY(h, launch_init_table(h->prog, h->groups.table, 0, h->groups.table.capacity, nullptr, h->stream));
-            HIP_TRY(h, hipMemsetAsync(h->groups.counters.p + 1, 0, sizeof(unsigned long long), h->stream));
+            HIP_TRY(h, hipMemsetAsync(h->groups.counters.p + CTR_GROUPS, 0, sizeof(unsigned long long), h->stream));
         }
     }
     if (b->nrows) {

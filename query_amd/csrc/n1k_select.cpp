@@ -70,7 +70,7 @@ n1k_status n1k_filter_device_batch(n1k_handle* h, const n1k_batch* batch, n1k_se
         hipEvent_t e0 = get_event(h), e1 = get_event(h);
         if (e0) (void)hipEventRecord(e0, h->stream);
         HIP_TRY(h, launch_filter_stream(h->prog, n, h->filter.sel32.p, (unsigned long long*)h->filter.tile_off.p,
-                                        (unsigned long long*)h->filter.tile_off.p + ntiles, h->groups.counters.p + 3, h->groups.errp, grid,
+                                        (unsigned long long*)h->filter.tile_off.p + ntiles, h->groups.counters.p + CTR_FILTER_TOTAL, h->groups.errp, grid,
                                         h->stream, fast));
         if (e1) (void)hipEventRecord(e1, h->stream);
         h->timing.events.emplace_back(e0, e1);
@@ -79,8 +79,8 @@ n1k_status n1k_filter_device_batch(n1k_handle* h, const n1k_batch* batch, n1k_se
         HIP_TRY(h, hipMemcpyAsync(h->res.pin_counters.p, h->groups.counters.p, kCounters * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
         if (h->timing.q0_recorded && h->timing.ev_q1 && hipEventRecord(h->timing.ev_q1, h->stream) == hipSuccess) h->timing.q1_recorded = true;
         HIP_TRY(h, hipStreamSynchronize(h->stream));
-        total = h->res.pin_counters.p[3];
-        err_flags = (uint32_t)h->res.pin_counters.p[12];
+        total = h->res.pin_counters.p[CTR_FILTER_TOTAL];
+        err_flags = (uint32_t)h->res.pin_counters.p[CTR_ERR_FLAGS];
         drain_events(h);
     }
     h->timing.stats.rows_in = n;

@@ -356,7 +356,7 @@ n1k_status array_agg_groups(n1k_handle* h, uint64_t ng, const unsigned long long
     for (size_t a = 0; a < na; a++) {
         const AggSpec& ag = h->prog.aggs[a];
         if (ag.kind != AGG_ARRAY) continue;
-        const uint64_t n = std::min<uint64_t>(counters[8 + ag.log_index], h->distinct.log_capacity);
+        const uint64_t n = std::min<uint64_t>(counters[CTR_PAIR_LOG_CURSORS + ag.log_index], h->distinct.log_capacity);
         std::vector<uint64_t> keys((size_t)n), vals((size_t)n);
         std::vector<uint8_t> tags((size_t)n);
         if (n) {
@@ -409,6 +409,16 @@ n1k_status array_agg_groups(n1k_handle* h, uint64_t ng, const unsigned long long
     return N1K_OK;
 }
 
+void publish_result(n1k_handle* h, uint64_t ng, bool partials, n1k_result* out) {
+    out->nproj = h->plan.has_project ? (uint32_t)h->tail.project_ops.size() : 0;
+    out->proj = out->nproj ? h->tail.r_proj.data() : nullptr;
+    out->ngroups = ng;
+    out->keys = h->res.keys.data();
+    out->aggs = h->res.aggs.data();
+    out->partials = partials ? h->res.parts.data() : nullptr;
+    out->rep_row = h->res.rep.data();
+}
+
 }  // namespace n1k_eng
 
 extern "C" {
@@ -431,17 +441,9 @@ n1k_status n1k_order_rows(n1k_handle* h, uint64_t ngroups, const n1k_value* keys
     h->res.rep.assign((size_t)ngroups, ~0ull);
     h->tail.r_proj.clear();
     uint64_t ng = ngroups;
-    n1k_status st = h->plan.has_project ? project_groups(h, ng) : N1K_OK;  // (sort terms may name projection aliases)
-    if (st != N1K_OK) return st;
-    st = order_groups(h, ng);
-    if (st != N1K_OK) return st;
-    out->nproj = h->plan.has_project ? (uint32_t)h->tail.project_ops.size() : 0;
-    out->proj = out->nproj ? h->tail.r_proj.data() : nullptr;
-    out->ngroups = ng;
-    out->keys = h->res.keys.data();
-    out->aggs = h->res.aggs.data();
-    out->partials = nullptr;
-    out->rep_row = h->res.rep.data();
+    if (h->plan.has_project) ST_TRY(project_groups(h, ng));  // (sort terms may name projection aliases)
+    ST_TRY(order_groups(h, ng));
+    publish_result(h, ng, false, out);
     return N1K_OK;
     });
 }
