@@ -159,7 +159,8 @@ typedef struct n1k_stats {
     uint64_t wide_key_values; /* distinct key numbers held in the wide-value tables (floats, |int| beyond the field); set by finish/export */
     uint32_t distinct_path;  /* how the last finish built the DISTINCT sets: bit 0 per-group sets in global memory (two-word
                                 pairs), bit 1 radix partition + LDS sets (one-word members), bit 2 global one-word set (fallback) */
-    uint32_t reserved0;
+    uint32_t order_passes;   /* ordered Filter-only plans: radix passes the last n1k_filter_device_batch launched (a digit whose
+                                histogram has one non-empty bin costs none) */
     uint64_t topk_candidates; /* ORDER BY ... LIMIT: groups that left the device after the top-k filter (0 = filter not used) */
     uint64_t json_device_docs; /* documents of n1k_push_json whose leaf values the DEVICE extractor produced (the rest: the host's) */
     double query_ms;        /* hipEvent time of the last WHOLE query on the handle's stream: from n1k_reset (reopen) to the last
@@ -189,6 +190,15 @@ typedef struct n1k_handle n1k_handle;
  *                                        {"#operator":"InitialGroup","group_keys":[…],"aggregates":[…]}]}
  *   {"#operator":"InitialGroup", …}            (no Filter)
  *   {"#operator":"Filter","condition":"…"}     (Filter only: result = selected row ordinals)
+ *   {"#operator":"Sequence","~children":[<Filter only, bare or under Parallel / Sequence>,       (ORDER BY / OFFSET / LIMIT over
+ *        {"#operator":"Order","sort_terms":[{"expr":"…","desc":true}],"offset":"…","limit":"…"},  the rows of a Filter-only plan:
+ *        {"#operator":"Offset","expr":"…"}, {"#operator":"Limit","expr":"…"}]}                    n1k_filter_device_batch)
+ *     1 to 4 sort terms, each a leaf path of the row in the text form a condition uses (its path joins the plan's columns
+ *     behind the condition's); offset / limit are integer constants; Offset / Limit may come without Order.  Arithmetic,
+ *     functions, aggregates or constants as sort terms, more than 4 terms, Order with neither Filter nor group before it,
+ *     and InitialProject / FinalProject in a plan without a group (the caller projects with n1k_gather_selected) are
+ *     N1K_UNSUPPORTED.  Such a plan runs through n1k_filter_device_batch alone: n1k_push_batch, n1k_push_device_batch,
+ *     n1k_push_json and n1k_run_device_batch answer N1K_UNSUPPORTED.
  *   {"#operator":"Parallel","~child":<one of the above>, "maxParallelism":n}
  *   {"#operator":"Sequence","~children":[<one of the above>, IntermediateGroup, FinalGroup,      (the grouped tail:
  *        {"#operator":"Filter","condition":"…"},                                       HAVING, plan/filter.go
@@ -317,9 +327,11 @@ n1k_status n1k_run_device_batch(n1k_handle *h, const n1k_batch *batch, n1k_resul
  * path and n1k_run_device_batch keep returning 64-bit host ordinals in n1k_result.selected.
  */
 typedef struct n1k_selection {
-    uint64_t nselected;     /* rows whose condition is TRUE */
-    const uint32_t *rows;   /* DEVICE pointer: their ordinals inside the batch, ascending; owned by the handle,
-                               valid until the next n1k_filter_device_batch / n1k_reset / n1k_destroy; NULL when 0 */
+    uint64_t nselected;     /* rows whose condition is TRUE; a plan with Offset / Limit: those left after the cut */
+    const uint32_t *rows;   /* DEVICE pointer: their ordinals inside the batch — ascending for a plan without Order, else in
+                               ORDER BY order (rows that tie on every term in ascending ordinal) — cut to [offset, offset + limit);
+                               owned by the handle, valid until the next n1k_filter_device_batch / n1k_reset / n1k_destroy;
+                               NULL when 0 */
 } n1k_selection;
 
 /*
@@ -331,6 +343,15 @@ typedef struct n1k_selection {
  * N1K_UNSUPPORTED_DATA: as n1k_finish reports it.  Afterwards n1k_get_stats describes this call (rows_in, rows_selected,
  * batches, device_ms, query_ms, spec_kernel); the handle is otherwise as after n1k_reset: a following n1k_finish returns an
  * empty selection.  One batch per selection.
+ *
+ * A plan with Order / Offset / Limit (n1k_create): the selection comes back ordered and cut, from this same call (≙
+ * execution/order.go:121-169, order_limit.go, offset.go, limit.go).  The order is value.Collate term by term, DESC flipping a
+ * term, with an INT and a FLOAT compared exactly and rows that tie on every term in ascending ordinal (the reference's
+ * sort.Sort is not stable: any tie order is admissible there); -0.0, 0.0 and INT 0 tie; a NaN sorts before every number.  The
+ * sort runs on the device — radix passes over 64-bit keys (n1k_order_key), a radix select of the offset + limit smallest
+ * first when that is fewer rows than were selected and at least "topk_min_groups" were — behind a few more small waits.
+ * An ARRAY or OBJECT met as a sort value: N1K_UNSUPPORTED_DATA.  n1k_get_stats: rows_in, rows_selected = the cut count,
+ * topk_candidates = the rows the select passed on to the sort (0: it did not run).
  */
 n1k_status n1k_filter_device_batch(n1k_handle *h, const n1k_batch *batch, n1k_selection *out);
 
@@ -348,6 +369,16 @@ n1k_status n1k_selected_to_host32(n1k_handle *h, uint32_t *out, uint64_t capacit
  * counts that do not match, capacity_rows below nselected.
  */
 n1k_status n1k_gather_selected(n1k_handle *h, const n1k_batch *src, uint64_t capacity_rows, const n1k_col *out_cols);
+
+/*
+ * The sort key of one value of a sort term, as the device computes it for an ordered Filter-only plan: comparing
+ * (key, residual) as unsigned integers is value.Collate with an INT and a FLOAT compared exactly.  Classes from the bottom:
+ * MISSING, NULL, FALSE, TRUE, NaN, the numbers (the sortable form of their float64, either zero as +0.0), the strings by
+ * `rank` (the bytewise rank of the string among the dictionary's).  residual: an INT's distance from its float64, biased by
+ * 1024 — other than 1024 only beyond +-2^53.  desc: both complemented.  Needs no device.  N1K_UNSUPPORTED_DATA: an ARRAY or
+ * OBJECT; N1K_INVALID: a NULL pointer, an unknown tag.
+ */
+n1k_status n1k_order_key(uint32_t tag, uint64_t payload, uint32_t rank, int desc, uint64_t *key, uint32_t *residual);
 
 /* Wait for all queued device work of the handle. */
 n1k_status n1k_sync(n1k_handle *h);

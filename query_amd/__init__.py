@@ -6,6 +6,6 @@ Python host layer used by tests, bench.py and the multi-GPU driver; it holds
 no compute of its own and no CPU fallback.
 """
 from . import _ffi, plan  # noqa: F401
-from .gpu_operator import GpuFilterGroup, GroupRows, N1kError, device_count  # noqa: F401
+from .gpu_operator import GpuFilterGroup, GroupRows, N1kError, device_count, order_key  # noqa: F401
 
-__all__ = ["GpuFilterGroup", "GroupRows", "N1kError", "device_count", "plan"]
+__all__ = ["GpuFilterGroup", "GroupRows", "N1kError", "device_count", "order_key", "plan"]

@@ -60,7 +60,7 @@ class Stats(C.Structure):
     _fields_ = [("rows_in", C.c_uint64), ("rows_selected", C.c_uint64), ("groups_out", C.c_uint64),
                 ("batches", C.c_uint64), ("device_ms", C.c_double), ("bytes_scanned", C.c_uint64),
                 ("agg_mode", C.c_uint32), ("spec_kernel", C.c_uint32),
-                ("wide_key_values", C.c_uint64), ("distinct_path", C.c_uint32), ("reserved0", C.c_uint32),
+                ("wide_key_values", C.c_uint64), ("distinct_path", C.c_uint32), ("order_passes", C.c_uint32),
                 ("topk_candidates", C.c_uint64), ("json_device_docs", C.c_uint64), ("query_ms", C.c_double)]
 
 
@@ -91,7 +91,7 @@ SYMBOLS = [
     "n1k_in_match", "n1k_in_match_device", "n1k_in_stats",
     "n1k_strfn_eval", "n1k_strfn_eval_device", "n1k_strfn_stats",
     "n1k_device_bytes_live",
-    "n1k_filter_device_batch", "n1k_selected_to_host32", "n1k_gather_selected",
+    "n1k_filter_device_batch", "n1k_selected_to_host32", "n1k_gather_selected", "n1k_order_key",
 ]
 
 _lib = None
@@ -269,6 +269,9 @@ def lib():
         L.n1k_selected_to_host32.argtypes = [H, C.c_void_p, C.c_uint64]
         L.n1k_gather_selected.restype = C.c_int
         L.n1k_gather_selected.argtypes = [H, C.POINTER(Batch), C.c_uint64, C.POINTER(Col)]
+    if hasattr(L, "n1k_order_key"):  # (idem)
+        L.n1k_order_key.restype = C.c_int
+        L.n1k_order_key.argtypes = [C.c_uint32, C.c_uint64, C.c_uint32, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
     L.n1k_abi_version.restype = C.c_int
     L.n1k_device_count.restype = C.c_int
     _lib = L

@@ -347,6 +347,7 @@ bool compile_plan(n1k_handle* h, PlanError& err) {
         }
         if (pl.has_order) h->need_rank = true;  // order images of string values (top-k filter)
     }
+    if (!pl.row_order.empty()) h->need_rank = true;  // order keys of string values (n1k_order.h)
     P.lds_words = lds_w;
     P.glob_words = glob_w ? glob_w : 1;
     if (h->has_array_agg) {
@@ -927,12 +928,14 @@ n1k_status n1k_set_option(n1k_handle* h, const char* name, int64_t value) {
 n1k_status n1k_push_device_batch(n1k_handle* h, const n1k_batch* batch) {
     return guarded(h, [&]() -> n1k_status {
     if (!h) return N1K_INVALID;
+    ST_TRY(refuse_ordered_rows(h, "n1k_push_device_batch"));
     return push_device(h, batch);
     });
 }
 
 n1k_status n1k_run_device_batch(n1k_handle* h, const n1k_batch* batch, n1k_result* out) {
     if (!h || !batch || !out) return N1K_INVALID;
+    if (h->plan.ordered_rows()) return guarded(h, [&]() -> n1k_status { return refuse_ordered_rows(h, "n1k_run_device_batch"); });
     static const bool trace = getenv("N1K_HOST_TRACE") != nullptr;
     auto now = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     const double t0 = trace ? now() : 0;
@@ -1039,6 +1042,7 @@ n1k_status n1k_extract_json(n1k_handle* h, uint64_t ndocs, const uint64_t* offse
 n1k_status n1k_push_json(n1k_handle* h, uint64_t ndocs, const uint64_t* offsets, const char* bytes) {
     return guarded(h, [&]() -> n1k_status {
     if (!h || (ndocs && (!offsets || !bytes))) return N1K_INVALID;
+    ST_TRY(refuse_ordered_rows(h, "n1k_push_json"));
     if (h->stop_flag.load()) return fail(h, N1K_STOPPED, "operator was stopped");
     // large batches: the device extractor (the bytes cross PCIe as they are; n1k_jsonpush.cpp) — it takes the batch or
     // leaves all of it to the host path below
@@ -1063,6 +1067,7 @@ n1k_status n1k_push_json(n1k_handle* h, uint64_t ndocs, const uint64_t* offsets,
 n1k_status n1k_push_batch(n1k_handle* h, const n1k_batch* batch) {
     return guarded(h, [&]() -> n1k_status {
     if (!h) return N1K_INVALID;
+    ST_TRY(refuse_ordered_rows(h, "n1k_push_batch"));
     if (h->stop_flag.load()) return fail(h, N1K_STOPPED, "operator was stopped");
     n1k_status st = ensure_device(h);
     if (st != N1K_OK) return st;

@@ -30,6 +30,7 @@
 #include "n1k_coll.h"
 #include "n1k_in.h"
 #include "n1k_like.h"
+#include "n1k_order.h"
 #include "n1k_plan.h"
 #include "n1k_strfn.h"
 
@@ -293,7 +294,28 @@ struct FilterOnly {
     DevBuf<uint32_t> sel32;
     bool has_sel32 = false;               // a selection exists: until the next n1k_filter_device_batch / n1k_reset
     uint64_t sel32_count = 0, sel32_rows = 0;  // its survivors; the rows of the batch it was taken from
+    const uint32_t* sel32_out = nullptr;  // where the selection lies: sel32, or — a plan with Order / Offset / Limit — what
+                                          // order_selection left (n1k_order.cpp); sel32_count is then the cut count
 };
+
+// ---- n1k_order.cpp: ORDER BY / OFFSET / LIMIT over the rows of a Filter-only plan, sorted on the device (n1k_order.hip)
+struct RowOrder {
+    DevBuf<uint64_t> key[kOrdHists];     // per term (and for the selection position, the select route): the survivors' keys
+    DevBuf<uint16_t> res[kOrdMaxTerms];  // ... and residuals
+    DevBuf<uint64_t> kbuf[2];            // the passes' keys, ping-pong
+    DevBuf<uint32_t> vbuf[2];            // ... and positions
+    DevBuf<uint32_t> hist, tile_hist;    // [term][digit][256]; 256 x tiles
+    DevBuf<uint32_t> cand;               // the select route: candidate positions (+ the sampled route's segment lists)
+    DevBuf<char> state;                  // ... and the select's state
+    DevBuf<uint32_t> rows_out;           // the ordered, cut selection
+    PinBuf<uint32_t> pin_hist;           // host copy of the histograms, then the error flags and the candidate count
+    uint32_t passes = 0;                 // digit passes the last ordering launched (diagnostics: tools/exp_order.py)
+};
+// the ascending selection of `total` survivors in h->filter.sel32 -> ordered and cut as the plan says; *out_rows (null when
+// *out_count is 0) is what n1k_selection.rows returns
+n1k_status order_selection(n1k_handle* h, uint64_t total, const uint32_t** out_rows, uint64_t* out_count);
+// the multi-batch calls on a plan whose rows are ordered or cut: N1K_UNSUPPORTED
+n1k_status refuse_ordered_rows(n1k_handle* h, const char* call);
 bool filter_stream_fast(const n1k_handle* h);  // the condition and the bound columns take filter_stream_kernel's FAST variant
 uint32_t filter_stream_grid(const n1k_handle* h, uint64_t ntiles, bool fast);
 bool build_fast_args(n1k_handle* h, uint32_t max_slots, FastArgs& F, bool fuse = false, bool partition_only = false);
@@ -496,6 +518,7 @@ struct n1k_handle {
     Json json;
     Staging stage;
     FilterOnly filter;
+    RowOrder order;
     Results res;
     Timing timing;
 };

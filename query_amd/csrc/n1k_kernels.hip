@@ -3165,6 +3165,13 @@ hipError_t launch_topk_select(const Program& P, const OutValue* vals, uint32_t s
     return hipGetLastError();
 }
 
+// The same select over images that are ready (the first sort term's keys of an ordered Filter-only selection, n1k_order.cpp):
+// cand receives the indices of the images at or below the keep-th smallest, in no particular order.
+hipError_t launch_topk_select_images(const uint64_t* images, uint64_t n, uint64_t keep, void* state, uint32_t* cand, hipStream_t st, bool sampled) {
+    const Program none{};  // (only the image kernel reads the program, and it does not run)
+    return launch_topk_select(none, nullptr, 0, 0, n, false, keep, const_cast<uint64_t*>(images), state, cand, st, sampled, true);
+}
+
 size_t topk_ncand_offset() { return offsetof(TopkState, ncand); }
 
 hipError_t launch_topk_compact(const uint32_t* cand, uint64_t ncand, uint32_t nk, uint32_t na, const OutValue* keys,

@@ -734,6 +734,7 @@ bool plan_node(const JVal& node, ParsedPlan& out, PlanError& err, int depth) {
     }
     if (name == "InitialGroup") {  // plan/group.go:54-70
         if (out.has_group) { err.unsupported = true; err.msg = "more than one InitialGroup"; return false; }
+        if (out.ordered_rows()) { err.unsupported = true; err.msg = "InitialGroup after Order / Offset / Limit does not run on the device"; return false; }
         const JVal* ks = node.get("group_keys");
         const JVal* as = node.get("aggregates");
         if (ks && ks->type == JVal::Arr)
@@ -780,9 +781,40 @@ bool plan_node(const JVal& node, ParsedPlan& out, PlanError& err, int depth) {
         return true;
     };
     if (name == "Order") {  // plan/order.go:51-79 (the node carries its own offset / limit for the top-k sort)
-        if (!out.has_group || out.has_order) { err.unsupported = true; err.msg = "Order runs on the device only over the groups"; return false; }
+        if ((!out.has_group && !out.has_filter) || out.has_order || !out.row_order.empty()) {
+            err.unsupported = true;
+            err.msg = "Order runs on the device only over the groups or over the rows of a Filter";
+            return false;
+        }
         const JVal* ts = node.get("sort_terms");
         if (!ts || ts->type != JVal::Arr || ts->arr.empty()) { err.msg = "Order without sort_terms"; return false; }
+        if (!out.has_group) {  // over the rows a Filter selects: every term a leaf path of the row
+            if (out.limit >= 0 || out.offset > 0) { err.unsupported = true; err.msg = "Order after Offset / Limit does not run on the device"; return false; }
+            if (ts->arr.size() > kOrderMaxTerms) {
+                err.unsupported = true;
+                err.msg = "Order over rows with " + std::to_string(ts->arr.size()) + " sort terms: the device takes 1 to " + std::to_string(kOrderMaxTerms);
+                return false;
+            }
+            for (auto& t : ts->arr) {
+                const JVal* e = t.type == JVal::Obj ? t.get("expr") : nullptr;
+                if (!e || e->type != JVal::Str) { err.msg = "sort term without expr"; return false; }
+                PlanError perr;
+                auto ex = parse_expression(e->str, perr);
+                if (!ex || ex->kind != EK::Path) {
+                    err.unsupported = true;
+                    err.msg = "sort term of a plan without a group is not a leaf path of the row (arithmetic, functions, aggregates and constants keep the reference's Order): " + e->str;
+                    return false;
+                }
+                RowOrderTerm rt;
+                rt.text = ex->text;
+                const JVal* d = t.get("desc");
+                rt.desc = d && d->type == JVal::Bool && d->b;
+                out.row_order.push_back(rt);
+            }
+            if (node.get("offset") && !const_count(node.get("offset"), "offset", out.offset)) return false;
+            if (node.get("limit") && !const_count(node.get("limit"), "limit", out.limit)) return false;
+            return true;
+        }
         for (auto& t : ts->arr) {
             const JVal* e = t.type == JVal::Obj ? t.get("expr") : nullptr;
             if (!e || e->type != JVal::Str) { err.msg = "sort term without expr"; return false; }
@@ -850,7 +882,7 @@ bool plan_node(const JVal& node, ParsedPlan& out, PlanError& err, int depth) {
         return true;
     }
     if (name == "Limit" || name == "Offset") {  // plan/limit.go:46-53, plan/offset.go
-        if (!out.has_group) { err.unsupported = true; err.msg = name + " runs on the device only over the groups"; return false; }
+        if (!out.has_group && !out.has_filter) { err.unsupported = true; err.msg = name + " runs on the device only over the groups or over the rows of a Filter"; return false; }
         return const_count(node.get("expr"), name == "Limit" ? "limit" : "offset", name == "Limit" ? out.limit : out.offset);
     }
     err.unsupported = true;
@@ -977,6 +1009,11 @@ bool parse_plan_json(const char* json, size_t len, ParsedPlan& out, PlanError& e
     collect_paths(out.condition.get(), out.paths);
     for (auto& k : out.keys) collect_paths(k.get(), out.paths);
     for (auto& a : out.aggs) collect_paths(a.operand.get(), out.paths);
+    for (auto& t : out.row_order) {  // sort-term paths after the condition's, in first-use order, none twice
+        auto at = std::find(out.paths.begin(), out.paths.end(), t.text);
+        t.col = (int)(at - out.paths.begin());
+        if (at == out.paths.end()) out.paths.push_back(t.text);
+    }
     return true;
 }
 

@@ -67,6 +67,14 @@ struct OrderTerm {
     int proj_index = -1; // >= 0: a projection term (by its alias, or by its expression text)
 };
 
+// one ORDER BY term over the rows of a Filter-only plan: a leaf path of the row, in the text form a Filter condition uses
+constexpr uint32_t kOrderMaxTerms = 4;
+struct RowOrderTerm {
+    std::string text;
+    bool desc = false;
+    int col = -1;  // its column: index into ParsedPlan::paths
+};
+
 // one result term of the InitialProject after the group operators (plan/project.go:73-110): its expression reads group
 // keys and aggregates (algebra/aggregate.go:97-118 looks an aggregate up by its text in the "aggregates" attachment)
 struct ProjectTerm {
@@ -88,6 +96,10 @@ struct ParsedPlan {
     std::vector<OrderTerm> order;
     int64_t limit = -1;  // < 0: none
     int64_t offset = 0;
+    // Order over the ROWS a Filter-only plan selects (no group): 1 to kOrderMaxTerms leaf paths; limit / offset above then cut
+    // the ordered (without Order: the ascending) selection
+    std::vector<RowOrderTerm> row_order;
+    bool ordered_rows() const { return !has_group && (!row_order.empty() || limit >= 0 || offset > 0); }
     // HAVING: a Filter after the group operators (planner/build_select_sub.go:295), over group keys and aggregates
     bool has_having = false;
     std::string having_text;

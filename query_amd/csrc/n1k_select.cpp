@@ -93,12 +93,20 @@ n1k_status n1k_filter_device_batch(n1k_handle* h, const n1k_batch* batch, n1k_se
     }
     if (h->stop_flag.load()) return fail(h, N1K_STOPPED, "operator was stopped");
     if (total > n) return fail(h, N1K_DEVICE_ERROR, "the Filter kernel counted %llu survivors of %llu rows", total, (unsigned long long)n);
+    // a plan with Order / Offset / Limit: the survivors in ORDER BY order, cut to [offset, offset + limit) (n1k_order.cpp)
+    const uint32_t* rows = total ? h->filter.sel32.p : nullptr;
+    if (h->plan.ordered_rows()) {
+        uint64_t cut = 0;
+        ST_TRY(order_selection(h, total, &rows, &cut));
+        total = cut;
+    }
     h->timing.stats.rows_selected = total;
     h->filter.has_sel32 = true;
     h->filter.sel32_count = total;
     h->filter.sel32_rows = n;
+    h->filter.sel32_out = rows;
     out->nselected = total;
-    out->rows = total ? h->filter.sel32.p : nullptr;
+    out->rows = rows;
     return N1K_OK;
     });
 }
@@ -112,7 +120,7 @@ n1k_status n1k_selected_to_host32(n1k_handle* h, uint32_t* out, uint64_t capacit
     if (!n) return N1K_OK;
     if (!out) return fail(h, N1K_INVALID, "null output");
     HIP_TRY(h, hipSetDevice(h->device));
-    HIP_TRY(h, hipMemcpyAsync(out, h->filter.sel32.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(out, h->filter.sel32_out, n * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return N1K_OK;
     });
@@ -144,7 +152,7 @@ n1k_status n1k_gather_selected(n1k_handle* h, const n1k_batch* src, uint64_t cap
         g.dst_codes = const_cast<uint32_t*>(out_cols[c].codes);
     }
     if (!n) return N1K_OK;
-    A.rows = h->filter.sel32.p;
+    A.rows = h->filter.sel32_out;
     A.n = n;
     A.ncols = src->ncols;
     HIP_TRY(h, hipSetDevice(h->device));

@@ -30,6 +30,17 @@ def device_count() -> int:
     return int(_ffi.lib().n1k_device_count())
 
 
+def order_key(tag: int, payload: int, rank: int = 0, desc: bool = False):
+    """n1k_order_key: the (key, residual) pair an ordered Filter-only plan sorts one value of a sort term by, computed on
+    the host by the function the key kernel compiles.  payload: the n1k_value payload as an unsigned 64-bit word (an INT's
+    two's complement, a FLOAT's bits); rank: the bytewise rank of a STRING among the dictionary's strings."""
+    key, res = C.c_uint64(), C.c_uint32()
+    st = _ffi.lib().n1k_order_key(int(tag), int(payload) & 0xFFFFFFFFFFFFFFFF, int(rank), 1 if desc else 0, C.byref(key), C.byref(res))
+    if st != _ffi.OK:
+        raise N1kError(st, "n1k_order_key(tag %d)" % tag)
+    return int(key.value), int(res.value)
+
+
 @dataclass
 class GroupRows:
     """Groups as FinalGroup would emit them: per group the key values and the final aggregate values
@@ -178,7 +189,8 @@ class GpuFilterGroup:
     def filter_device_batch(self, batch):
         """n1k_filter_device_batch: one whole execution of a Filter-only plan over a device-resident batch (as
         make_device_batch builds it).  Returns (nselected, device address of the ascending uint32 batch-local ordinals; None
-        when nothing passed): the ordinals stay in the handle's device memory until the next call / reopen / done."""
+        when nothing passed): the ordinals stay in the handle's device memory until the next call / reopen / done.  A plan
+        with Order / Offset / Limit: the ordinals in ORDER BY order, cut, and nselected the cut count."""
         sel = _ffi.Selection()
         self._nselected = 0
         self._check(self._lib.n1k_filter_device_batch(self._h, C.byref(batch[0]), C.byref(sel)))

@@ -160,7 +160,9 @@ def filter_group_plan(condition: Optional[str], group_keys: Optional[Sequence[st
     """Plan JSON of Parallel{Sequence[Filter?, InitialGroup?]} as the planner emits it
     (planner/build_select_sub.go:209-211, 276-296).  With `order` / `limit` / `offset` the whole grouped tail
     follows: IntermediateGroup, FinalGroup, Order (which carries offset and limit, plan/order.go:51-79), Offset,
-    Limit (planner/build_select.go) — the sort terms must be group keys or aggregates of the plan."""
+    Limit (planner/build_select.go) — the sort terms must be group keys or aggregates of the plan.  With `filter_only`
+    the same three follow the Filter directly, over the rows it selects: `order` = [(leaf path of the row, descending)],
+    1 to 4 terms; n1k_filter_device_batch then returns the selection ordered and cut."""
     children: List[object] = []
     if condition:
         children.append(Filter(condition))
@@ -169,8 +171,15 @@ def filter_group_plan(condition: Optional[str], group_keys: Optional[Sequence[st
     par = Parallel(Sequence(children))
     if order is None and limit is None and offset is None and having is None and project is None:
         return marshal_json(par)
-    tail: List[object] = [par, IntermediateGroup(list(group_keys or []), list(aggregates or [])),
-                          FinalGroup(list(group_keys or []), list(aggregates or []))]
+    if filter_only:
+        # a Filter-only plan: Order / Offset / Limit over the rows it selects; the sort terms are leaf paths of the row
+        # (the caller projects with n1k_gather_selected: no InitialProject here)
+        if having is not None or project is not None:
+            raise ValueError("a Filter-only plan takes order / offset / limit, not having / project")
+        tail: List[object] = [par]
+    else:
+        tail = [par, IntermediateGroup(list(group_keys or []), list(aggregates or [])),
+                FinalGroup(list(group_keys or []), list(aggregates or []))]
     if project is not None:
         # HAVING and the projection share the Parallel after FinalGroup (planner/build_select_sub.go:217-235, :295);
         # `project` = [(expression text, alias or None)]
