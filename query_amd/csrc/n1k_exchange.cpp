@@ -1,6 +1,7 @@
 // n1k_exchange.cpp — partial groups in and out of a handle, the hash partition of the row exchange, and the collectives
 // (RCCL, or the loopback transport) behind n1k_comm_* / n1k_exchange_* / n1k_gather_groups.
 #include "n1k_engine.h"
+#include "n1k_wire.h"
 
 using namespace n1k;
 using namespace n1k_eng;
@@ -274,7 +275,6 @@ struct LoopHub {
     std::vector<const void*> ptr;
     std::vector<size_t> stride;  // all-to-all: distance between the regions a rank published (0: one region for every peer)
     std::vector<unsigned long long> val;
-    int refs = 0;
     void barrier() {
         std::unique_lock<std::mutex> lk(mu);
         const uint64_t g = generation;
@@ -287,12 +287,13 @@ struct LoopHub {
     }
 };
 
+// (owns what it holds: the hub is shared by its ranks and goes with the last of them, the buffers free themselves)
 struct n1k_comm {
     ncclComm_t comm = nullptr;
-    LoopHub* hub = nullptr;  // non-null: loopback transport
+    std::shared_ptr<LoopHub> hub;  // non-null: loopback transport
     int rank = 0, world = 1, device = 0;
     DevBuf<char> send, recv, gsend, grecv;
-    DevBuf<char> void_send, void_recv;  // one region each: what a rank whose own part of a step failed ships / lets land (void_regions)
+    DevBuf<char> void_send, void_recv;  // one region each: what a rank whose own part of a step failed ships / lets land (void_wire)
     DevBuf<unsigned long long> scalar;
     hipEvent_t ev = nullptr;
     hipEvent_t ev_consumed = nullptr;   // on the receiving stream, behind the last kernel that reads send / recv
@@ -304,6 +305,14 @@ struct n1k_comm {
     uint64_t gather_cap = 1024;    // records per slot of n1k_gather_groups (the same on every rank, see there)
     std::vector<char> ghost;       // gathered records on the host
     std::vector<n1k_value> gkeys, gaggs;
+    ~n1k_comm() {  // (on the communicator's device: n1k_comm_destroy; no copies: its buffers have none)
+        if (comm) (void)ncclCommDestroy(comm);
+        if (ev) (void)hipEventDestroy(ev);
+        if (ev_consumed) (void)hipEventDestroy(ev_consumed);
+    }
+    bool create_events() {
+        return hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&ev_consumed, hipEventDisableTiming) == hipSuccess;
+    }
 };
 
 namespace {
@@ -367,8 +376,11 @@ n1k_status loop_refused(n1k_comm* c) {
     return N1K_INVALID;
 }
 
-// all-gather of `bytes` from every rank: send_extent / recv_extent are the sizes of the buffers behind `send` / `recv`
-n1k_status all_gather_bytes(n1k_comm* c, const char* send, size_t send_extent, char* recv, size_t recv_extent, size_t bytes, hipStream_t st) {
+// all-gather of w.region bytes from every rank (n1k_wire.h Wire: the strides play no part)
+n1k_status all_gather_bytes(n1k_comm* c, const Wire& w, hipStream_t st) {
+    const char* const send = w.send;
+    char* const recv = w.recv;
+    const size_t bytes = w.region, send_extent = w.send_extent, recv_extent = w.recv_extent;
     if (outside_extent(c, "send", bytes, send_extent) || outside_extent(c, "receive", bytes * (size_t)c->world, recv_extent))
         return c->hub ? loop_refused(c) : N1K_INVALID;
     if (c->hub)
@@ -383,16 +395,16 @@ n1k_status all_gather_bytes(n1k_comm* c, const char* send, size_t send_extent, c
     return N1K_OK;
 }
 
-// All-to-all of equal regions: the region at send + p * send_stride goes to rank p, rank s's region lands at
-// recv + s * recv_stride.  This rank's own region is not copied: the caller reads it where it lies (`self`).  A stride of 0
-// is how a rank whose own part failed takes part (void_regions): one region for every peer, one sink for what arrives.
-// send_extent / recv_extent: the sizes of the buffers behind `send` / `recv`.  A call whose last region ((world - 1) * stride +
-// its length; stride 0: the longest region alone) ends outside either is refused before the group is opened.
+// All-to-all of the regions of a Wire (n1k_wire.h).  This rank's own region is not copied: the caller reads it where it lies
+// (`self`).  A stride of 0 is how a rank whose own part failed takes part (void_wire): one region for every peer, one sink
+// for what arrives.  A call whose last region ((world - 1) * stride + its length; stride 0: the longest region alone) ends
+// outside either extent is refused before the group is opened.
 // Once the group is open it is always closed: no early return between ncclGroupStart and ncclGroupEnd.
-n1k_status all_to_all_regions(n1k_comm* c, const char* send, size_t send_extent, size_t send_stride, char* recv, size_t recv_extent, size_t recv_stride,
-                              size_t region, hipStream_t st, const char** self, const size_t* send_bytes = nullptr) {
-    // send_bytes: the region for rank p is send_bytes[p] long (regions of per-destination capacities: every rank sizes the regions
-    // for destination p alike, so what this rank receives from everybody is `region` = send_bytes[its own rank] long)
+n1k_status all_to_all_regions(n1k_comm* c, const Wire& w, hipStream_t st, const char** self) {
+    const char* const send = w.send;
+    char* const recv = w.recv;
+    const size_t send_extent = w.send_extent, send_stride = w.send_stride, recv_extent = w.recv_extent, recv_stride = w.recv_stride, region = w.region;
+    const size_t* const send_bytes = w.send_bytes;
     *self = send + (size_t)c->rank * send_stride;
     size_t send_end = 0;
     for (int p = 0; p < c->world; p++) send_end = std::max(send_end, (size_t)p * send_stride + (send_bytes ? send_bytes[p] : region));
@@ -462,27 +474,27 @@ n1k_status order_streams(n1k_comm* c, n1k_handle* snd, n1k_handle* rcv) {
     return N1K_OK;
 }
 
-// layout of one packed row region for `cap` rows (kRowSubs sub-regions of cap / kRowSubs rows) of the plan's input columns:
-// the header (sub-region x's row count at word x * kCursorStride, the verdict in word 1), then per column its arrays, each
-// starting on a 16-byte boundary
-size_t row_region_layout(const n1k_handle* h, uint64_t cap, std::vector<size_t>& off_a, std::vector<size_t>& off_b) {
-    size_t at = (size_t)kRowSubs * kCursorStride * 8;  // header: the sub-regions' counts, 128 bytes apart; verdict in word 1
-    const size_t nc = h->plan.paths.size();
-    off_a.assign(nc, 0);
-    off_b.assign(nc, 0);
-    auto pad = [](size_t x) { return (x + 15) / 16 * 16; };
-    for (size_t i = 0; i < nc; i++) {
-        if (h->col_kinds[i] == N1K_COL_DICT32) {
-            off_a[i] = at;
-            at = pad(at + cap * 4);
-        } else {
-            off_a[i] = at;  // payload
-            at = pad(at + cap * 8);
-            off_b[i] = at;  // tags
-            at = pad(at + cap);
+// the largest of every rank's values[i], for each of the n: n1k_comm_max_u64 (n = 1) and n1k_comm_max_u64_v
+n1k_status comm_max(n1k_comm* c, n1k_handle* h, uint32_t n, const uint64_t* values, uint64_t* out) {
+    n1k_status st = ensure_device(h);
+    if (st != N1K_OK) return st;
+    if (c->hub) {  // loopback: values through the hub, one at a time
+        for (uint32_t i = 0; i < n; i++) {
+            c->hub->val[c->rank] = values[i];
+            c->hub->barrier();
+            unsigned long long mx = 0;
+            for (int p = 0; p < c->world; p++) mx = std::max(mx, c->hub->val[p]);
+            c->hub->barrier();
+            out[i] = mx;
         }
+        return N1K_OK;
     }
-    return (at + 127) / 128 * 128;
+    HIP_TRY(h, c->scalar.ensure(2 * (size_t)kMaxParts));
+    HIP_TRY(h, hipMemcpyAsync(c->scalar.p, values, (size_t)n * 8, hipMemcpyHostToDevice, h->stream));
+    NCCL_TRY(c, ncclAllReduce(c->scalar.p, c->scalar.p + kMaxParts, n, ncclUint64, ncclMax, c->comm, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(out, c->scalar.p + kMaxParts, (size_t)n * 8, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return N1K_OK;
 }
 
 }  // namespace
@@ -504,23 +516,18 @@ n1k_status n1k_comm_create(const void* id, int rank, int world, int device, n1k_
     return guarded(nullptr, [&]() -> n1k_status {
         if (out) *out = nullptr;
         if (!id || !out || world < 1 || rank < 0 || rank >= world || world > (int)kMaxParts) return cfail(nullptr, N1K_INVALID, "bad communicator arguments");
-        auto* c = new n1k_comm();
+        std::unique_ptr<n1k_comm> c(new n1k_comm());  // (an early return releases whatever it holds by then)
         c->rank = rank;
         c->world = world;
         c->device = device;
-        auto bail = [&](n1k_status st) {
-            delete c;
-            return st;
-        };
-        if (hipSetDevice(device) != hipSuccess) return bail(cfail(nullptr, N1K_DEVICE_ERROR, "no HIP device %d", device));
+        if (hipSetDevice(device) != hipSuccess) return cfail(nullptr, N1K_DEVICE_ERROR, "no HIP device %d", device);
         ncclUniqueId u;
         memcpy(&u, id, sizeof u);
         ncclResult_t r = ncclCommInitRank(&c->comm, world, u, rank);
-        if (r != ncclSuccess) return bail(cfail(nullptr, N1K_DEVICE_ERROR, "ncclCommInitRank failed: %s", ncclGetErrorString(r)));
-        if (hipEventCreateWithFlags(&c->ev, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&c->ev_consumed, hipEventDisableTiming) != hipSuccess)
-            return bail(cfail(nullptr, N1K_DEVICE_ERROR, "hipEventCreate failed"));
-        if (c->scalar.ensure(2 * (size_t)kMaxParts) != hipSuccess) return bail(cfail(nullptr, N1K_OOM, "no device memory for the communicator"));  // (nothing of n1k_comm_max_u64 can fail before its collective)
-        *out = c;
+        if (r != ncclSuccess) return cfail(nullptr, N1K_DEVICE_ERROR, "ncclCommInitRank failed: %s", ncclGetErrorString(r));
+        if (!c->create_events()) return cfail(nullptr, N1K_DEVICE_ERROR, "hipEventCreate failed");
+        if (c->scalar.ensure(2 * (size_t)kMaxParts) != hipSuccess) return cfail(nullptr, N1K_OOM, "no device memory for the communicator");  // (nothing of n1k_comm_max_u64 can fail before its collective)
+        *out = c.release();
         return N1K_OK;
     });
 }
@@ -529,22 +536,23 @@ n1k_status n1k_comm_create_loopback(int world, int device, n1k_comm** out) {
     return guarded(nullptr, [&]() -> n1k_status {
         if (!out || world < 1 || world > (int)kMaxParts) return cfail(nullptr, N1K_INVALID, "bad communicator arguments");
         if (hipSetDevice(device) != hipSuccess) return cfail(nullptr, N1K_DEVICE_ERROR, "no HIP device %d", device);
-        auto* hub = new LoopHub();
+        auto hub = std::make_shared<LoopHub>();
         hub->world = world;
         hub->ptr.assign(world, nullptr);
         hub->stride.assign(world, 0);
         hub->val.assign(world, 0);
-        hub->refs = world;
+        std::vector<std::unique_ptr<n1k_comm>> ranks;  // (an early return releases the ranks made so far, the last of them the hub)
+        ranks.reserve(world);
         for (int r = 0; r < world; r++) {
-            auto* c = new n1k_comm();
+            ranks.emplace_back(new n1k_comm());
+            n1k_comm* c = ranks.back().get();
             c->rank = r;
             c->world = world;
             c->device = device;
             c->hub = hub;
-            (void)hipEventCreateWithFlags(&c->ev, hipEventDisableTiming);
-            (void)hipEventCreateWithFlags(&c->ev_consumed, hipEventDisableTiming);
-            out[r] = c;
+            if (!c->create_events()) return cfail(nullptr, N1K_DEVICE_ERROR, "hipEventCreate failed");
         }
+        for (int r = 0; r < world; r++) out[r] = ranks[r].release();
         return N1K_OK;
     });
 }
@@ -553,18 +561,7 @@ void n1k_comm_destroy(n1k_comm* c) {
     if (!c) return;
     try {
         (void)hipSetDevice(c->device);
-        if (c->hub) {
-            bool last;
-            {
-                std::lock_guard<std::mutex> lk(c->hub->mu);
-                last = --c->hub->refs == 0;
-            }
-            if (last) delete c->hub;
-        }
-        if (c->comm) (void)ncclCommDestroy(c->comm);
-        if (c->ev) (void)hipEventDestroy(c->ev);
-        if (c->ev_consumed) (void)hipEventDestroy(c->ev_consumed);
-        delete c;  // (its buffers with it)
+        delete c;
     } catch (...) {
     }
 }
@@ -576,26 +573,18 @@ int n1k_comm_world(const n1k_comm* c) { return c ? c->world : 0; }
 n1k_status n1k_comm_max_u64(n1k_comm* c, n1k_handle* h, uint64_t value, uint64_t* out) {
     return guarded(h, [&]() -> n1k_status {
         if (!c || !h || !out) return N1K_INVALID;
-        n1k_status st = ensure_device(h);
-        if (st != N1K_OK) return st;
-        if (c->hub) {  // loopback: values through the hub
-            c->hub->val[c->rank] = value;
-            c->hub->barrier();
-            unsigned long long mx = 0;
-            for (int p = 0; p < c->world; p++) mx = std::max(mx, c->hub->val[p]);
-            c->hub->barrier();
-            *out = mx;
-            return N1K_OK;
-        }
-        unsigned long long v = value, m = 0;
-        HIP_TRY(h, hipMemcpyAsync(c->scalar.p, &v, 8, hipMemcpyHostToDevice, h->stream));
-        NCCL_TRY(c, ncclAllReduce(c->scalar.p, c->scalar.p + 1, 1, ncclUint64, ncclMax, c->comm, h->stream));
-        HIP_TRY(h, hipMemcpyAsync(&m, c->scalar.p + 1, 8, hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        *out = m;
-        return N1K_OK;
+        return comm_max(c, h, 1, &value, out);
     });
 }
+
+n1k_status n1k_comm_max_u64_v(n1k_comm* c, n1k_handle* h, uint32_t n, const uint64_t* values, uint64_t* out) {
+    return guarded(h, [&]() -> n1k_status {
+        if (!c || !h || !values || !out || n == 0 || n > kMaxParts) return N1K_INVALID;
+        return comm_max(c, h, n, values, out);
+    });
+}
+
+}  // extern "C"
 
 // ---- one exchange step, failure-safe -------------------------------------------------------------------------------------
 //
@@ -625,31 +614,19 @@ n1k_status mark_consumed(n1k_comm* c, n1k_handle* rcv) {
     return N1K_OK;
 }
 
-// the regions of a rank whose local part failed: headers that hold nothing but the status.  Its usual buffers when they are
-// large enough (stride = region), else ONE scratch region that goes to every peer and one that every peer's region lands in.
-n1k_status void_regions(n1k_comm* c, n1k_handle* snd, size_t region, size_t header_bytes, uint32_t nsend, uint32_t nrecv, n1k_status status,
-                        const char** send, size_t* send_extent, size_t* send_stride, char** recv, size_t* recv_extent, size_t* recv_stride,
-                        bool recv_contiguous) {
-    if (c->send.n >= region * nsend && c->recv.n >= region * nrecv) {
-        *send = c->send.p;
-        *send_extent = c->send.n;
-        *send_stride = region;
-        *recv = c->recv.p;
-        *recv_extent = c->recv.n;
-        *recv_stride = region;
-    } else {
-        CHIP_TRY(c, c->void_send.ensure(region));
-        CHIP_TRY(c, c->void_recv.ensure(recv_contiguous ? region * nrecv : region));
-        *send = c->void_send.p;
-        *send_extent = c->void_send.n;
-        *send_stride = 0;
-        *recv = c->void_recv.p;
-        *recv_extent = c->void_recv.n;
-        *recv_stride = recv_contiguous ? region : 0;
-        nsend = 1;
+// the regions of a rank whose local part failed: headers that hold nothing but the status.  Its usual buffers when they hold
+// this step's regions, else ONE scratch region that goes to every peer and one that every peer's region lands in (n1k_wire.h).
+// Only a scratch region that cannot be had keeps the rank out of the collective: a header that could not be zeroed or stamped
+// still travels (staying out would leave the peers waiting).
+n1k_status void_wire(n1k_comm* c, n1k_handle* snd, const StepShape& s, size_t header_bytes, n1k_status status, Wire& w) {
+    if (!usual_buffers_hold(s, c->send.n, c->recv.n)) {
+        CHIP_TRY(c, c->void_send.ensure(scratch_send_bytes(s)));
+        CHIP_TRY(c, c->void_recv.ensure(scratch_recv_bytes(s)));
     }
-    for (uint32_t d = 0; d < nsend; d++) CHIP_TRY(c, hipMemsetAsync((char*)*send + (size_t)d * *send_stride, 0, header_bytes, snd->stream));
-    CHIP_TRY(c, launch_stamp_verdict((unsigned long long*)*send, nsend, *send_stride / 8, nullptr, (uint32_t)status, snd->stream));
+    w = voided_wire(s, c->send.p, c->send.n, c->recv.p, c->recv.n, c->void_send.p, c->void_send.n, c->void_recv.p, c->void_recv.n);
+    const uint32_t nsend = w.send_stride ? s.nsend : 1;
+    for (uint32_t d = 0; d < nsend; d++) (void)hipMemsetAsync((char*)w.send + (size_t)d * w.send_stride, 0, header_bytes, snd->stream);
+    (void)launch_stamp_verdict((unsigned long long*)w.send, nsend, w.send_stride / 8, nullptr, (uint32_t)status, snd->stream);
     return N1K_OK;
 }
 
@@ -660,58 +637,71 @@ bool injected(n1k_handle* h, uint32_t site) {
     return true;
 }
 
-// n1k_exchange_partials; `failed`: what the caller's own preparation of this step returned (n1k_partials_step)
-n1k_status exchange_partials_impl(n1k_comm* c, n1k_handle* sender, n1k_handle* receiver, uint64_t capacity_groups, int gathered, n1k_status failed) {
-    c->failure_broadcast = false;
-    sender->failure_global = false;
+// One exchange step: `s` says what it moves, the callables what the two exchanges differ in.
+//   local_part()         fills c->send
+//   receiving_part(self) the owner's work over what arrived (`self`: this rank's own region, where it lies in c->send;
+//                        copy_self: in c->recv, beside the others)
+// `local`: what this rank's preparation of the step returned so far (n1k_rows_step_v, n1k_partials_step; the rows front).
+template <class Local, class Receive>
+n1k_status exchange_step(n1k_comm* c, n1k_handle* sender, n1k_handle* receiver, n1k_status local, const StepShape& s, size_t header_bytes,
+                         bool copy_self, Local&& local_part, Receive&& receiving_part) {
+    c->failure_broadcast = sender->failure_global = false;
     n1k_status st = ensure_device(sender);
     if (st != N1K_OK) return st;  // (no device: this rank cannot take part in anything)
+    // 1. the local part, behind the previous exchange's readers.  From here on nothing returns before the collective.
     st = wait_consumed(c, sender);
-    if (st != N1K_OK) return fail(sender, st, "%s", c->last_error.c_str());
-    const size_t region = (size_t)n1k_partial_region_bytes(sender, capacity_groups);  // (a function of the plan alone)
-    const uint32_t P = (uint32_t)c->world, nsend = gathered ? 1u : P;
-    // 1. local part
-    n1k_status local = failed;
-    if (local == N1K_OK && sender->stop_flag.load()) local = fail(sender, N1K_STOPPED, "operator was stopped");
-    if (local == N1K_OK) {
-        local = prepare_receiver(sender, receiver);
-        if (local == N1K_INVALID && sender->last_error.empty()) fail(sender, local, "%s", receiver->last_error.c_str());
-    }
-    if (local == N1K_OK && injected(sender, 1)) local = fail(sender, N1K_OOM, "injected failure: buffers of the exchange");
-    if (local == N1K_OK) {
-        hipError_t e = c->send.ensure(region * nsend);
-        if (e == hipSuccess) e = c->recv.ensure(region * (size_t)P);
-        if (e != hipSuccess) local = fail(sender, e == hipErrorOutOfMemory ? N1K_OOM : N1K_DEVICE_ERROR, "buffers of the exchange: %s", hipGetErrorString(e));
-    }
-    if (local == N1K_OK) local = n1k_export_partials_async(sender, nsend, capacity_groups, c->send.p);
-    if (local == N1K_OK && injected(sender, 2)) local = fail(sender, N1K_DEVICE_ERROR, "injected failure: export of the partial groups");
-    // 2. the collective, always
-    const char* send = c->send.p;
-    char* recv = c->recv.p;
-    size_t sstride = region, rstride = region, sextent = c->send.n, rextent = c->recv.n;
-    if (local != N1K_OK) {
-        st = void_regions(c, sender, region, 16, nsend, P, local, &send, &sextent, &sstride, &recv, &rextent, &rstride, gathered != 0);
-        if (st != N1K_OK) return local;  // (not even one region: the peers are not told — see the comment above)
-    }
+    if (st != N1K_OK && local == N1K_OK) local = fail(sender, st, "%s", c->last_error.c_str());
+    if (local == N1K_OK) local = local_part();
+    // 2. ONE collective, always: from the usual buffers, or with nothing but this rank's status
+    Wire w = wire_of(s, c->send.p, c->send.n, c->recv.p, c->recv.n, false);
+    if (local != N1K_OK && void_wire(c, sender, s, header_bytes, local, w) != N1K_OK)
+        return local;  // (not even one region: the peers are not told — see the comment above)
     const char* self = nullptr;
-    if (gathered) st = all_gather_bytes(c, send, sextent, recv, rextent, region, sender->stream);
-    else st = all_to_all_regions(c, send, sextent, sstride, recv, rextent, rstride, region, sender->stream, &self);
+    st = s.gathered ? all_gather_bytes(c, w, sender->stream) : all_to_all_regions(c, w, sender->stream, &self);
     if (local != N1K_OK) {
-        c->failure_broadcast = st == N1K_OK;
-        sender->failure_global = st == N1K_OK;
+        c->failure_broadcast = sender->failure_global = st == N1K_OK;
         return local;
     }
     if (st != N1K_OK) return fail(sender, st, "%s", c->last_error.c_str());
-    // 3. the receiving part
-    if (!gathered)  // (this rank's own region joins the received ones by a device copy of G groups, not through the fabric)
-        HIP_TRY(sender, hipMemcpyAsync(c->recv.p + (size_t)c->rank * region, self, region, hipMemcpyDeviceToDevice, sender->stream));
-    st = order_streams(c, sender, receiver);
-    if (st != N1K_OK) return fail(sender, st, "%s", c->last_error.c_str());
-    if (injected(sender, 3)) return fail(sender, N1K_DEVICE_ERROR, "injected failure: the receiving part");
-    st = n1k_merge_partials_device(receiver, P, capacity_groups, c->recv.p);
+    // 3. the receiving part.  Its launches read c->send / c->recv: whichever way it ends, the next exchange waits behind them.
+    auto receive = [&]() -> n1k_status {
+        if (copy_self)  // (this rank's own region joins the received ones by a device copy, not through the fabric)
+            HIP_TRY(sender, hipMemcpyAsync(c->recv.p + (size_t)c->rank * s.region, self, s.region, hipMemcpyDeviceToDevice, sender->stream));
+        n1k_status r = order_streams(c, sender, receiver);
+        if (r != N1K_OK) return fail(sender, r, "%s", c->last_error.c_str());
+        if (injected(sender, 3)) return fail(sender, N1K_DEVICE_ERROR, "injected failure: the receiving part");
+        return receiving_part(self);
+    };
+    st = receive();
     (void)mark_consumed(c, receiver);
-    if (st != N1K_OK) return fail(sender, st, "receiver: %s", receiver->last_error.c_str());
-    return N1K_OK;
+    return st;
+}
+
+// n1k_exchange_partials: every destination's partial groups in one region (gathered: all of them in one, for everybody)
+n1k_status exchange_partials_impl(n1k_comm* c, n1k_handle* sender, n1k_handle* receiver, uint64_t capacity_groups, int gathered, n1k_status failed) {
+    StepShape s;
+    s.send_stride = s.region = (size_t)n1k_partial_region_bytes(sender, capacity_groups);  // (a function of the plan alone)
+    s.nrecv = (uint32_t)c->world;
+    s.nsend = gathered ? 1u : s.nrecv;
+    s.gathered = gathered != 0;
+    auto local_part = [&]() -> n1k_status {
+        if (sender->stop_flag.load()) return fail(sender, N1K_STOPPED, "operator was stopped");
+        n1k_status st = prepare_receiver(sender, receiver);
+        if (st == N1K_INVALID && sender->last_error.empty()) fail(sender, st, "%s", receiver->last_error.c_str());
+        if (st != N1K_OK) return st;
+        if (injected(sender, 1)) return fail(sender, N1K_OOM, "injected failure: buffers of the exchange");
+        hipError_t e = c->send.ensure(s.region * s.nsend);
+        if (e == hipSuccess) e = c->recv.ensure(s.region * s.nrecv);
+        if (e != hipSuccess) return fail(sender, e == hipErrorOutOfMemory ? N1K_OOM : N1K_DEVICE_ERROR, "buffers of the exchange: %s", hipGetErrorString(e));
+        st = n1k_export_partials_async(sender, s.nsend, capacity_groups, c->send.p);
+        if (st == N1K_OK && injected(sender, 2)) return fail(sender, N1K_DEVICE_ERROR, "injected failure: export of the partial groups");
+        return st;
+    };
+    auto receiving_part = [&](const char*) -> n1k_status {
+        const n1k_status st = n1k_merge_partials_device(receiver, s.nrecv, capacity_groups, c->recv.p);
+        return st == N1K_OK ? st : fail(sender, st, "receiver: %s", receiver->last_error.c_str());
+    };
+    return exchange_step(c, sender, receiver, failed, s, 16, !gathered, local_part, receiving_part);
 }
 
 // the column kinds of a batch are the plan's (and the ones seen before): what the size of a row region hangs on
@@ -724,14 +714,17 @@ bool batch_kinds_ok(const n1k_handle* h, const n1k_batch* b) {
     return true;
 }
 
+// n1k_exchange_rows_v: Filter + hash partition of a batch into one packed row region per destination, the owner's InitialGroup
+// over the regions it receives
 n1k_status exchange_rows_impl(n1k_comm* c, n1k_handle* sender, const n1k_batch* batch, n1k_handle* receiver, const uint64_t* capacity_rows,
                               n1k_status failed) {
-    c->failure_broadcast = false;
-    sender->failure_global = false;
+    // The front: what it refuses, it refuses on every rank alike (the arguments are the same everywhere), so returning before the
+    // collective leaves nobody waiting.
+    c->failure_broadcast = sender->failure_global = false;
     if (!sender->plan.has_group) return fail(sender, N1K_INVALID, "the row exchange partitions on group keys");
     n1k_status st = ensure_device(sender);
     if (st != N1K_OK) return st;  // (no device: this rank cannot take part in anything)
-    // 0. the size of a region: from the column kinds (of this batch, or as fixed by an earlier one)
+    // the size of a region: from the column kinds (of this batch, or as fixed by an earlier one)
     n1k_status local = failed;
     if (!batch_kinds_ok(sender, batch)) {
         if (!sender->layout_fixed)
@@ -745,40 +738,45 @@ n1k_status exchange_rows_impl(n1k_comm* c, n1k_handle* sender, const n1k_batch* 
     // Every destination has its own capacity (the same vector on every rank): the regions for owner d — one per sender — are
     // sized for what THAT owner receives, so a hot owner (skewed keys) does not inflate the regions of the other P - 1.
     const uint32_t P = (uint32_t)c->world;
-    const uint64_t quantum = 16ull * kRowSubs;  // kRowSubs sub-regions of whole 16-row groups
     std::vector<uint64_t> cap(P);
     uint64_t cap_max = 0;
     for (uint32_t d = 0; d < P; d++) {
-        if (capacity_rows[d] == 0) return fail(sender, N1K_INVALID, "a region capacity of zero rows");  // (the same on every rank)
-        cap[d] = (capacity_rows[d] + quantum - 1) / quantum * quantum;
+        if (capacity_rows[d] == 0) return fail(sender, N1K_INVALID, "a region capacity of zero rows");
+        cap[d] = quantum(capacity_rows[d]);
         cap_max = std::max(cap_max, cap[d]);
     }
-    if (cap_max >= (1ull << 31)) return fail(sender, N1K_INVALID, "row regions hold fewer than 2^31 rows");  // (the same on every rank)
-    std::vector<size_t> off_a, off_b, wire(P);
-    const size_t stride = row_region_layout(sender, cap_max, off_a, off_b);  // distance between the regions in the send buffer
-    for (uint32_t d = 0; d < P; d++) wire[d] = row_region_layout(sender, cap[d], off_a, off_b);
-    const uint64_t cap_me = cap[(uint32_t)c->rank];
-    const size_t region = row_region_layout(sender, cap_me, off_a, off_b);  // what this rank receives from every sender (off_*: its layout)
-    const size_t header = (size_t)kRowSubs * kCursorStride * 8;
-    st = wait_consumed(c, sender);
-    if (st != N1K_OK && local == N1K_OK) local = fail(sender, st, "%s", c->last_error.c_str());
-    // 1. local part: Filter + hash partition on the group key values into the packed regions (headers zeroed first)
+    if (cap_max >= (1ull << 31)) return fail(sender, N1K_INVALID, "row regions hold fewer than 2^31 rows");
+    // one layout for a region of cap_max rows (the sender's side, and the stride), one for this rank's own capacity (what it
+    // receives), and the bytes of a region by destination
+    const size_t nc = sender->plan.paths.size();
+    const RowLayout widest = row_region_layout(sender->col_kinds, nc, cap_max), mine = row_region_layout(sender->col_kinds, nc, cap[(uint32_t)c->rank]);
+    std::vector<size_t> wire(P);
+    for (uint32_t d = 0; d < P; d++) wire[d] = row_region_bytes(sender->col_kinds, nc, cap[d]);
+    StepShape s;
+    s.send_stride = widest.bytes;
+    s.region = mine.bytes;
+    s.nsend = s.nrecv = P;
+    s.send_bytes = wire.data();
+    c->sent_stride = widest.bytes;  // (n1k_exchange_sent_rows: the capacities follow once the local part has written the regions)
+    c->sent_cap.clear();
+    // Filter + hash partition on the group key values into the packed regions (headers zeroed first)
     auto local_part = [&]() -> n1k_status {
+        const size_t stride = s.send_stride;
         if (sender->stop_flag.load()) return fail(sender, N1K_STOPPED, "operator was stopped");
-        n1k_status s = validate_batch(sender, batch);
-        if (s != N1K_OK) return s;
-        s = prepare_receiver(sender, receiver);
-        if (s != N1K_OK) return s;
+        n1k_status st = validate_batch(sender, batch);
+        if (st != N1K_OK) return st;
+        st = prepare_receiver(sender, receiver);
+        if (st != N1K_OK) return st;
         if (injected(sender, 1)) return fail(sender, N1K_OOM, "injected failure: buffers of the exchange");
         HIP_TRY(sender, c->send.ensure(stride * P));
-        HIP_TRY(sender, c->recv.ensure(region * P));
-        for (uint32_t d = 0; d < P; d++) HIP_TRY(sender, hipMemsetAsync(c->send.p + (size_t)d * stride, 0, header, sender->stream));
-        s = bind_columns(sender, batch, true);
-        if (s != N1K_OK) return s;
-        s = ensure_rank(sender);
-        if (s != N1K_OK) return s;
-        s = ensure_match_table(sender);
-        if (s != N1K_OK) return s;
+        HIP_TRY(sender, c->recv.ensure(s.region * P));
+        for (uint32_t d = 0; d < P; d++) HIP_TRY(sender, hipMemsetAsync(c->send.p + (size_t)d * stride, 0, kRowHeaderBytes, sender->stream));
+        st = bind_columns(sender, batch, true);
+        if (st != N1K_OK) return st;
+        st = ensure_rank(sender);
+        if (st != N1K_OK) return st;
+        st = ensure_match_table(sender);
+        if (st != N1K_OK) return st;
         PartArgs A{};
         A.nrows = batch->nrows;
         A.capacity = cap_max;
@@ -788,19 +786,16 @@ n1k_status exchange_rows_impl(n1k_comm* c, n1k_handle* sender, const n1k_batch* 
         A.count_stride = (uint32_t)(stride / 8);
         A.region_bytes = stride;
         A.sub_rows = cap_max / kRowSubs;
-        bool uniform = true;
-        for (uint32_t d = 0; d < P; d++) uniform &= cap[d] == cap_max;
-        A.hdr_bytes = (uint32_t)header;
+        const bool uniform = *std::min_element(cap.begin(), cap.end()) == cap_max;
+        A.hdr_bytes = (uint32_t)kRowHeaderBytes;
         if (uniform) {
             // every destination alike (uniform keys; one rank): the kernels' plain addressing — one layout, region d a whole number
             // of strides further on — which spares them the per-destination tables (0.43 against 0.46 ms per 100 M rows)
-            std::vector<size_t> oa, ob;
-            (void)row_region_layout(sender, cap_max, oa, ob);
             for (uint32_t i = 0; i < A.ncopy; i++) {
-                if (sender->col_kinds[i] == N1K_COL_DICT32) A.out_codes[i] = (uint32_t*)(c->send.p + oa[i]);
+                if (sender->col_kinds[i] == N1K_COL_DICT32) A.out_codes[i] = (uint32_t*)(c->send.p + widest.a[i]);
                 else {
-                    A.out_payload[i] = (uint64_t*)(c->send.p + oa[i]);
-                    A.out_tags[i] = (uint8_t*)(c->send.p + ob[i]);
+                    A.out_payload[i] = (uint64_t*)(c->send.p + widest.a[i]);
+                    A.out_tags[i] = (uint8_t*)(c->send.p + widest.b[i]);
                 }
             }
         } else {
@@ -808,113 +803,63 @@ n1k_status exchange_rows_impl(n1k_comm* c, n1k_handle* sender, const n1k_batch* 
             for (uint32_t d = 0; d < P; d++) A.dest_cap[d] = (uint32_t)cap[d];
         }
         A.err_flags = sender->groups.errp;
-        s = run_partition(sender, batch, A);
-        if (s != N1K_OK) return s;
+        st = run_partition(sender, batch, A);
+        if (st != N1K_OK) return st;
         if (injected(sender, 2)) return fail(sender, N1K_DEVICE_ERROR, "injected failure: the partition");
         sender->timing.stats.rows_in += batch->nrows;
         sender->timing.stats.batches += 1;
         // what the partition itself found (rows whose key does not pack, values the Filter cannot order) joins the verdicts
         HIP_TRY(sender, launch_stamp_verdict((unsigned long long*)c->send.p, P, stride / 8, sender->groups.errp, 0, sender->stream));
+        c->sent_cap = cap;
         return N1K_OK;
     };
-    if (local == N1K_OK) local = local_part();
-    c->sent_stride = stride;
-    c->sent_cap = cap;
-    // 2. ONE all-to-all, always: counts, verdicts and rows of every column travel in the same region
-    const char* send = c->send.p;
-    char* recv = c->recv.p;
-    size_t sstride = stride, rstride = region, sextent = c->send.n, rextent = c->recv.n;
-    if (local != N1K_OK) {
-        c->sent_cap.clear();
-        if (c->send.n >= stride * P && c->recv.n >= region * P) {
-            for (uint32_t d = 0; d < P; d++) (void)hipMemsetAsync(c->send.p + (size_t)d * stride, 0, header, sender->stream);
-            (void)launch_stamp_verdict((unsigned long long*)c->send.p, P, stride / 8, nullptr, (uint32_t)local, sender->stream);
-        } else {
-            // the usual buffers do not hold P regions of this step's stride (they were sized by a step of smaller capacities, or
-            // not at all): asking void_regions for all P of them takes it to its scratch regions, whatever the buffers do hold
-            st = void_regions(c, sender, stride, header, P, P, local, &send, &sextent, &sstride, &recv, &rextent, &rstride, false);
-            if (st != N1K_OK) return local;  // (not even one region: the peers are not told — see the comment above)
-        }
-    }
-    const char* self = nullptr;
-    st = all_to_all_regions(c, send, sextent, sstride, recv, rextent, rstride, region, sender->stream, &self, wire.data());
-    if (local != N1K_OK) {
-        c->failure_broadcast = st == N1K_OK;
-        sender->failure_global = st == N1K_OK;
-        return local;
-    }
-    if (st != N1K_OK) return fail(sender, st, "%s", c->last_error.c_str());
-    st = order_streams(c, sender, receiver);
-    if (st != N1K_OK) return fail(sender, st, "%s", c->last_error.c_str());
-    // 3. the owner's InitialGroup over what it received: one batch per source, each with its row count on the device.
-    //    (Headers are checked first: a sender that overflowed, dropped rows or failed voids the step on every rank.)
-    std::vector<const char*> src(P);
-    for (uint32_t sidx = 0; sidx < P; sidx++) src[sidx] = (int)sidx == c->rank ? self : c->recv.p + (size_t)sidx * region;
-    {
+    // the owner's InitialGroup over what it received: one batch per source, each with its row count on the device.
+    // (Headers are checked first: a sender that overflowed, dropped rows or failed voids the step on every rank.)
+    auto receiving_part = [&](const char* self) -> n1k_status {
+        std::vector<const char*> src(P);
         HeaderList H{};
-        for (uint32_t sidx = 0; sidx < P; sidx++) H.h[sidx] = (unsigned long long*)src[sidx];
+        for (uint32_t sidx = 0; sidx < P; sidx++) {
+            src[sidx] = (int)sidx == c->rank ? self : c->recv.p + (size_t)sidx * s.region;
+            H.h[sidx] = (unsigned long long*)src[sidx];
+        }
         HIP_TRY(receiver, launch_exchange_verdict(H, P, receiver->groups.errp, receiver->stream));
-    }
-    if (injected(sender, 3)) return fail(sender, N1K_DEVICE_ERROR, "injected failure: the receiving part");
-    for (uint32_t sidx = 0; sidx < P; sidx++) {
+        // the receiver's columns are the sender's in another order (prepare_receiver checked that each exists)
         const uint32_t rnc = (uint32_t)receiver->plan.paths.size();
+        std::vector<int> from(rnc);
         std::vector<n1k_col> cols(std::max<size_t>(1, rnc));
         for (uint32_t i = 0; i < rnc; i++) {
-            const int j = sender_column(sender, receiver->plan.paths[i]);  // (prepare_receiver checked that it exists)
-            cols[i].kind = sender->col_kinds[j];
-            if (cols[i].kind == N1K_COL_DICT32) cols[i].codes = (const uint32_t*)(src[sidx] + off_a[j]);
-            else {
-                cols[i].payload = (const uint64_t*)(src[sidx] + off_a[j]);
-                cols[i].tags = (const uint8_t*)(src[sidx] + off_b[j]);
+            from[i] = sender_column(sender, receiver->plan.paths[i]);
+            cols[i].kind = sender->col_kinds[from[i]];
+        }
+        const uint64_t cap_me = cap[(uint32_t)c->rank];
+        for (uint32_t sidx = 0; sidx < P; sidx++) {
+            for (uint32_t i = 0; i < rnc; i++) {
+                if (cols[i].kind == N1K_COL_DICT32) cols[i].codes = (const uint32_t*)(src[sidx] + mine.a[from[i]]);
+                else {
+                    cols[i].payload = (const uint64_t*)(src[sidx] + mine.a[from[i]]);
+                    cols[i].tags = (const uint8_t*)(src[sidx] + mine.b[from[i]]);
+                }
             }
+            n1k_batch rb{};
+            rb.nrows = cap_me;
+            rb.ncols = rnc;
+            rb.cols = cols.data();
+            receiver->push_seg_counts = (const unsigned long long*)src[sidx];  // (the region's header)
+            receiver->push_nseg = kRowSubs;
+            receiver->push_seg_rows = cap_me / kRowSubs;
+            const n1k_status st = push_device(receiver, &rb);
+            receiver->push_seg_counts = nullptr;
+            receiver->push_nseg = 0;
+            if (st != N1K_OK) return fail(sender, st, "receiver: %s", receiver->last_error.c_str());
         }
-        n1k_batch rb{};
-        rb.nrows = cap_me;
-        rb.ncols = rnc;
-        rb.cols = cols.data();
-        receiver->push_seg_counts = (const unsigned long long*)src[sidx];  // (the region's header)
-        receiver->push_nseg = kRowSubs;
-        receiver->push_seg_rows = cap_me / kRowSubs;
-        st = push_device(receiver, &rb);
-        receiver->push_seg_counts = nullptr;
-        receiver->push_nseg = 0;
-        if (st != N1K_OK) {
-            (void)mark_consumed(c, receiver);
-            return fail(sender, st, "receiver: %s", receiver->last_error.c_str());
-        }
-    }
-    (void)mark_consumed(c, receiver);
-    return N1K_OK;
+        return N1K_OK;
+    };
+    return exchange_step(c, sender, receiver, local, s, kRowHeaderBytes, false, local_part, receiving_part);
 }
 
 }  // namespace
 
-n1k_status n1k_comm_max_u64_v(n1k_comm* c, n1k_handle* h, uint32_t n, const uint64_t* values, uint64_t* out) {
-    return guarded(h, [&]() -> n1k_status {
-        if (!c || !h || !values || !out || n == 0 || n > kMaxParts) return N1K_INVALID;
-        n1k_status st = ensure_device(h);
-        if (st != N1K_OK) return st;
-        if (c->hub) {  // loopback: values through the hub, one at a time
-            for (uint32_t i = 0; i < n; i++) {
-                c->hub->val[c->rank] = values[i];
-                c->hub->barrier();
-                unsigned long long mx = 0;
-                for (int p = 0; p < c->world; p++) mx = std::max(mx, c->hub->val[p]);
-                c->hub->barrier();
-                out[i] = mx;
-            }
-            return N1K_OK;
-        }
-        HIP_TRY(h, c->scalar.ensure(2 * (size_t)kMaxParts));
-        std::vector<unsigned long long> m(n);
-        HIP_TRY(h, hipMemcpyAsync(c->scalar.p, values, (size_t)n * 8, hipMemcpyHostToDevice, h->stream));
-        NCCL_TRY(c, ncclAllReduce(c->scalar.p, c->scalar.p + kMaxParts, n, ncclUint64, ncclMax, c->comm, h->stream));
-        HIP_TRY(h, hipMemcpyAsync(m.data(), c->scalar.p + kMaxParts, (size_t)n * 8, hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        for (uint32_t i = 0; i < n; i++) out[i] = m[i];
-        return N1K_OK;
-    });
-}
+extern "C" {
 
 n1k_status n1k_exchange_partials(n1k_comm* c, n1k_handle* sender, n1k_handle* receiver, uint64_t capacity_groups, int gathered) {
     return guarded(sender, [&]() -> n1k_status {
@@ -1054,7 +999,7 @@ n1k_status n1k_gather_groups_status(n1k_comm* c, n1k_handle* h, const n1k_result
             HIP_TRY(h, c->gsend.ensure(slot));
             HIP_TRY(h, c->grecv.ensure(slot * (size_t)c->world));
             HIP_TRY(h, hipMemcpyAsync(c->gsend.p, stage.data(), slot, hipMemcpyHostToDevice, h->stream));
-            st = all_gather_bytes(c, c->gsend.p, c->gsend.n, c->grecv.p, c->grecv.n, slot, h->stream);
+            st = all_gather_bytes(c, Wire{c->gsend.p, c->gsend.n, slot, c->grecv.p, c->grecv.n, slot, slot, nullptr}, h->stream);
             if (st != N1K_OK) return fail(h, st, "%s", c->last_error.c_str());
             c->ghost.resize(slot * (size_t)c->world);
             HIP_TRY(h, hipMemcpyAsync(c->ghost.data(), c->grecv.p, c->ghost.size(), hipMemcpyDeviceToHost, h->stream));

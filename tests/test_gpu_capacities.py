@@ -327,7 +327,7 @@ def test_export_partials_at_exact_and_short_capacities(shape, nparts):
 # 2. protocol level: overflow, retry and growth over the loopback transport
 # ---------------------------------------------------------------------------------------------------------------------
 
-QUANTUM = 128  # n1k_exchange.cpp exchange_rows_impl: capacities are rounded up to kRowSubs sub-regions of whole 16-row groups
+QUANTUM = 128  # n1k_wire.h quantum: capacities are rounded up to kRowSubs sub-regions of whole 16-row groups
 
 
 def _round_up(x, q=QUANTUM):

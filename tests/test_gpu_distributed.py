@@ -868,3 +868,154 @@ def test_skewed_keys_size_each_owners_regions_on_their_own():
         assert max(uni) <= 1.25 * min(uni), uni                      # uniform keys: every owner alike
         assert max(zpf) >= 1.5 * min(zpf), zpf                       # Zipf: the hot owner's regions are the large ones ...
         assert sum(zpf) <= 1.3 * sum(uni), (sum(zpf), sum(uni))      # ... and only they: a rank ships about what it shipped before
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the communicator's small calls, and the refusals every rank makes alike
+# ---------------------------------------------------------------------------------------------------------------------
+
+# per rank (rows) the five values it offers: distinct per rank, 0 and 2^63 + 1 among them (an unsigned maximum)
+MAX_VALUES = [[0, 2**63 + 1, 17, 2**40, 3],
+              [2**63 + 1, 0, 18, 2**40 + 1, 2],
+              [5, 1, 2**64 - 1, 0, 2**63]]
+
+
+def _max_both_ways(comm, h, mine):
+    """n1k_comm_max_u64 of every value of `mine`, n1k_comm_max_u64_v of the first alone (n = 1) and of all of them (n = 5)."""
+    lib = h._lib
+    single = []
+    for v in mine:
+        out = C.c_uint64()
+        h._check(lib.n1k_comm_max_u64(comm._h, h._h, v, C.byref(out)))
+        single.append(int(out.value))
+    one_in, one_out = (C.c_uint64 * 1)(mine[0]), (C.c_uint64 * 1)()
+    h._check(lib.n1k_comm_max_u64_v(comm._h, h._h, 1, one_in, one_out))
+    all_in, all_out = (C.c_uint64 * len(mine))(*mine), (C.c_uint64 * len(mine))()
+    h._check(lib.n1k_comm_max_u64_v(comm._h, h._h, len(mine), all_in, all_out))
+    return single, int(one_out[0]), [int(x) for x in all_out]
+
+
+@pytest.mark.timeout(300)
+def test_comm_max_u64_and_its_vector_form_agree():
+    """n1k_comm_max_u64 is n1k_comm_max_u64_v with n = 1: world 3 over the loopback transport, every rank offering other
+    values (0 and 2^63 + 1 among them), with n = 1 and n = 5; then once over RCCL at world size 1."""
+    import torch
+    import torch.distributed as dist
+    from query_amd import distributed as qd
+    world = 3
+    comms = qd.Comm.loopback(world, 0)
+    want = [max(MAX_VALUES[r][i] for r in range(world)) for i in range(5)]
+
+    def rank_body(r):
+        h = query_amd.GpuFilterGroup(plan.filter_group_plan(COND, KEYS, AGGS))
+        got = _max_both_ways(comms[r], h, MAX_VALUES[r])
+        h.done()
+        return got
+
+    for single, one, vec in _run_ranks(world, rank_body):
+        assert single == want and one == want[0] and vec == want, (single, one, vec, want)
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    port = s.getsockname()[1]
+    s.close()
+    os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
+    dist.init_process_group("nccl", init_method="tcp://127.0.0.1:%d" % port, rank=0, world_size=1,
+                            device_id=torch.device("cuda", 0))
+    try:
+        comm = qd.Comm(0, 1, 0)
+        h = query_amd.GpuFilterGroup(plan.filter_group_plan(COND, KEYS, AGGS))
+        for mine in MAX_VALUES:
+            single, one, vec = _max_both_ways(comm, h, mine)
+            assert single == mine and one == mine[0] and vec == mine, (single, one, vec, mine)
+        h.done()
+        comm.done()
+    finally:
+        dist.destroy_process_group()
+
+
+def _rows_step_v(op, rows_n, dev, caps):
+    """One n1k_rows_step_v with the capacities given: (status, worst status, the handles' messages, groups or None)."""
+    from query_amd.gpu_operator import GroupRows
+    lib = op.sender._lib
+    batch = op._batch(rows_n, dev)
+    arr = (C.c_uint64 * op.world)(*[int(c) for c in caps])
+    out, worst = _ffi.Result(), C.c_int(0)
+    st = int(lib.n1k_rows_step_v(op.comm._h, op.sender._h, C.byref(batch[0]), op.receiver._h, op.merger._h, arr, C.byref(out), C.byref(worst)))
+    msg = " | ".join((lib.n1k_last_error(h._h) or b"").decode(errors="replace") for h in (op.sender, op.receiver, op.merger))
+    rows = None
+    if st == _ffi.OK and worst.value == 0:
+        raw, cache = op._result_dict(out), {}
+        rows = GroupRows(raw["nkeys"], raw["naggs"], op.merger._py_values(raw["keys"], cache), op.merger._py_values(raw["aggs"], cache), [])
+    return st, worst.value, msg, rows
+
+
+def _sent_rows(op):
+    lib = op.sender._lib
+    sent = (C.c_uint64 * op.world)()
+    st = int(lib.n1k_exchange_sent_rows(op.comm._h, op.sender._h, sent))
+    return st, (lib.n1k_last_error(op.sender._h) or b"").decode(errors="replace"), [int(x) for x in sent]
+
+
+@pytest.mark.timeout(300)
+def test_exchange_sent_rows_before_after_a_voided_and_after_a_good_step():
+    """n1k_exchange_sent_rows at world 2 over 4000 rows: N1K_INVALID ("no completed row exchange") on a communicator that has
+    exchanged nothing, the same on the rank that voided its step (inject_failure = 1: no regions of its own were written), and
+    after a good step what the ranks wrote per destination adds up to the oracle's surviving rows — destination d's share to
+    what owner d aggregated."""
+    from query_amd import distributed as qd
+    world, bad, n = 2, 1, 4000
+    t = n1o.synth_table(n, k_cat=37)
+    aggs = sorted(["count(*)", "sum(%s)" % D("price")])
+    ora = n1o.run(t, COND, KEYS, aggs)
+    comms = qd.Comm.loopback(world, 0)
+    shards, keep = _shards(t, _paths(COND, KEYS, aggs), world)
+
+    def rank_body(r):
+        op = qd.ShardedFilterGroup(COND, KEYS, aggs, t.dictionary, r, world, 0, comm=comms[r])
+        rows_n, dev = shards[r]
+        before = _sent_rows(op)
+        if r == bad:
+            op.sender.set_option("inject_failure", 1)
+        voided = _rows_step_v(op, rows_n, dev, [4096] * world)
+        after_voided = _sent_rows(op)
+        good = _rows_step_v(op, rows_n, dev, [4096] * world)
+        return before, voided, after_voided, good, _sent_rows(op), int(op.receiver.stats()["rows_selected"])
+
+    outs = _run_ranks(world, rank_body)
+    for r, (before, voided, after_voided, good, after_good, _recv) in enumerate(outs):
+        assert before[0] == _ffi.INVALID and "no completed row exchange" in before[1], (r, before)
+        assert voided[0] == _ffi.OOM, (r, voided[:3])
+        if r == bad:
+            assert after_voided[0] == _ffi.INVALID and "no completed row exchange" in after_voided[1], after_voided
+        assert (good[0], good[1]) == (_ffi.OK, 0), (r, good[:3])
+        pu.assert_same_groups(good[3], ora, aggs=aggs)
+        assert after_good[0] == _ffi.OK, (r, after_good)
+    for d in range(world):
+        assert sum(o[4][2][d] for o in outs) == outs[d][5]  # what was written for owner d is what owner d aggregated
+    assert sum(sum(o[4][2]) for o in outs) == ora.rows_passed
+
+
+@pytest.mark.timeout(300)
+@pytest.mark.parametrize("bad,text", [([4096, 0], "a region capacity of zero rows"), ([2**31, 4096], "row regions hold fewer than 2^31 rows")],
+                         ids=["zero-rows", "2^31-rows"])
+def test_a_capacity_every_rank_refuses_alike_blocks_nobody(bad, text):
+    """A capacity vector that is refused before the collective — a destination of 0 rows, one of 2^31 — is the same on every
+    rank: world 2, every rank gets N1K_INVALID with the refusal's text, nobody waits for anybody, and a good step on the same
+    communicator afterwards gives the oracle's groups."""
+    from query_amd import distributed as qd
+    world, n = 2, 4000
+    t = n1o.synth_table(n, k_cat=37)
+    aggs = sorted(["count(*)", "sum(%s)" % D("price")])
+    ora = n1o.run(t, COND, KEYS, aggs)
+    comms = qd.Comm.loopback(world, 0)
+    shards, keep = _shards(t, _paths(COND, KEYS, aggs), world)
+
+    def rank_body(r):
+        op = qd.ShardedFilterGroup(COND, KEYS, aggs, t.dictionary, r, world, 0, comm=comms[r])
+        rows_n, dev = shards[r]
+        return _rows_step_v(op, rows_n, dev, bad), _rows_step_v(op, rows_n, dev, [4096] * world)
+
+    for refused, good in _run_ranks(world, rank_body):
+        assert refused[0] == _ffi.INVALID and text in refused[2], refused[:3]
+        assert (good[0], good[1]) == (_ffi.OK, 0), good[:3]
+        pu.assert_same_groups(good[3], ora, aggs=aggs)
