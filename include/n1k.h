@@ -33,7 +33,9 @@ extern "C" {
 #endif
 
 #define N1K_ABI_VERSION 3 /* 2: n1k_result.nproj / proj, projection and communicator entry points; 3: n1k_stats.query_ms,
-                             N1K_REGION_FULL, n1k_partials_step, n1k_failure_is_global */
+                             N1K_REGION_FULL, n1k_partials_step, n1k_failure_is_global.  Entry points that only add to the ABI
+                             (the Filter-only calls, n1k_order_key, n1k_rowdistinct_stats) and new plan forms leave it at 3: no
+                             struct changed its layout and no call its meaning */
 
 /* ---------------------------------------------------------------- status -- */
 
@@ -199,6 +201,21 @@ typedef struct n1k_handle n1k_handle;
  *     and InitialProject / FinalProject in a plan without a group (the caller projects with n1k_gather_selected) are
  *     N1K_UNSUPPORTED.  Such a plan runs through n1k_filter_device_batch alone: n1k_push_batch, n1k_push_device_batch,
  *     n1k_push_json and n1k_run_device_batch answer N1K_UNSUPPORTED.
+ *   {"#operator":"Sequence","~children":[                                                     (SELECT DISTINCT over the rows,
+ *        {"#operator":"Parallel","~child":{"#operator":"Sequence","~children":[                planner/build_select_sub.go:217-240,
+ *             {"#operator":"Filter",…},                                                        plan/project.go:69-108,
+ *             {"#operator":"InitialProject","distinct":true,"result_terms":[{"expr":"…","as":"…"}]},   plan/distinct.go:32-40:
+ *             {"#operator":"Distinct"}, {"#operator":"FinalProject"}]}},                       n1k_filter_device_batch)
+ *        {"#operator":"Distinct"}, Order, Offset, Limit, {"#operator":"FinalProject"}]}
+ *     also bare, without the outer Sequence or the Parallel; the Filter, the FinalProjects and the tail are optional, the two
+ *     Distinct nodes are one stage.  1 to 4 result terms, each a leaf path of the row in the text form a condition uses, each
+ *     with an optional alias (n1k_num_projection_terms / n1k_projection_expr / n1k_projection_alias report them); their paths
+ *     join the plan's columns behind the condition's and before the sort terms', none twice.  A sort term is a leaf path or
+ *     `alias`, which names a result term — by its explicit alias, else by the last field name of its path — and resolves to that
+ *     term's path.  Without Filter every row is a survivor.  Expressions, functions or constants as terms, star or raw
+ *     projections, more than 4 terms, a Distinct without the InitialProject{distinct} before it or after Order / Offset / Limit,
+ *     an InitialProject{distinct} that no Distinct follows, and distinct over groups are N1K_UNSUPPORTED; so is an InitialProject
+ *     without distinct in a plan without a group.  One batch through n1k_filter_device_batch, as for the ordered plans.
  *   {"#operator":"Parallel","~child":<one of the above>, "maxParallelism":n}
  *   {"#operator":"Sequence","~children":[<one of the above>, IntermediateGroup, FinalGroup,      (the grouped tail:
  *        {"#operator":"Filter","condition":"…"},                                       HAVING, plan/filter.go
@@ -245,8 +262,9 @@ uint32_t n1k_num_aggregates(const n1k_handle *h);
  * attachment map (execution/group_initial.go:74-79). */
 const char *n1k_aggregate_name(const n1k_handle *h, uint32_t i);
 
-/* Result terms of the plan's InitialProject (0 when it has none): expression text and explicit alias ("" = none; the
- * caller derives one as algebra.ResultTerm does: the last name of a path, else $1, $2, ...). */
+/* Result terms of the plan's InitialProject — over the final groups, or the one of a DISTINCT over the rows — (0 when it has
+ * none): expression text and explicit alias ("" = none; the caller derives one as algebra.ResultTerm does: the last name of
+ * a path, else $1, $2, ...). */
 uint32_t n1k_num_projection_terms(const n1k_handle *h);
 const char *n1k_projection_expr(const n1k_handle *h, uint32_t i);
 const char *n1k_projection_alias(const n1k_handle *h, uint32_t i);
@@ -275,6 +293,9 @@ n1k_status n1k_dict_get(const n1k_handle *h, uint32_t code, const char **ptr, si
  *         partitioned high-cardinality path: batches of at least min_rows (8 Mi) rows whose first probe_rows (512 Ki) rows
  *         bring at least min_groups (4096) new groups; forced number of passes), "topk_min_groups" (ORDER BY ... LIMIT: the device top-k filter runs from this many groups on, default 65536),
  *         "distinct_set_slots" / "distinct_levels" (LDS set size, forced number of partition passes: tests),
+ *         "rowdistinct_slots" (DISTINCT over rows: forced capacity of the table of ordinals, any value >= 1, not rounded; 0 = the
+ *         next power of two >= 2 x survivors: tests) / "rowdistinct_lds_slots" (size of an LDS set ahead of it that passes on only the smallest
+ *         ordinal a workgroup has met of a key, at most 4096; default 0 = none),
  *         "distinct_region_cap" (forced capacity of the specialised scan's hash regions: tests), "dedupe_block" (256 / 512 / 1024: tuning), "wide_values" (before the first push: how many distinct float / wide-integer group key
  *         values the handle can code, default 1<<20; 0 = such keys are N1K_UNSUPPORTED_DATA),
  *         "inject_failure" (tests of the multi-GPU failure rules, one shot, on the SENDING handle: the next exchange call
@@ -352,8 +373,27 @@ typedef struct n1k_selection {
  * first when that is fewer rows than were selected and at least "topk_min_groups" were — behind a few more small waits.
  * An ARRAY or OBJECT met as a sort value: N1K_UNSUPPORTED_DATA.  n1k_get_stats: rows_in, rows_selected = the cut count,
  * topk_candidates = the rows the select passed on to the sort (0: it did not run).
+ *
+ * A plan with Distinct (n1k_create): between the Filter and the tail the survivors are de-duplicated on the device (≙
+ * execution/distinct.go:60-71, whose set is keyed by the JSON text of the projected object, value/set.go:100-103).  Two rows
+ * are equal when every result term is: a MISSING term is left out of the object, so MISSING != NULL; FALSE, TRUE and NULL are
+ * each a value of their own; numbers are equal when numerically equal, compared exactly — INT 2 = FLOAT 2.0 and -0.0 = 0.0 =
+ * INT 0 (value/float.go:41-45), INT 2^53+1 != FLOAT 2^53, INT 2^63-1 != FLOAT 2^63; STRING / ARRAY / OBJECT are equal by
+ * dictionary code within the same tag.  Divergence: all NaNs are one value and each infinity its own, where the reference
+ * would also collide them with the strings "NaN" / "+Infinity" / "-Infinity" (value/float.go:31-39).  The representative of
+ * a distinct row is the survivor with the smallest ordinal (the reference keeps whichever a Parallel copy met first: any is
+ * admissible there).  Without Order the selection is the representatives in ascending ordinal; with Order the sort terms
+ * are read at the representative; Offset / Limit cut after that; nselected and rows_selected are the counts after the cut.
+ * n1k_selected_to_host32 and n1k_gather_selected work on the result as on any selection.  The table of ordinals takes the
+ * next power of two >= 2 x survivors slots ("rowdistinct_slots" forces another capacity); a table with no room: N1K_OOM, the
+ * handle as after n1k_reset.  One more wait, for the representatives' count.
  */
 n1k_status n1k_filter_device_batch(n1k_handle *h, const n1k_batch *batch, n1k_selection *out);
+
+/* Diagnostics of the last DISTINCT over rows of this handle: out[0] survivors of the Filter, [1] distinct rows before the
+ * cut, [2] slots of the table, [3] rows that reached the table (all of them, unless "rowdistinct_lds_slots" is set: the others then
+ * fell to a smaller ordinal of their key in the LDS set of their workgroup). */
+n1k_status n1k_rowdistinct_stats(const n1k_handle *h, uint64_t out[4]);
 
 /* The last selection's ordinals to the caller's host buffer (pinned or not) of `capacity` entries: 4 bytes per survivor of
  * execution/filter.go:49-61, one copy, one wait.  N1K_INVALID: no selection, or capacity below nselected. */

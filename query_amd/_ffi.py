@@ -91,7 +91,7 @@ SYMBOLS = [
     "n1k_in_match", "n1k_in_match_device", "n1k_in_stats",
     "n1k_strfn_eval", "n1k_strfn_eval_device", "n1k_strfn_stats",
     "n1k_device_bytes_live",
-    "n1k_filter_device_batch", "n1k_selected_to_host32", "n1k_gather_selected", "n1k_order_key",
+    "n1k_filter_device_batch", "n1k_selected_to_host32", "n1k_gather_selected", "n1k_order_key", "n1k_rowdistinct_stats",
 ]
 
 _lib = None
@@ -272,6 +272,9 @@ def lib():
     if hasattr(L, "n1k_order_key"):  # (idem)
         L.n1k_order_key.restype = C.c_int
         L.n1k_order_key.argtypes = [C.c_uint32, C.c_uint64, C.c_uint32, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
+    if hasattr(L, "n1k_rowdistinct_stats"):  # (idem)
+        L.n1k_rowdistinct_stats.restype = C.c_int
+        L.n1k_rowdistinct_stats.argtypes = [H, C.POINTER(C.c_uint64 * 4)]
     L.n1k_abi_version.restype = C.c_int
     L.n1k_device_count.restype = C.c_int
     _lib = L

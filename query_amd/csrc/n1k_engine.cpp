@@ -784,11 +784,14 @@ const char* n1k_aggregate_name(const n1k_handle* h, uint32_t i) {
     return (h && i < h->agg_names.size()) ? h->agg_names[i].c_str() : nullptr;
 }
 
-uint32_t n1k_num_projection_terms(const n1k_handle* h) { return h ? (uint32_t)h->plan.project.size() : 0; }
+// (a plan has either the InitialProject over its groups or the one of a DISTINCT over its rows)
+uint32_t n1k_num_projection_terms(const n1k_handle* h) { return h ? (uint32_t)(h->plan.project.size() + h->plan.row_distinct.size()) : 0; }
 const char* n1k_projection_expr(const n1k_handle* h, uint32_t i) {
+    if (h && i < h->plan.row_distinct.size()) return h->plan.row_distinct[i].text.c_str();
     return (h && i < h->plan.project.size()) ? h->plan.project[i].text.c_str() : nullptr;
 }
 const char* n1k_projection_alias(const n1k_handle* h, uint32_t i) {
+    if (h && i < h->plan.row_distinct.size()) return h->plan.row_distinct[i].as.c_str();
     return (h && i < h->plan.project.size()) ? h->plan.project[i].as.c_str() : nullptr;
 }
 
@@ -919,7 +922,7 @@ n1k_status n1k_set_option(n1k_handle* h, const char* name, int64_t value) {
         h->has_distinct = false;
         h->n_distinct = 0;
         if (!compile_plan(h, err)) return fail(h, N1K_INVALID, "%s", err.msg.c_str());
-    } else
+    } else if (!rowdistinct_option(h, n, value))  // (the DISTINCT stage's own options: n1k_rowdistinct.cpp)
         return fail(h, N1K_INVALID, "unknown option %s", name);
     return N1K_OK;
     });
@@ -935,7 +938,7 @@ n1k_status n1k_push_device_batch(n1k_handle* h, const n1k_batch* batch) {
 
 n1k_status n1k_run_device_batch(n1k_handle* h, const n1k_batch* batch, n1k_result* out) {
     if (!h || !batch || !out) return N1K_INVALID;
-    if (h->plan.ordered_rows()) return guarded(h, [&]() -> n1k_status { return refuse_ordered_rows(h, "n1k_run_device_batch"); });
+    if (h->plan.ordered_rows() || h->plan.has_row_distinct) return guarded(h, [&]() -> n1k_status { return refuse_ordered_rows(h, "n1k_run_device_batch"); });
     static const bool trace = getenv("N1K_HOST_TRACE") != nullptr;
     auto now = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     const double t0 = trace ? now() : 0;

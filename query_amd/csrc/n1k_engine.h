@@ -32,6 +32,7 @@
 #include "n1k_like.h"
 #include "n1k_order.h"
 #include "n1k_plan.h"
+#include "n1k_rowdistinct.h"
 #include "n1k_strfn.h"
 
 
@@ -177,6 +178,8 @@ struct Options {
     uint32_t block = 0, rows_per_lane = 4;
     uint32_t lds_bytes = 64 * 1024;   // HASH mode: LDS table bytes per workgroup
     uint32_t rep_row = 0;
+    uint64_t rowdistinct_slots = 0;  // DISTINCT over rows: forced capacity of the table, any value >= 1, not rounded (0 = from the survivors; tests)
+    uint32_t rowdistinct_lds_slots = 0;  // ... size of the LDS set ahead of the table; 0 = no pre-filter, the default: measured, it costs more than it saves
 };
 
 // ---- n1k_engine.cpp: plan binding, device and table management
@@ -202,10 +205,12 @@ enum Counter : uint32_t {
     CTR_EXACT_OVERFLOW = 24,     // COUNT(DISTINCT) exact path: an LDS set overflowed
     CTR_SAVED_ROWS_SELECTED = 25,  // CTR_ROWS_SELECTED before the optimistic records path, to undo it
     CTR_REGION_GROUPS = 26,      // ... its region's group count, copied beside the others for the host
-    CTR_PEER_STATUS = 27         // the n1k_status a peer's verdict carried (ERR_PEER_FAILED)
+    CTR_PEER_STATUS = 27,        // the n1k_status a peer's verdict carried (ERR_PEER_FAILED)
+    CTR_ROWDISTINCT_COUNT = 28,  // DISTINCT over rows: the representatives
+    CTR_ROWDISTINCT_REACHED = 29 // ... and the rows that reached the global table (the word behind the count: cleared together)
 };
 static_assert(CTR_ERR_FLAGS + kPeerStatusFromErr == CTR_PEER_STATUS, "the verdict kernel writes the peer status this far behind the flags");
-static_assert(CTR_PEER_STATUS < kCounters, "every counter word lies inside the buffer (CTR_PEER_STATUS is the last)");
+static_assert(CTR_ROWDISTINCT_REACHED < kCounters && CTR_ROWDISTINCT_REACHED == CTR_ROWDISTINCT_COUNT + 1, "every counter word lies inside the buffer (CTR_ROWDISTINCT_REACHED is the last)");
 static_assert(CTR_PAIR_LOG_CURSORS + kMaxDistinct <= CTR_ERR_FLAGS && CTR_WORD_LOG_CURSORS + kMaxDistinct <= CTR_OPTIMISTIC_OVERFLOW, "cursor words overlap their neighbours");
 
 // The group table and the device words every stage reports through.
@@ -311,11 +316,26 @@ struct RowOrder {
     PinBuf<uint32_t> pin_hist;           // host copy of the histograms, then the error flags and the candidate count
     uint32_t passes = 0;                 // digit passes the last ordering launched (diagnostics: tools/exp_order.py)
 };
-// the ascending selection of `total` survivors in h->filter.sel32 -> ordered and cut as the plan says; *out_rows (null when
-// *out_count is 0) is what n1k_selection.rows returns
-n1k_status order_selection(n1k_handle* h, uint64_t total, const uint32_t** out_rows, uint64_t* out_count);
-// the multi-batch calls on a plan whose rows are ordered or cut: N1K_UNSUPPORTED
+// the ascending selection `sel` of `total` survivors (the Filter's, or the representatives DISTINCT left of it) -> ordered and
+// cut as the plan says; *out_rows (null when *out_count is 0) is what n1k_selection.rows returns
+n1k_status order_selection(n1k_handle* h, const uint32_t* sel, uint64_t total, const uint32_t** out_rows, uint64_t* out_count);
+// the multi-batch calls on a plan whose rows are de-duplicated, ordered or cut: N1K_UNSUPPORTED
 n1k_status refuse_ordered_rows(n1k_handle* h, const char* call);
+
+// ---- n1k_rowdistinct.cpp: SELECT DISTINCT over the rows of a Filter-only plan, de-duplicated on the device (n1k_rowdistinct.hip)
+struct RowDistinct {
+    DevBuf<uint32_t> table;       // the open-addressed table of ordinals, cleared every call
+    DevBuf<uint32_t> slot_of;     // per survivor: the slot of its key, then whether it is the representative
+    DevBuf<uint32_t> tile_count;  // the tiles' representatives and their scan
+    DevBuf<uint32_t> rows_out;    // the representatives, ascending
+    uint64_t stats[4] = {0, 0, 0, 0};  // n1k_rowdistinct_stats: survivors, distinct rows, table slots, rows that reached the table
+};
+// the ascending selection `sel` (null: the identity, a plan without Filter) of `total` survivors -> *out_rows: per distinct row
+// key of the plan's result terms the survivor with the smallest ordinal, ascending (null when there is none), *out_count of them
+n1k_status distinct_selection(n1k_handle* h, const uint32_t* sel, uint64_t total, const uint32_t** out_rows, uint64_t* out_count);
+// the stage's options ("rowdistinct_slots", "rowdistinct_lds_slots"; checked by tests/test_gpu_distinct_rows.py): false when
+// `name` is none of them
+bool rowdistinct_option(n1k_handle* h, const std::string& name, int64_t value);
 bool filter_stream_fast(const n1k_handle* h);  // the condition and the bound columns take filter_stream_kernel's FAST variant
 uint32_t filter_stream_grid(const n1k_handle* h, uint64_t ntiles, bool fast);
 bool build_fast_args(n1k_handle* h, uint32_t max_slots, FastArgs& F, bool fuse = false, bool partition_only = false);
@@ -518,6 +538,7 @@ struct n1k_handle {
     Json json;
     Staging stage;
     FilterOnly filter;
+    RowDistinct rowdistinct;
     RowOrder order;
     Results res;
     Timing timing;

@@ -27,11 +27,11 @@ n1k_status unsupported_value(n1k_handle* h) {
     return fail(h, N1K_UNSUPPORTED_DATA, "a value outside the device subset was met (an array or object as a sort value)");
 }
 
-void key_args(n1k_handle* h, OrderKeyArgs& A) {
+void key_args(n1k_handle* h, const uint32_t* sel, OrderKeyArgs& A) {
     const ParsedPlan& pl = h->plan;
     RowOrder& O = h->order;
     A = OrderKeyArgs{};
-    A.rows = h->filter.sel32.p;
+    A.rows = sel;
     A.nterms = (uint32_t)pl.row_order.size();
     for (uint32_t t = 0; t < A.nterms; t++) {
         A.cols[t] = h->prog.cols[pl.row_order[t].col];
@@ -102,11 +102,10 @@ n1k_status sort_passes(n1k_handle* h, uint64_t n, uint32_t nterms, bool pos_term
     return N1K_OK;
 }
 
-n1k_status order_rows(n1k_handle* h, uint64_t total, uint64_t first, uint64_t last, const uint32_t** out_rows) {
+n1k_status order_rows(n1k_handle* h, const uint32_t* sel, uint64_t total, uint64_t first, uint64_t last, const uint32_t** out_rows) {
     const ParsedPlan& pl = h->plan;
     RowOrder& O = h->order;
     const uint32_t nterms = (uint32_t)pl.row_order.size();
-    const uint32_t* sel = h->filter.sel32.p;
     const uint64_t keep = pl.limit >= 0 ? (uint64_t)pl.offset + (uint64_t)pl.limit : total;
     // ≙ order_limit.go: fewer rows wanted than selected, and enough of them for the select to pay (the grouped tail's option)
     const bool select = pl.limit >= 0 && keep > 0 && keep < total && total >= h->opt.topk_min_groups;
@@ -122,7 +121,7 @@ n1k_status order_rows(n1k_handle* h, uint64_t total, uint64_t first, uint64_t la
     const uint32_t* perm = nullptr;
     const uint32_t* cand = nullptr;
     if (!select) {
-        key_args(h, A);
+        key_args(h, sel, A);
         A.n = total;
         A.store = (1u << nterms) - 1u;
         A.hist = O.hist.p;
@@ -139,7 +138,7 @@ n1k_status order_rows(n1k_handle* h, uint64_t total, uint64_t first, uint64_t la
         // the candidate's selection position as the least significant term, since the select leaves them in no order
         HIP_TRY(h, O.cand.ensure(topk_cand_entries(total)));
         HIP_TRY(h, O.state.ensure(topk_state_bytes()));
-        key_args(h, A);
+        key_args(h, sel, A);
         A.n = total;
         A.store = 1u;
         HIP_TRY(h, launch_order_keys(A, order_grid(h), h->stream));
@@ -160,7 +159,7 @@ n1k_status order_rows(n1k_handle* h, uint64_t total, uint64_t first, uint64_t la
             HIP_TRY(h, O.key[t].ensure(ncand));
             if (t < nterms) HIP_TRY(h, O.res[t].ensure(ncand));
         }
-        key_args(h, A);
+        key_args(h, sel, A);
         cand = A.cand = O.cand.p;
         A.n = ncand;
         A.store = (1u << nterms) - 1u;
@@ -190,7 +189,7 @@ n1k_status order_rows(n1k_handle* h, uint64_t total, uint64_t first, uint64_t la
 
 namespace n1k_eng {
 
-n1k_status order_selection(n1k_handle* h, uint64_t total, const uint32_t** out_rows, uint64_t* out_count) {
+n1k_status order_selection(n1k_handle* h, const uint32_t* sel, uint64_t total, const uint32_t** out_rows, uint64_t* out_count) {
     const ParsedPlan& pl = h->plan;
     h->order.passes = 0;
     h->timing.stats.topk_candidates = 0;
@@ -202,10 +201,10 @@ n1k_status order_selection(n1k_handle* h, uint64_t total, const uint32_t** out_r
     if (pl.row_order.empty()) {
         // Offset / Limit alone cut the ascending selection: pointer arithmetic — unless the offset would leave the ordinals off
         // the 16-byte alignment that n1k_gather_selected loads them with; those few are copied
-        if (last > first && first % 4 == 0) *out_rows = h->filter.sel32.p + first;
+        if (last > first && first % 4 == 0) *out_rows = sel + first;
         else if (last > first) {
             HIP_TRY(h, h->order.rows_out.ensure(last - first));
-            HIP_TRY(h, launch_order_finish(h->filter.sel32.p, nullptr, nullptr, first, last, h->order.rows_out.p, h->stream));
+            HIP_TRY(h, launch_order_finish(sel, nullptr, nullptr, first, last, h->order.rows_out.p, h->stream));
             HIP_TRY(h, hipStreamSynchronize(h->stream));
             *out_rows = h->order.rows_out.p;
         }
@@ -213,7 +212,7 @@ n1k_status order_selection(n1k_handle* h, uint64_t total, const uint32_t** out_r
     }
     hipEvent_t e0 = get_event(h), e1 = get_event(h);
     if (e0) (void)hipEventRecord(e0, h->stream);
-    const n1k_status st = order_rows(h, total, first, last, out_rows);
+    const n1k_status st = order_rows(h, sel, total, first, last, out_rows);
     h->timing.stats.order_passes = h->order.passes;
     if (e1) (void)hipEventRecord(e1, h->stream);
     h->timing.events.emplace_back(e0, e1);
@@ -225,6 +224,7 @@ n1k_status order_selection(n1k_handle* h, uint64_t total, const uint32_t** out_r
 }
 
 n1k_status refuse_ordered_rows(n1k_handle* h, const char* call) {
+    if (h->plan.has_row_distinct) return fail(h, N1K_UNSUPPORTED, "%s: a plan with Distinct over its rows takes one batch through n1k_filter_device_batch", call);
     if (!h->plan.ordered_rows()) return N1K_OK;
     return fail(h, N1K_UNSUPPORTED, "%s: a Filter-only plan with Order / Offset / Limit takes one batch through n1k_filter_device_batch", call);
 }

@@ -683,6 +683,15 @@ void collect_paths(const Expr* e, std::vector<std::string>& paths) {
     for (auto& c : e->ch) collect_paths(c.get(), paths);
 }
 
+// The alias algebra.ResultTerm derives for a term without one, back-quoted as a sort term writes it: the last field name of
+// a path that ends in one — (`d`.`cat`) gives `cat` — else none ("")
+std::string derived_alias(const std::string& path) {
+    const size_t n = path.size();
+    if (n < 4 || path[n - 1] != ')' || path[n - 2] != '`') return "";
+    const size_t open = path.rfind('`', n - 3);
+    return open == std::string::npos ? "" : path.substr(open, n - 1 - open);
+}
+
 bool plan_node(const JVal& node, ParsedPlan& out, PlanError& err, int depth) {
     if (node.type != JVal::Obj || depth > 8) {
         err.msg = "plan node is not an object";
@@ -720,6 +729,11 @@ bool plan_node(const JVal& node, ParsedPlan& out, PlanError& err, int depth) {
         return true;
     }
     if (name == "Filter") {  // plan/filter.go:46-53
+        if (!out.row_distinct.empty()) {
+            err.unsupported = true;
+            err.msg = "a Filter after the InitialProject of a DISTINCT over rows does not run on the device";
+            return false;
+        }
         if (out.has_filter) {
             err.unsupported = true;
             err.msg = "only [Filter?, InitialGroup] sequences run on the device";
@@ -735,6 +749,7 @@ bool plan_node(const JVal& node, ParsedPlan& out, PlanError& err, int depth) {
     if (name == "InitialGroup") {  // plan/group.go:54-70
         if (out.has_group) { err.unsupported = true; err.msg = "more than one InitialGroup"; return false; }
         if (out.ordered_rows()) { err.unsupported = true; err.msg = "InitialGroup after Order / Offset / Limit does not run on the device"; return false; }
+        if (!out.row_distinct.empty()) { err.unsupported = true; err.msg = "InitialGroup after a DISTINCT over rows does not run on the device"; return false; }
         const JVal* ks = node.get("group_keys");
         const JVal* as = node.get("aggregates");
         if (ks && ks->type == JVal::Arr)
@@ -781,9 +796,14 @@ bool plan_node(const JVal& node, ParsedPlan& out, PlanError& err, int depth) {
         return true;
     };
     if (name == "Order") {  // plan/order.go:51-79 (the node carries its own offset / limit for the top-k sort)
-        if ((!out.has_group && !out.has_filter) || out.has_order || !out.row_order.empty()) {
+        if ((!out.has_group && !out.has_filter && !out.has_row_distinct) || out.has_order || !out.row_order.empty()) {
             err.unsupported = true;
             err.msg = "Order runs on the device only over the groups or over the rows of a Filter";
+            return false;
+        }
+        if (!out.row_distinct.empty() && !out.has_row_distinct) {
+            err.unsupported = true;
+            err.msg = "Order between the InitialProject of a DISTINCT over rows and its Distinct does not run on the device";
             return false;
         }
         const JVal* ts = node.get("sort_terms");
@@ -807,6 +827,14 @@ bool plan_node(const JVal& node, ParsedPlan& out, PlanError& err, int depth) {
                 }
                 RowOrderTerm rt;
                 rt.text = ex->text;
+                // after a DISTINCT projection the item carries its terms under their aliases (execution/project_initial.go:
+                // 118-121): `alias` names a term — by its explicit alias, else by the last field name of its path, the alias
+                // algebra.ResultTerm derives — and resolves to that term's path
+                for (auto& dt : out.row_distinct)
+                    if (ex->text == (dt.as.empty() ? derived_alias(dt.text) : "`" + dt.as + "`")) {
+                        rt.text = dt.text;
+                        break;
+                    }
                 const JVal* d = t.get("desc");
                 rt.desc = d && d->type == JVal::Bool && d->b;
                 out.row_order.push_back(rt);
@@ -841,6 +869,53 @@ bool plan_node(const JVal& node, ParsedPlan& out, PlanError& err, int depth) {
         out.has_order = true;
         if (node.get("offset") && !const_count(node.get("offset"), "offset", out.offset)) return false;
         if (node.get("limit") && !const_count(node.get("limit"), "limit", out.limit)) return false;
+        return true;
+    }
+    auto flag_set = [&](const char* flag) {
+        const JVal* f = node.get(flag);
+        return f && f->type == JVal::Bool && f->b;
+    };
+    if (name == "InitialProject" && !out.has_group && flag_set("distinct")) {
+        // SELECT DISTINCT over the rows (planner/build_select_sub.go:217-240): the terms are the row key of the Distinct that follows
+        if (!out.row_distinct.empty() || out.ordered_rows()) {
+            err.unsupported = true;
+            err.msg = "InitialProject with distinct runs on the device once, before Order / Offset / Limit";
+            return false;
+        }
+        if (flag_set("raw")) { err.unsupported = true; err.msg = "InitialProject with raw does not run on the device"; return false; }
+        const JVal* ts = node.get("result_terms");
+        if (!ts || ts->type != JVal::Arr || ts->arr.empty()) { err.msg = "InitialProject without result_terms"; return false; }
+        if (ts->arr.size() > kDistinctMaxTerms) {
+            err.unsupported = true;
+            err.msg = "DISTINCT over rows with " + std::to_string(ts->arr.size()) + " result terms: the device takes 1 to " + std::to_string(kDistinctMaxTerms);
+            return false;
+        }
+        for (auto& t : ts->arr) {
+            if (t.type != JVal::Obj) { err.msg = "result term is not an object"; return false; }
+            const JVal* star = t.get("star");
+            if (star && star->type == JVal::Bool && star->b) { err.unsupported = true; err.msg = "a star projection does not run on the device"; return false; }
+            const JVal* e = t.get("expr");
+            if (!e || e->type != JVal::Str) { err.msg = "result term without expr"; return false; }
+            PlanError perr;
+            auto ex = parse_expression(e->str, perr);
+            if (!ex || ex->kind != EK::Path) {
+                err.unsupported = true;
+                err.msg = "result term of a DISTINCT over rows is not a leaf path of the row (arithmetic, functions, aggregates and constants keep the reference's Distinct): " + e->str;
+                return false;
+            }
+            RowDistinctTerm dt;
+            dt.text = ex->text;
+            const JVal* as = t.get("as");
+            if (as && as->type == JVal::Str) dt.as = as->str;
+            out.row_distinct.push_back(std::move(dt));
+        }
+        return true;
+    }
+    if (name == "Distinct") {  // plan/distinct.go:32-40: no data; the key is the projection the InitialProject attached
+        if (out.has_group) { err.unsupported = true; err.msg = "Distinct over the groups does not run on the device"; return false; }
+        if (out.row_distinct.empty()) { err.unsupported = true; err.msg = "Distinct without the InitialProject{distinct} before it does not run on the device"; return false; }
+        if (out.ordered_rows()) { err.unsupported = true; err.msg = "Distinct after Order / Offset / Limit does not run on the device"; return false; }
+        out.has_row_distinct = true;  // (the Distinct inside the Parallel and the serial one behind it are one stage)
         return true;
     }
     if (name == "InitialProject") {  // plan/project.go:73-110: result_terms [{expr, as?, star?}], raw?, distinct?
@@ -878,11 +953,13 @@ bool plan_node(const JVal& node, ParsedPlan& out, PlanError& err, int depth) {
         return true;
     }
     if (name == "FinalProject") {  // plan/project.go:171-181: no data; the projection attachment becomes the row
+        if (!out.row_distinct.empty()) return true;  // (DISTINCT over rows: the caller projects the representatives)
         if (!out.has_project) { err.unsupported = true; err.msg = "FinalProject without an InitialProject over the groups"; return false; }
         return true;
     }
     if (name == "Limit" || name == "Offset") {  // plan/limit.go:46-53, plan/offset.go
-        if (!out.has_group && !out.has_filter) { err.unsupported = true; err.msg = name + " runs on the device only over the groups or over the rows of a Filter"; return false; }
+        if (!out.has_group && !out.has_filter && !out.has_row_distinct) { err.unsupported = true; err.msg = name + " runs on the device only over the groups or over the rows of a Filter"; return false; }
+        if (!out.row_distinct.empty() && !out.has_row_distinct) { err.unsupported = true; err.msg = name + " between the InitialProject of a DISTINCT over rows and its Distinct does not run on the device"; return false; }
         return const_count(node.get("expr"), name == "Limit" ? "limit" : "offset", name == "Limit" ? out.limit : out.offset);
     }
     err.unsupported = true;
@@ -1001,12 +1078,22 @@ bool parse_plan_json(const char* json, size_t len, ParsedPlan& out, PlanError& e
         return false;
     }
     if (!plan_node(root, out, err, 0)) return false;
-    if (!out.has_filter && !out.has_group) {
+    if (!out.row_distinct.empty() && !out.has_row_distinct) {
+        err.unsupported = true;
+        err.msg = "InitialProject with distinct that no Distinct follows does not run on the device";
+        return false;
+    }
+    if (!out.has_filter && !out.has_group && !out.has_row_distinct) {
         err.unsupported = true;
         err.msg = "plan holds neither Filter nor InitialGroup";
         return false;
     }
     collect_paths(out.condition.get(), out.paths);
+    for (auto& t : out.row_distinct) {  // the DISTINCT terms' paths behind the condition's and before the sort terms', none twice
+        auto at = std::find(out.paths.begin(), out.paths.end(), t.text);
+        t.col = (int)(at - out.paths.begin());
+        if (at == out.paths.end()) out.paths.push_back(t.text);
+    }
     for (auto& k : out.keys) collect_paths(k.get(), out.paths);
     for (auto& a : out.aggs) collect_paths(a.operand.get(), out.paths);
     for (auto& t : out.row_order) {  // sort-term paths after the condition's, in first-use order, none twice

@@ -75,6 +75,15 @@ struct RowOrderTerm {
     int col = -1;  // its column: index into ParsedPlan::paths
 };
 
+// one result term of SELECT DISTINCT over the rows of a plan without a group (InitialProject{"distinct":true} + Distinct,
+// plan/project.go:69-108, plan/distinct.go:32-40): a leaf path of the row, like a sort term
+constexpr uint32_t kDistinctMaxTerms = 4;
+struct RowDistinctTerm {
+    std::string text;
+    std::string as;  // explicit alias ("" = none)
+    int col = -1;    // its column: index into ParsedPlan::paths
+};
+
 // one result term of the InitialProject after the group operators (plan/project.go:73-110): its expression reads group
 // keys and aggregates (algebra/aggregate.go:97-118 looks an aggregate up by its text in the "aggregates" attachment)
 struct ProjectTerm {
@@ -100,6 +109,10 @@ struct ParsedPlan {
     // the ordered (without Order: the ascending) selection
     std::vector<RowOrderTerm> row_order;
     bool ordered_rows() const { return !has_group && (!row_order.empty() || limit >= 0 || offset > 0); }
+    // SELECT DISTINCT over the rows (no group): the InitialProject's 1 to kDistinctMaxTerms leaf paths, and whether the Distinct
+    // operator followed it (the parallel and the serial Distinct of the planner fold into one); Order / Offset / Limit come after
+    std::vector<RowDistinctTerm> row_distinct;
+    bool has_row_distinct = false;
     // HAVING: a Filter after the group operators (planner/build_select_sub.go:295), over group keys and aggregates
     bool has_having = false;
     std::string having_text;
@@ -109,7 +122,8 @@ struct ParsedPlan {
 };
 
 // Parse plan JSON (Sequence / Parallel / Filter / InitialGroup nodes, optionally followed by IntermediateGroup /
-// FinalGroup — which the device operator subsumes — and Order / Offset / Limit over the groups).  Returns false and fills err on failure.
+// FinalGroup — which the device operator subsumes — and Order / Offset / Limit over the groups; or, without a group,
+// Filter? / InitialProject{distinct} / Distinct / Order / Offset / Limit over the rows).  Returns false and fills err on failure.
 bool parse_plan_json(const char* json, size_t len, ParsedPlan& out, PlanError& err);
 
 // Parse one stringified expression / aggregate.

@@ -61,7 +61,9 @@ n1k_status n1k_filter_device_batch(n1k_handle* h, const n1k_batch* batch, n1k_se
     const uint64_t n = batch->nrows;
     unsigned long long total = 0;
     uint32_t err_flags = 0;
-    if (n) {
+    if (n && !h->plan.has_filter) {
+        total = n;  // a DISTINCT plan without Filter: every row is a survivor, the selection is the identity and is not written
+    } else if (n) {
         const uint64_t ntiles = (n + kFilterStreamTile - 1) / kFilterStreamTile;
         HIP_TRY(h, h->filter.tile_off.ensure(ntiles + 1));
         HIP_TRY(h, h->filter.sel32.ensure(n));
@@ -93,11 +95,18 @@ n1k_status n1k_filter_device_batch(n1k_handle* h, const n1k_batch* batch, n1k_se
     }
     if (h->stop_flag.load()) return fail(h, N1K_STOPPED, "operator was stopped");
     if (total > n) return fail(h, N1K_DEVICE_ERROR, "the Filter kernel counted %llu survivors of %llu rows", total, (unsigned long long)n);
-    // a plan with Order / Offset / Limit: the survivors in ORDER BY order, cut to [offset, offset + limit) (n1k_order.cpp)
     const uint32_t* rows = total ? h->filter.sel32.p : nullptr;
+    // a plan with Distinct: per distinct row of the result terms the survivor with the smallest ordinal (n1k_rowdistinct.cpp)
+    if (h->plan.has_row_distinct) {
+        uint64_t reps = 0;
+        ST_TRY(distinct_selection(h, h->plan.has_filter ? rows : nullptr, total, &rows, &reps));
+        if (h->stop_flag.load()) return fail(h, N1K_STOPPED, "operator was stopped");
+        total = reps;
+    }
+    // a plan with Order / Offset / Limit: the survivors in ORDER BY order, cut to [offset, offset + limit) (n1k_order.cpp)
     if (h->plan.ordered_rows()) {
         uint64_t cut = 0;
-        ST_TRY(order_selection(h, total, &rows, &cut));
+        ST_TRY(order_selection(h, rows, total, &rows, &cut));
         total = cut;
     }
     h->timing.stats.rows_selected = total;

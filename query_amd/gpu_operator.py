@@ -190,7 +190,8 @@ class GpuFilterGroup:
         """n1k_filter_device_batch: one whole execution of a Filter-only plan over a device-resident batch (as
         make_device_batch builds it).  Returns (nselected, device address of the ascending uint32 batch-local ordinals; None
         when nothing passed): the ordinals stay in the handle's device memory until the next call / reopen / done.  A plan
-        with Order / Offset / Limit: the ordinals in ORDER BY order, cut, and nselected the cut count."""
+        with Order / Offset / Limit: the ordinals in ORDER BY order, cut, and nselected the cut count.  A plan with Distinct:
+        per distinct row of its result terms the survivor with the smallest ordinal, before that tail."""
         sel = _ffi.Selection()
         self._nselected = 0
         self._check(self._lib.n1k_filter_device_batch(self._h, C.byref(batch[0]), C.byref(sel)))
@@ -399,6 +400,13 @@ class GpuFilterGroup:
         out = (C.c_uint64 * 4)()
         self._check(self._lib.n1k_strfn_stats(self._h, C.byref(out)))
         return {"device_strings": int(out[0]), "host_strings": int(out[1]), "predicates": int(out[2]), "device_threshold": int(out[3])}
+
+    def rowdistinct_stats(self) -> dict:
+        """The last DISTINCT over rows of this operator: survivors of the Filter, distinct rows before the cut, slots of the
+        table of ordinals, and the rows that reached it (all, unless rowdistinct_lds_slots is set)."""
+        out = (C.c_uint64 * 4)()
+        self._check(self._lib.n1k_rowdistinct_stats(self._h, C.byref(out)))
+        return {"survivors": int(out[0]), "distinct_rows": int(out[1]), "table_slots": int(out[2]), "reached_table": int(out[3])}
 
     def reopen(self):
         self._check(self._lib.n1k_reset(self._h))

@@ -129,8 +129,9 @@ class Offset:
 
 @dataclass
 class InitialProject:
-    """plan/project.go:73-110: result_terms [{expr, as?}] (star / raw / distinct projections are not built here)."""
+    """plan/project.go:73-110: result_terms [{expr, as?}], distinct (star / raw projections are not built here)."""
     result_terms: Sequence[tuple]  # (expression text, alias or None)
+    distinct: bool = False
 
     def marshal(self) -> dict:
         terms = []
@@ -139,7 +140,18 @@ class InitialProject:
             if alias:
                 t["as"] = alias
             terms.append(t)
-        return {"#operator": "InitialProject", "result_terms": terms}
+        d = {"#operator": "InitialProject", "result_terms": terms}
+        if self.distinct:  # (plan/project.go:84-86: marshalled only when set)
+            d["distinct"] = True
+        return d
+
+
+@dataclass
+class Distinct:
+    """plan/distinct.go:32-40: no data; the set is keyed by the projection the InitialProject before it attached."""
+
+    def marshal(self) -> dict:
+        return {"#operator": "Distinct"}
 
 
 @dataclass
@@ -156,16 +168,31 @@ def filter_group_plan(condition: Optional[str], group_keys: Optional[Sequence[st
                       aggregates: Optional[Sequence[str]], *, filter_only: bool = False,
                       order: Optional[Sequence[tuple]] = None, limit: Optional[int] = None,
                       offset: Optional[int] = None, having: Optional[str] = None,
-                      project: Optional[Sequence[tuple]] = None) -> str:
+                      project: Optional[Sequence[tuple]] = None, distinct: Optional[Sequence[tuple]] = None) -> str:
     """Plan JSON of Parallel{Sequence[Filter?, InitialGroup?]} as the planner emits it
     (planner/build_select_sub.go:209-211, 276-296).  With `order` / `limit` / `offset` the whole grouped tail
     follows: IntermediateGroup, FinalGroup, Order (which carries offset and limit, plan/order.go:51-79), Offset,
     Limit (planner/build_select.go) — the sort terms must be group keys or aggregates of the plan.  With `filter_only`
     the same three follow the Filter directly, over the rows it selects: `order` = [(leaf path of the row, descending)],
-    1 to 4 terms; n1k_filter_device_batch then returns the selection ordered and cut."""
+    1 to 4 terms; n1k_filter_device_batch then returns the selection ordered and cut.  With `filter_only` and `distinct` =
+    [(leaf path of the row, alias or None)], 1 to 4 terms, it is SELECT DISTINCT over the rows (planner/build_select_sub.go:
+    217-240): InitialProject{distinct}, Distinct and FinalProject follow the Filter inside the Parallel, the serial Distinct, the
+    tail and the last FinalProject come behind it; a sort term may then name a term by `alias`."""
     children: List[object] = []
     if condition:
         children.append(Filter(condition))
+    if distinct is not None:
+        if not filter_only or having is not None or project is not None:
+            raise ValueError("distinct goes with filter_only, without having / project")
+        children += [InitialProject(list(distinct), distinct=True), Distinct(), FinalProject()]
+        tail = [Parallel(Sequence(children)), Distinct()]
+        if order:
+            tail.append(Order(list(order), offset, limit))
+        if offset is not None:
+            tail.append(Offset(offset))
+        if limit is not None:
+            tail.append(Limit(limit))
+        return marshal_json(Sequence(tail + [FinalProject()]))
     if not filter_only:
         children.append(InitialGroup(list(group_keys or []), list(aggregates or [])))
     par = Parallel(Sequence(children))
