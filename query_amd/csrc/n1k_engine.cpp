@@ -591,6 +591,8 @@ n1k_status reset_handle(n1k_handle* h, bool clear_stop) {
     h->failure_global = false;
     h->row_base = 0;
     h->groups.merged_bound = 0;
+    h->groups.pending.grid = 0;
+    h->groups.pending.clean_at_push = false;
     h->filter.selected.clear();
     h->filter.has_sel32 = false;
     h->res.keys.clear();
@@ -944,13 +946,14 @@ n1k_status n1k_run_device_batch(n1k_handle* h, const n1k_batch* batch, n1k_resul
     const double t0 = trace ? now() : 0;
     n1k_status st = n1k_reset(h);
     const double t1 = trace ? now() : 0;
+    // one call: the result leaves the device, and the state behind it is the next execution's reset.  Marked before the push,
+    // whose scan may then leave its slabs for n1k_finish to turn into rows (slabs_to_rows)
+    h->clear_on_finish = true;
     if (st == N1K_OK) st = n1k_push_device_batch(h, batch);
     const double t2 = trace ? now() : 0;
-    if (st == N1K_OK) {
-        h->clear_on_finish = true;  // the result leaves the device; the state behind it is the next execution's reset
-        st = n1k_finish(h, out);
-        h->clear_on_finish = false;
-    }
+    if (st == N1K_OK) st = n1k_finish(h, out);
+    h->clear_on_finish = false;
+    h->groups.pending.grid = 0;  // (a finish that failed before its last kernel: nothing folds these slabs later)
     if (trace) {
         h->timing.host_us[0] += t1 - t0;
         h->timing.host_us[1] += t2 - t1;

@@ -192,6 +192,7 @@ enum Counter : uint32_t {
     CTR_FILTER_TOTAL = 3,        // survivors of a Filter-only batch
     CTR_REHASH_SCRATCH = 4,
     CTR_DISTINCT_REGION_WORDS = 5,  // K6: set-table words the layout kernel asks for
+    CTR_TAIL_TICKET = 6,         // fold_rows_kernel: workgroups done (the last one publishes and zeroes the counters, this one too)
     CTR_PAIR_LOG_CURSORS = 8,    // + log_index (kMaxDistinct words): the (key, value, class) pair logs
     CTR_ERR_FLAGS = 12,          // ERR_* (n1k_types.h), low 32 bits: GroupTable::errp
     CTR_WIDE_VALUES = 13,        // distinct wide key values met so far (Program::wide_count)
@@ -211,6 +212,8 @@ enum Counter : uint32_t {
 };
 static_assert(CTR_ERR_FLAGS + kPeerStatusFromErr == CTR_PEER_STATUS, "the verdict kernel writes the peer status this far behind the flags");
 static_assert(CTR_ROWDISTINCT_REACHED < kCounters && CTR_ROWDISTINCT_REACHED == CTR_ROWDISTINCT_COUNT + 1, "every counter word lies inside the buffer (CTR_ROWDISTINCT_REACHED is the last)");
+static_assert(CTR_ROWS_SELECTED == 0 && CTR_GROUPS == 1 && CTR_OUT_COUNT == 2 && CTR_TAIL_TICKET > CTR_DISTINCT_REGION_WORDS && CTR_TAIL_TICKET < CTR_PAIR_LOG_CURSORS,
+              "the query's last kernels (finalize_small_kernel, fold_rows_kernel) write words [0], [1] and [2] by number");
 static_assert(CTR_PAIR_LOG_CURSORS + kMaxDistinct <= CTR_ERR_FLAGS && CTR_WORD_LOG_CURSORS + kMaxDistinct <= CTR_OPTIMISTIC_OVERFLOW, "cursor words overlap their neighbours");
 
 // The group table and the device words every stage reports through.
@@ -223,6 +226,14 @@ struct GroupTable {
     DevBuf<unsigned long long> counters;  // kCounters words, named by Counter (above)
     DevBuf<uint64_t> wide_int, wide_flt;  // the wide key value tables, Options::wide_values entries (n1k_engine.cpp alone)
     uint64_t merged_bound = 0;  // groups that may have arrived through merges (bounds the table like rows do)
+    // One-call executions: the slabs of the batch's only scan launch, left unmerged by launch_chunk for n1k_finish to fold
+    // straight into result rows (fold_rows_kernel; slabs_to_rows is the one predicate of both).  The program is the handle's
+    // (no DISTINCT on this path).  reset_handle forgets them.
+    struct PendingSlabs {
+        bool clean_at_push = false;  // the device was as n1k_reset leaves it when the push began, and nothing before the scan touched it
+        uint32_t grid = 0;           // > 0: slabs of this many workgroups are pending
+        FastArgs F{};                // ... the scan's arguments: slabs, survivor counts, slot -> key, error flags
+    } pending;
 };
 uint32_t intern(n1k_handle* h, const std::string& s);
 uint32_t lookup_code(const n1k_handle* h, const char* s);
@@ -470,6 +481,10 @@ n1k_status having_groups(n1k_handle* h, uint64_t& ng);
 n1k_status project_groups(n1k_handle* h, uint64_t ng);
 n1k_status order_groups(n1k_handle* h, uint64_t& ng);
 n1k_status array_agg_groups(n1k_handle* h, uint64_t ng, const unsigned long long* counters);
+// A scan launch of g workgroups with slabs of F.lds_slots slots may leave them unmerged, and n1k_finish turns them into result
+// rows without the table: the one predicate of launch_chunk and read_counters.  only_chunk: the launch is the
+// batch's only one; whole: it covers every row of it (no odd last row, whose scalar launch merges into the table).
+bool slabs_to_rows(const n1k_handle* h, const FastArgs& F, uint32_t g, bool only_chunk, bool whole);
 // the ng groups of h->res (and the projection of h->tail) into the caller's n1k_result; partials only where FinalGroup made them
 void publish_result(n1k_handle* h, uint64_t ng, bool partials, n1k_result* out);
 

@@ -48,6 +48,19 @@ static uint64_t speculative_groups(const n1k_handle* h) {
     return std::min<uint64_t>(h->groups.table.capacity, 4096);
 }
 
+namespace n1k_eng {
+bool slabs_to_rows(const n1k_handle* h, const FastArgs& F, uint32_t g, bool only_chunk, bool whole) {
+    // a one-call execution on a device that n1k_reset found clean: the table is empty and the counters are zero, before
+    // the scan and — the table never touched — after the fold
+    if (!h->clear_on_finish || !h->groups.pending.clean_at_push || !only_chunk || !whole || h->push_nrows_dev || h->push_nseg) return false;
+    if (!F.slabs || F.hashed || g <= 1 || h->opt.merge_chunks != 0 || h->prog.wide_int || h->has_array_agg) return false;
+    const uint64_t spec = speculative_groups(h), cap = h->groups.table.capacity;
+    // every slot that can be a group has its row in the pinned buffer (and ERR_TABLE_FULL could not arise with the table
+    // either): there is no table to run a sized second pass from
+    return spec && cap <= kFinalizeSmallMax && F.lds_slots <= std::min<uint64_t>(std::min<uint64_t>(cap, spec), h->opt.max_groups);
+}
+}  // namespace n1k_eng
+
 // FinalGroup's position counter starts from zero (reopen zeroes every counter in its one launch)
 static n1k_status zero_out_count(n1k_handle* h) {
     if (h->res.out_count_dirty) HIP_TRY(h, hipMemsetAsync(h->groups.counters.p + CTR_OUT_COUNT, 0, sizeof(unsigned long long), h->stream));
@@ -63,6 +76,13 @@ static n1k_status read_counters(n1k_handle* h, Finish& F) {
     if (!h->device_ready) return h->timing.stats.rows_in == 0 ? ensure_device(h) : N1K_OK;
     HIP_TRY(h, hipSetDevice(h->device));
     ST_TRY(ensure_pinned_counters(h));
+    GroupTable::PendingSlabs& ps = h->groups.pending;
+    const bool fold = ps.grid && slabs_to_rows(h, ps.F, ps.grid, true, true);
+    if (ps.grid && !fold) {
+        // (not reached: launch_chunk asked the same predicate.)  IntermediateGroup into the table after all, as the push would have
+        HIP_TRY(h, launch_merge_slabs(h->prog, ps.F, h->groups.table, ps.grid, h->groups.counters.p + CTR_GROUPS, h->stream, h->opt.merge_chunks));
+        ps.grid = 0;
+    }
     F.spec_groups = speculative_groups(h);
     if (F.spec_groups) {
         F.lay = OutLayout(F.spec_groups, h->plan.keys.size(), h->plan.aggs.size());
@@ -72,7 +92,14 @@ static n1k_status read_counters(n1k_handle* h, Finish& F) {
         // cost ~ 21 us of a 0.33 ms query: 2 x 4.7 us + a 12 us gap).
         char* d = F.rows = h->res.pin_out.p;
         unsigned long long* host_counters = (unsigned long long*)(d + F.lay.total);
-        if (h->groups.table.capacity <= 8192) {
+        if (fold) {
+            // slabs -> rows in the query's one kernel behind the scan; the table stays empty, the counters come back zero
+            HIP_TRY(h, launch_fold_rows(h->prog, ps.F, h->groups.table, ps.grid, F.lay.k(d), F.lay.a(d), F.lay.p(d), F.lay.r(d), h->groups.counters.p, CTR_TAIL_TICKET,
+                                        host_counters, F.spec_groups, h->stream));
+            ps.grid = 0;
+            h->res.out_count_dirty = false;
+            h->device_clean = true;
+        } else if (h->groups.table.capacity <= kFinalizeSmallMax) {
             // small tables: FinalGroup, the counters behind it and — for a one-call execution, when nothing else on the
             // device needs a reset (no wide-value tables) — the state the next execution starts from, in ONE last kernel
             const bool clear = h->clear_on_finish && !h->prog.wide_int;
@@ -93,6 +120,10 @@ static n1k_status read_counters(n1k_handle* h, Finish& F) {
         F.wait_end = std::chrono::steady_clock::now();
         h->timing.host_us[3] += std::chrono::duration<double, std::micro>(F.wait_end - w0).count();
         memcpy(F.counters, host_counters, sizeof F.counters);
+        if (fold && F.counters[CTR_TAIL_TICKET]) {  // the scan's bypass put rows into the table: n1k_reset has to clear it
+            h->device_clean = false;
+            F.counters[CTR_TAIL_TICKET] = 0;
+        }
     } else {
         HIP_TRY(h, hipMemcpyAsync(h->res.pin_counters.p, h->groups.counters.p, sizeof F.counters, hipMemcpyDeviceToHost, h->stream));
         mark_query_end(h);

@@ -7,6 +7,7 @@
 namespace n1k {
 
 constexpr int kFilterStreamTile = 8192;  // rows per tile of the one-pass Filter-only kernel (4 passes of 256 threads x 8 rows)
+constexpr uint32_t kFinalizeSmallMax = 8192;  // table slots up to which FinalGroup is the query's one last kernel (finalize_small_kernel, fold_rows_kernel)
 
 struct OutValue {  // same 16-byte layout as n1k_value
     uint64_t tag;  // low byte = tag (little endian), rest zero
@@ -127,6 +128,14 @@ hipError_t launch_finalize(const Program& P, const GlobalTable& G, OutValue* out
 hipError_t launch_finalize_small(const Program& P, const GlobalTable& G, OutValue* out_keys, OutValue* out_aggs, OutPartial* out_parts,
                                  uint64_t* out_rep, unsigned long long* counters, unsigned long long* host_counters, uint64_t max_out,
                                  uint32_t* err_flags, bool clear, hipStream_t st);
+// The slabs of a one-call execution's only scan launch (F.slabs, F.block_selected: nslabs workgroups) folded straight into
+// result rows, the counters published behind them and zeroed (fold_rows_kernel): instead of launch_merge_slabs +
+// launch_finalize_small.  counters[ticket_word] is the kernel's own; it must be zero before and is zero after.  The table G is
+// only read: rows the scan's bypass of the narrow LDS sums left there join their groups, and host_counters[ticket_word] is
+// then their number (not zero: the table is not empty behind this query).
+hipError_t launch_fold_rows(const Program& P, const FastArgs& F, const GlobalTable& G, uint32_t nslabs, OutValue* out_keys, OutValue* out_aggs,
+                            OutPartial* out_parts, uint64_t* out_rep, unsigned long long* counters, uint32_t ticket_word,
+                            unsigned long long* host_counters, uint64_t max_out, hipStream_t st);
 // Filter alone in one pass: predicate + ordered compaction, tile offsets by a chained scan (tile_state: ntiles + 1 words, the
 // last one the tile counter; zeroed here)
 hipError_t launch_filter_stream(const Program& P, uint64_t nrows, uint64_t row_base, uint64_t* out_rows, unsigned long long* tile_state,

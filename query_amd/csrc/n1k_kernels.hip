@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 #include "n1k_device.h"
 #include "n1k_tables.h"
+#include "n1k_fold.h"
 #include "n1k_scatter.h"
 #include "n1k_kernels.h"
 #include <algorithm>
@@ -1458,31 +1459,55 @@ __global__ __launch_bounds__(BLOCK) void partition_kernel(const Program P, const
 // CumulateIntermediate.  Every workgroup of a DIRECT-mode scan left its LDS table (same slot for the same key in
 // every workgroup) in a slab; one thread per slot folds the slabs in workgroup order — no atomics between
 // workgroups, and float sums are reproducible for a given grid.
-enum { RED_ADD_U64, RED_ADD_F64, RED_OR, RED_MIN_I64, RED_MAX_I64, RED_MIN_U64, RED_MAX_U64 };
-
-// reduce one 64-bit value over threadIdx.y (16 rows) for every threadIdx.x column; all threads of the block call it
-template <int OP>
-N1K_DEV uint64_t reduce_over_y(uint64_t (*red)[64], uint64_t v) {
+// reduce one 64-bit value over threadIdx.y (16 rows) for every threadIdx.x column with fold_word(op); all threads of the block
+// call it
+N1K_DEV uint64_t reduce_over_y(uint64_t (*red)[64], uint64_t v, uint32_t op) {
     const uint32_t tx = threadIdx.x, ty = threadIdx.y;
     red[ty][tx] = v;
     __syncthreads();
     for (uint32_t off = 8; off > 0; off >>= 1) {
-        if (ty < off) {
-            uint64_t a = red[ty][tx], b = red[ty + off][tx], r;
-            if (OP == RED_ADD_U64) r = a + b;
-            else if (OP == RED_ADD_F64) r = f64_bits(as_f64(a) + as_f64(b));
-            else if (OP == RED_OR) r = a | b;
-            else if (OP == RED_MIN_I64) r = (int64_t)a < (int64_t)b ? a : b;
-            else if (OP == RED_MAX_I64) r = (int64_t)a > (int64_t)b ? a : b;
-            else if (OP == RED_MIN_U64) r = a < b ? a : b;
-            else r = a > b ? a : b;
-            red[ty][tx] = r;
-        }
+        if (ty < off) red[ty][tx] = fold_word(op, red[ty][tx], red[ty + off][tx]);
         __syncthreads();
     }
     uint64_t out = red[0][tx];
     __syncthreads();
     return out;
+}
+
+// a partial fold's word into the word of a global row that other block rows fold into as well
+N1K_DEV void atomic_fold_word(uint32_t op, unsigned long long* w, uint64_t v) {
+    switch (op) {
+        case FOLD_ADD_U64: atomicAdd(w, (unsigned long long)v); break;
+        case FOLD_ADD_F64: atomicAdd((double*)w, as_f64(v)); break;
+        case FOLD_OR: atomicOr(w, (unsigned long long)v); break;
+        case FOLD_MIN_I64: atomicMin((long long*)w, (long long)v); break;
+        case FOLD_MAX_I64: atomicMax((long long*)w, (long long)v); break;
+        case FOLD_MIN_U64: atomicMin(w, (unsigned long long)v); break;
+        default: atomicMax(w, (unsigned long long)v); break;
+    }
+}
+
+// one aggregate of merge_slabs_kernel's thread: its slabs folded (n1k_fold.h), the block's 16 chunks joined word by word, the
+// live words applied to the global row w (null: no row)
+template <uint32_t KIND, int UNROLL>
+N1K_DEV void merge_slabs_agg(uint64_t (*red)[64], const uint64_t* l, uint32_t S, size_t slab_words, uint32_t nblocks, unsigned long long* w) {
+    uint64_t acc[kFoldMaxWords];
+    fold_init(KIND, acc);
+#pragma unroll UNROLL
+    for (uint32_t b = 0; b < nblocks; b++) {
+        const uint64_t* lb = l + b * slab_words;  // word i of workgroup b at lb[i * S]
+        uint64_t x[kFoldMaxWords];
+#pragma unroll
+        for (uint32_t i = 0; i < fold_slab_words(KIND); i++) x[i] = lb[i * (size_t)S];
+        fold_slab(KIND, acc, x);
+    }
+#pragma unroll
+    for (uint32_t i = 0; i < fold_acc_words(KIND); i++) acc[i] = reduce_over_y(red, acc[i], fold_word_op(KIND, i));
+    if (!w) return;
+    const uint64_t fl = acc[fold_flags_word(KIND)];
+#pragma unroll
+    for (uint32_t i = 0; i < fold_acc_words(KIND); i++)
+        if (fold_word_live(KIND, i, fl)) atomic_fold_word(fold_word_op(KIND, i), &w[i], acc[i]);
 }
 
 __global__ __launch_bounds__(1024) void merge_slabs_kernel(const Program P, const FastArgs F, const GlobalTable G,
@@ -1508,7 +1533,7 @@ __global__ __launch_bounds__(1024) void merge_slabs_kernel(const Program P, cons
     uint64_t touched = 0;
 #pragma unroll 8
     for (uint32_t b = 0; b < nblocks; b++) touched |= base[b * slab_words] ^ kEmptyKey;
-    touched = reduce_over_y<RED_OR>(red, touched);
+    touched = reduce_over_y(red, touched, FOLD_OR);
     const bool leader = threadIdx.y == 0 && in_range && touched != 0;
     long long g = -1;
     if (leader) g = global_find_or_insert(G, fast_slot_key(F, s), F.err_flags, ngroups);
@@ -1520,74 +1545,11 @@ __global__ __launch_bounds__(1024) void merge_slabs_kernel(const Program P, cons
         unsigned long long* w = grow ? (unsigned long long*)(grow + ag.glob_off) : nullptr;
         switch (ag.kind) {
             case AGG_COUNT:
-            case AGG_COUNTN: {
-                unsigned long long c = 0;
-#pragma unroll 8
-                for (uint32_t b = 0; b < nblocks; b++) c += l[b * slab_words];
-                c = reduce_over_y<RED_ADD_U64>(red, c);
-                if (w && c) atomicAdd(&w[0], c);
-                break;
-            }
-            case AGG_SUM:
-            case AGG_AVG: {
-                unsigned long long lo = 0, hi = 0, fl = 0, n = 0;
-                double fs = 0.0;
-                const bool avg = ag.kind == AGG_AVG;
-#pragma unroll 4
-                for (uint32_t b = 0; b < nblocks; b++) {
-                    const uint64_t* lb = l + b * slab_words;
-                    int64_t x = (int64_t)lb[0];        // 0 when no int was added
-                    double f = as_f64(lb[(size_t)S]);  // +0.0 when no float was added
-                    fl |= lb[2 * (size_t)S];
-                    lo += (unsigned long long)(uint32_t)x;
-                    hi += (unsigned long long)(x >> 32);
-                    fs += f;
-                    if (avg) n += lb[3 * (size_t)S];
-                }
-                lo = reduce_over_y<RED_ADD_U64>(red, lo);
-                hi = reduce_over_y<RED_ADD_U64>(red, hi);
-                fs = as_f64(reduce_over_y<RED_ADD_F64>(red, f64_bits(fs)));
-                fl = reduce_over_y<RED_OR>(red, fl);
-                if (avg) n = reduce_over_y<RED_ADD_U64>(red, n);
-                if (!w || !fl) break;
-                if (fl & (SF_NONNEG_INT | SF_NEG_INT)) { atomicAdd(&w[0], lo); atomicAdd(&w[1], hi); }
-                if (fl & SF_FLOAT) atomicAdd((double*)&w[2], fs);
-                atomicOr(&w[3], fl);
-                if (avg) atomicAdd(&w[4], n);
-                break;
-            }
-            default: {
-                const bool mn = ag.kind == AGG_MIN;
-                unsigned long long fl = 0;
-                long long iv = mn ? INT64_MAX : INT64_MIN;
-                unsigned long long fv = mn ? ~0ull : 0ull, sv = mn ? ~0ull : 0ull;
-#pragma unroll 4
-                for (uint32_t b = 0; b < nblocks; b++) {
-                    const uint64_t* lb = l + b * slab_words;
-                    fl |= lb[0];
-                    long long x = (long long)lb[(size_t)S];  // identities of untouched slabs never win
-                    unsigned long long yv = lb[2 * (size_t)S], z = lb[3 * (size_t)S];
-                    iv = mn ? (x < iv ? x : iv) : (x > iv ? x : iv);
-                    fv = mn ? (yv < fv ? yv : fv) : (yv > fv ? yv : fv);
-                    sv = mn ? (z < sv ? z : sv) : (z > sv ? z : sv);
-                }
-                fl = reduce_over_y<RED_OR>(red, fl);
-                if (mn) {
-                    iv = (long long)reduce_over_y<RED_MIN_I64>(red, (uint64_t)iv);
-                    fv = reduce_over_y<RED_MIN_U64>(red, fv);
-                    sv = reduce_over_y<RED_MIN_U64>(red, sv);
-                } else {
-                    iv = (long long)reduce_over_y<RED_MAX_I64>(red, (uint64_t)iv);
-                    fv = reduce_over_y<RED_MAX_U64>(red, fv);
-                    sv = reduce_over_y<RED_MAX_U64>(red, sv);
-                }
-                if (!w || !fl) break;
-                atomicOr(&w[0], fl);
-                if (fl & MM_INT) { if (mn) atomicMin((long long*)&w[1], iv); else atomicMax((long long*)&w[1], iv); }
-                if (fl & MM_FLOAT) { if (mn) atomicMin(&w[2], fv); else atomicMax(&w[2], fv); }
-                if (fl & MM_STRING) { if (mn) atomicMin(&w[3], sv); else atomicMax(&w[3], sv); }
-                break;
-            }
+            case AGG_COUNTN: merge_slabs_agg<AGG_COUNT, 8>(red, l, S, slab_words, nblocks, w); break;
+            case AGG_SUM: merge_slabs_agg<AGG_SUM, 4>(red, l, S, slab_words, nblocks, w); break;
+            case AGG_AVG: merge_slabs_agg<AGG_AVG, 4>(red, l, S, slab_words, nblocks, w); break;
+            case AGG_MIN: merge_slabs_agg<AGG_MIN, 4>(red, l, S, slab_words, nblocks, w); break;
+            default: merge_slabs_agg<AGG_MAX, 4>(red, l, S, slab_words, nblocks, w); break;
         }
     }
 }
@@ -1943,7 +1905,6 @@ __global__ __launch_bounds__(256) void finalize_kernel(const Program P, const Gl
 // over resident columns (n1k_run_device_batch) then starts with its scan, no reopen kernel in front of it.  Replaces
 // finalize_kernel + publish_counters_kernel (+ the next init_table_kernel): three dependent launches of a few microseconds
 // each, which is what a query over 10 M cached rows is made of.
-constexpr uint32_t kFinalizeSmallMax = 8192;
 __global__ __launch_bounds__(1024) void finalize_small_kernel(const Program P, const GlobalTable G, OutValue* out_keys, OutValue* out_aggs,
                                                              OutPartial* out_parts, uint64_t* out_rep, unsigned long long* counters,
                                                              unsigned long long* host_counters, uint64_t max_out, uint32_t* err_flags,
@@ -2002,6 +1963,195 @@ hipError_t launch_finalize_small(const Program& P, const GlobalTable& G, OutValu
     if (G.capacity > kFinalizeSmallMax) return hipErrorInvalidValue;
     hipLaunchKernelGGL(finalize_small_kernel, dim3(1), dim3(1024), 0, st, P, G, out_keys, out_aggs, out_parts, out_rep, counters,
                        host_counters, max_out, err_flags, clear ? 1u : 0u);
+    return hipGetLastError();
+}
+
+// IntermediateGroup + FinalGroup of a one-call execution whose only scan launch left slabs: slabs -> result rows, no table.
+// A workgroup owns kFoldSlots adjacent DIRECT slots (one 128-byte line per slab and word at 16) and folds them over ALL
+// slabs: thread (slot sx, slab-lane bl) takes slabs bl, bl + LANES, ... in chunks of kFoldChunk with every load of a chunk
+// issued before the first is used (a slab beyond the end re-reads slab 0 and is replaced by the identities), the slab-lanes
+// of a wave meet through shuffles, the 16 waves once through LDS.  No other workgroup holds these slots: no atomics on
+// accumulators.  A slot is a group iff its key word is set in some slab; its accumulators, laid out as a table row in LDS,
+// go through finalize_agg into the pinned result buffer exactly as finalize_small_kernel's do.  Row positions: one
+// atomicAdd per workgroup on counters[2], ranks by ballot.  Every workgroup adds its share of the scan's survivor counts to
+// counters[0]; the one that takes the last ticket publishes the counters behind the rows ([1] and [2]: the number of rows)
+// and zeroes them: the device is as n1k_reset leaves it.  The table is not written.  It is read where the scan wrote to it: an integer operand of 2^40 or
+// more in magnitude bypasses the workgroup's narrow sum into the group's table row (acc_global), which counters[1] then
+// counts; such a row is folded in like one more slab, and the host copy of the ticket word says that the table is not
+// empty (the next n1k_reset clears it, as after any other query).
+#ifndef N1K_FOLD_SLOTS
+#define N1K_FOLD_SLOTS 16  // (8: 64-byte segments, twice the workgroups; measured slower)
+#endif
+#ifndef N1K_FOLD_CHUNK
+#define N1K_FOLD_CHUNK 6  // slabs a thread has in flight (aggregates of four slab words: 4)
+#endif
+constexpr uint32_t kFoldSlots = N1K_FOLD_SLOTS, kFoldChunk = N1K_FOLD_CHUNK;
+constexpr uint32_t kFoldStage = kFoldMaxWords + 1;  // (+ 1: the touched word)
+static_assert(kFoldSlots == 4 || kFoldSlots == 8 || kFoldSlots == 16 || kFoldSlots == 32, "slots of a workgroup share a wave");
+
+// One aggregate of a thread's slot over the thread's slabs, then over the wave's slab-lanes.  KEY: the slabs' key words are
+// read along with it (the first aggregate only) and `touched` says whether any of them is set.
+template <uint32_t KIND, uint32_t SLOTS, bool KEY>
+N1K_DEV void fold_rows_agg(const uint64_t* key0, const uint64_t* l, uint32_t S, size_t slab_words, uint32_t nslabs, uint32_t bl,
+                           uint64_t* acc, uint64_t& touched) {
+    constexpr uint32_t LANES = 1024 / SLOTS, NW = fold_slab_words(KIND), CH = NW <= 3 || kFoldChunk < 4 ? kFoldChunk : 4;
+    fold_init(KIND, acc);
+    for (uint32_t b0 = 0; b0 < nslabs; b0 += LANES * CH) {
+        uint64_t x[CH][kFoldMaxWords], k[CH];
+#pragma unroll
+        for (uint32_t c = 0; c < CH; c++) {
+            const uint32_t b = b0 + c * LANES + bl;
+            const size_t at = (size_t)(b < nslabs ? b : 0u) * slab_words;
+            k[c] = KEY ? key0[at] : kEmptyKey;
+#pragma unroll
+            for (uint32_t i = 0; i < NW; i++) x[c][i] = l[at + i * (size_t)S];
+        }
+#pragma unroll
+        for (uint32_t c = 0; c < CH; c++) {
+            const bool valid = b0 + c * LANES + bl < nslabs;
+#pragma unroll
+            for (uint32_t i = 0; i < NW; i++) x[c][i] = valid ? x[c][i] : fold_slab_identity(KIND, i);
+            touched |= valid ? (k[c] ^ kEmptyKey) : 0ull;
+            fold_slab(KIND, acc, x[c]);
+        }
+    }
+    // the slab-lanes of the wave that hold the same slot
+    for (uint32_t off = SLOTS; off < 64; off <<= 1) {
+        uint64_t other[kFoldMaxWords];
+#pragma unroll
+        for (uint32_t i = 0; i < fold_acc_words(KIND); i++) other[i] = (uint64_t)__shfl_xor((unsigned long long)acc[i], (int)off, 64);
+        fold_join(KIND, acc, other);
+        if (KEY) touched |= (uint64_t)__shfl_xor((unsigned long long)touched, (int)off, 64);
+    }
+}
+
+template <uint32_t SLOTS, bool KEY>
+N1K_DEV void fold_rows_kind(uint32_t kind, const uint64_t* key0, const uint64_t* l, uint32_t S, size_t slab_words, uint32_t nslabs,
+                            uint32_t bl, uint64_t* acc, uint64_t& touched) {
+    switch (kind) {
+        case AGG_COUNT:
+        case AGG_COUNTN: fold_rows_agg<AGG_COUNT, SLOTS, KEY>(key0, l, S, slab_words, nslabs, bl, acc, touched); break;
+        case AGG_SUM: fold_rows_agg<AGG_SUM, SLOTS, KEY>(key0, l, S, slab_words, nslabs, bl, acc, touched); break;
+        case AGG_AVG: fold_rows_agg<AGG_AVG, SLOTS, KEY>(key0, l, S, slab_words, nslabs, bl, acc, touched); break;
+        case AGG_MIN: fold_rows_agg<AGG_MIN, SLOTS, KEY>(key0, l, S, slab_words, nslabs, bl, acc, touched); break;
+        default: fold_rows_agg<AGG_MAX, SLOTS, KEY>(key0, l, S, slab_words, nslabs, bl, acc, touched); break;
+    }
+}
+
+template <uint32_t SLOTS>
+__global__ __launch_bounds__(1024) void fold_rows_kernel(const Program P, const FastArgs F, const GlobalTable G, uint32_t nslabs,
+                                                        OutValue* out_keys, OutValue* out_aggs, OutPartial* out_parts,
+                                                        uint64_t* out_rep, unsigned long long* counters, uint32_t ticket_word,
+                                                        unsigned long long* host_counters, uint64_t max_out) {
+    __shared__ uint64_t stage[16][SLOTS][kFoldStage];        // per wave and slot: one aggregate's accumulator, the touched word
+    __shared__ uint64_t accs[SLOTS][kMaxAggs][kFoldMaxWords];  // per slot: every aggregate's accumulator over all slabs
+    __shared__ uint64_t rows[SLOTS][kMaxAggs * kFoldMaxWords];  // ... as the words of a table row (Program::glob_words)
+    __shared__ uint64_t touched_s[SLOTS];
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, sx = tid % SLOTS, bl = tid / SLOTS;
+    const uint32_t S = F.lds_slots;
+    const uint32_t s = blockIdx.x * SLOTS + sx;
+    const size_t slab_words = (size_t)P.lds_words * S;
+    const uint64_t* key0 = F.slabs + (s < S ? s : S - 1);  // (a slot beyond the end re-reads the last one and is no group)
+    // (the join behind the fold: thread (sx, bl) of the first SLOTS * kFoldStage takes stage word bl of slot sx)
+    // wave 0 finishes the workgroup's slots; what it needs besides the fold is requested now and used behind it: the groups the
+    // scan put into the table (an integer too large for the narrow LDS sum bypasses the slab, acc_global), and this
+    // workgroup's share of the scan's survivor counts (-> Filter #itemsOut)
+    unsigned long long in_table = 0, sel = 0;
+    if (wave == 0) {
+        in_table = __hip_atomic_load(&counters[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const uint32_t per = (nslabs + gridDim.x - 1) / gridDim.x, lo = blockIdx.x * per, hi = lo + per < nslabs ? lo + per : nslabs;
+        for (uint32_t b = lo + lane; b < hi; b += 64) sel += F.block_selected[b];
+    }
+    for (uint32_t a = 0; a < P.naggs; a++) {
+        const AggSpec& ag = P.aggs[a];
+        const uint64_t* l = key0 + (size_t)ag.lds_off * S;
+        uint64_t acc[kFoldMaxWords], touched = 0;
+        const bool first = a == 0;  // the key words travel with the first aggregate, once
+        if (first) fold_rows_kind<SLOTS, true>(ag.kind, key0, l, S, slab_words, nslabs, bl, acc, touched);
+        else fold_rows_kind<SLOTS, false>(ag.kind, key0, l, S, slab_words, nslabs, bl, acc, touched);
+        const uint32_t na = fold_acc_words(ag.kind);
+        if (lane < SLOTS) {
+#pragma unroll
+            for (uint32_t i = 0; i < kFoldMaxWords; i++)
+                if (i < na) stage[wave][sx][i] = acc[i];
+            if (first) stage[wave][sx][kFoldMaxWords] = touched;
+        }
+        __syncthreads();
+        if (tid < SLOTS * kFoldStage && (bl < na || (first && bl == kFoldMaxWords))) {
+            const uint32_t op = bl == kFoldMaxWords ? (uint32_t)FOLD_OR : fold_word_op(ag.kind, bl);
+            uint64_t v = stage[0][sx][bl];
+            for (uint32_t w = 1; w < 16; w++) v = fold_word(op, v, stage[w][sx][bl]);
+            if (bl == kFoldMaxWords) touched_s[sx] = v;
+            else accs[sx][a][bl] = v;
+        }
+        __syncthreads();
+    }
+    if (wave != 0) return;
+    for (int off = 32; off > 0; off >>= 1) sel += __shfl_xor(sel, off, 64);
+    if (lane == 0 && sel) atomicAdd(&counters[0], sel);
+    {
+        const bool used = tid < SLOTS && s < S && touched_s[tid % SLOTS] != 0;
+        const unsigned long long m = __ballot(used);
+        unsigned long long first = 0;
+        if (tid == 0 && m) first = atomicAdd(&counters[2], (unsigned long long)__popcll(m));
+        first = __shfl(first, 0, 64);
+        const unsigned long long idx = first + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+        if (used && idx < max_out) {
+            uint64_t* g = rows[tid % SLOTS];
+            const uint64_t key = fast_slot_key(F, s);
+            if (in_table) {  // the group's row there, if it has one, is one more partial fold (read only: n1k_reset clears the table)
+                const uint64_t mask = G.capacity - 1;
+                uint64_t at = mix64(key) & mask;
+                for (uint64_t probe = 0; probe < G.capacity; probe++, at = (at + 1) & mask) {
+                    const uint64_t cur = G.keys[at];
+                    if (cur == kEmptyKey) break;
+                    if (cur != key) continue;
+                    for (uint32_t a = 0; a < P.naggs; a++)
+                        fold_join(P.aggs[a].kind, accs[tid % SLOTS][a], &G.acc[at * P.glob_words + P.aggs[a].glob_off]);
+                    break;
+                }
+            }
+            for (uint32_t a = 0; a < P.naggs; a++) fold_row(P.aggs[a].kind, accs[tid % SLOTS][a], g + P.aggs[a].glob_off);
+            for (uint32_t k = 0; k < P.nkeys; k++) {
+                const KeySpec& ks = P.keys[k];
+                uint64_t field = ks.bits >= 64 ? key : ((key >> ks.shift) & ((1ull << ks.bits) - 1ull));
+                uint32_t tag;
+                uint64_t p;
+                unpack_key_field(P, ks.mode, field, tag, p);
+                put_value(&out_keys[idx * P.nkeys + k], tag, p);
+            }
+            for (uint32_t a = 0; a < P.naggs; a++)
+                finalize_agg(P, P.aggs[a], g, &out_aggs[idx * P.naggs + a], &out_parts[idx * P.naggs + a], F.err_flags);
+            if (out_rep) out_rep[idx] = P.emit_packed_key ? key : ~0ull;
+        }
+    }
+    // the last workgroup done: every other one's position, survivor and error-flag atomics are behind its ticket (all of
+    // them this wave's: no barrier)
+    uint32_t last = 0;
+    __threadfence();
+    if (lane == 0) last = atomicAdd(&counters[ticket_word], 1ull) == (unsigned long long)gridDim.x - 1ull ? 1u : 0u;
+    if (!__shfl(last, 0, 64)) return;
+    __threadfence();
+    unsigned long long v = __hip_atomic_load(&counters[lane % kCounters], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned long long nrows_out = __shfl(v, 2, 64);
+    in_table = __shfl(v, 1, 64);
+    if (lane == 1 || lane == 2) v = nrows_out;  // (groups: the table does not count them)
+    if (lane == ticket_word) v = in_table;      // not zero: the table is not empty, the host has n1k_reset clear it
+    if (lane < kCounters) {
+        host_counters[lane] = v;
+        counters[lane] = 0;
+    }
+}
+
+hipError_t launch_fold_rows(const Program& P, const FastArgs& F, const GlobalTable& G, uint32_t nslabs, OutValue* out_keys,
+                            OutValue* out_aggs, OutPartial* out_parts, uint64_t* out_rep, unsigned long long* counters,
+                            uint32_t ticket_word, unsigned long long* host_counters, uint64_t max_out, hipStream_t st) {
+    if (!G.capacity || (G.capacity & (G.capacity - 1)) || !F.slabs || !F.block_selected || !nslabs || !F.lds_slots || F.hashed) return hipErrorInvalidValue;
+    if (ticket_word < 3 || ticket_word >= kCounters || P.naggs == 0) return hipErrorInvalidValue;
+    for (uint32_t a = 0; a < P.naggs; a++)
+        if (P.aggs[a].distinct || P.aggs[a].kind > AGG_MAX) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(fold_rows_kernel<kFoldSlots>, dim3((F.lds_slots + kFoldSlots - 1) / kFoldSlots), dim3(1024), 0, st, P, F, G,
+                       nslabs, out_keys, out_aggs, out_parts, out_rep, counters, ticket_word, host_counters, max_out);
     return hipGetLastError();
 }
 

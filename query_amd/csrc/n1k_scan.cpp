@@ -290,9 +290,10 @@ static ScanChoice choose_scan(n1k_handle* h, uint64_t nrows) {
 }
 
 // Rows [off, off + n) of the bound columns through the chosen kernel on program P: slabs for the grid, the launch, the
-// merge.  A specialised kernel takes its WIDE form (2 adjacent rows per lane and load) over the even prefix of aligned
+// merge — or, slabs_to_rows, none: the slabs stay for n1k_finish.
+// A specialised kernel takes its WIDE form (2 adjacent rows per lane and load) over the even prefix of aligned
 // columns, and an odd last row through a second, scalar launch.
-static n1k_status launch_chunk(n1k_handle* h, const ScanChoice& c, const Program& P, FastArgs& F, const WordLogArgs& L, uint64_t off, uint64_t n) {
+static n1k_status launch_chunk(n1k_handle* h, const ScanChoice& c, const Program& P, FastArgs& F, const WordLogArgs& L, uint64_t off, uint64_t n, bool only_chunk) {
     unsigned long long* ngroups = h->groups.counters.p + CTR_GROUPS;
     auto launch = [&](uint32_t g, bool wide) {
         if (c.kernel.spec) return c.kernel.spec->launch(P, F, h->groups.table, ngroups, g, c.fblock, wide, L, h->stream);
@@ -318,7 +319,12 @@ static n1k_status launch_chunk(n1k_handle* h, const ScanChoice& c, const Program
         F.block_selected = h->groups.block_sel.p;
     }
     HIP_TRY(h, launch(g, wide));
-    if (F.slabs) HIP_TRY(h, launch_merge_slabs(P, F, h->groups.table, g, ngroups, h->stream, h->opt.merge_chunks));
+    if (F.slabs && &P == &h->prog && slabs_to_rows(h, F, g, only_chunk, n_main == n)) {
+        // a one-call execution's only launch: n1k_finish folds the slabs straight into result rows (read_counters)
+        h->groups.pending.grid = g;
+        h->groups.pending.F = F;
+    } else if (F.slabs)
+        HIP_TRY(h, launch_merge_slabs(P, F, h->groups.table, g, ngroups, h->stream, h->opt.merge_chunks));
     F.slabs = nullptr;
     if (n_main < n) {
         advance_cols(F.cols, F.ncols, n_main);
@@ -352,7 +358,7 @@ static n1k_status run_shaped(n1k_handle* h, ScanChoice& c, const ScanArgs& A, ui
     if (e0) (void)hipEventRecord(e0, h->stream);
     const uint64_t chunk = 1ull << 31;  // 32-bit row indices inside one launch
     for (uint64_t off = 0; off < nrows; off += chunk) {
-        n1k_status st = launch_chunk(h, c, P, F, L, off, std::min<uint64_t>(chunk, nrows - off));
+        n1k_status st = launch_chunk(h, c, P, F, L, off, std::min<uint64_t>(chunk, nrows - off), nrows <= chunk);
         if (st != N1K_OK) return st;
     }
     if (e1) (void)hipEventRecord(e1, h->stream);
@@ -554,6 +560,8 @@ n1k_status materialize_derived(n1k_handle* h, const n1k_batch* b) {
 
 n1k_status push_device(n1k_handle* h, const n1k_batch* b) {
     if (h->stop_flag.load()) return fail(h, N1K_STOPPED, "operator was stopped");
+    // (the first push behind a reset that left the device clean; a second push finds device_clean false)
+    h->groups.pending.clean_at_push = h->device_clean && h->row_base == 0 && h->groups.merged_bound == 0 && !h->groups.pending.grid;
     h->device_clean = false;
     n1k_status st = ensure_device(h);
     if (st != N1K_OK) return st;
@@ -604,6 +612,7 @@ n1k_status push_device(n1k_handle* h, const n1k_batch* b) {
         groups_est = std::min<uint64_t>(b->nrows, h->part.sticky.groups_est * b->nrows / std::max<uint64_t>(h->part.sticky.rows, 1) + 1024);
     }
     if (decide) {
+        h->groups.pending.clean_at_push = false;  // (the probe's keys are in the table)
         // probe: Filter + group key of the first `head` rows into the table (keys only), counted before and after
         st = ensure_table(h, head);
         if (st != N1K_OK) return st;
