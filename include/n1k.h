@@ -230,6 +230,21 @@ typedef struct n1k_handle n1k_handle;
  *     term may name a term's alias (`alias`) or repeat its expression; star / raw / distinct projections are N1K_UNSUPPORTED;
  *     the HAVING condition and the sort terms may name only group keys and aggregates of the plan (by their text);
  *     offset / limit are integer constants.  n1k_finish then returns the groups filtered, ordered and cut.
+ * A VALUE of the Filter / InitialGroup part — a group key, an aggregate's operand, an operand of a comparison or of arithmetic, a
+ * bare condition — may be, besides a leaf path, a constant, arithmetic, round / trunc / abs / ceil / floor / sign / sqrt and
+ * greatest / least:
+ *     case when <cond> then <value> [when … then …]* [else <value>] end            (expression/case_searched.go:73-100)
+ *     case <value> when <value> then <value> … [else <value>] end                  (case_simple.go:78-110)
+ *     ifmissing(a, b, …)  ifnull(a, b, …)  ifmissingornull(a, b, …)  with 2 to 4 arguments,   (func_cond_unknown.go)
+ *     nullif(a, b)  missingif(a, b)
+ *   evaluated per row on the device, the arms of a CASE in order and each row only up to its first taken arm.  Their operands are
+ *   values again (paths, constants, arithmetic, another of these).  A STRING they return is a code of the handle's dictionary:
+ *   a THEN constant equal to a string the columns hold is that string.  N1K_UNSUPPORTED, each named in n1k_create_error: more
+ *   than 8 WHEN arms; more than 16 predicate terms or 32 logic ops in the WHENs of one CASE; more than 4 arguments; LIKE,
+ *   ANY / EVERY, IN or a string function inside a WHEN; greatest / least inside one of them; one of them in HAVING, in a
+ *   projection over the groups, as a sort term or as a DISTINCT term of a Filter-only plan; more than 16 columns counting the
+ *   plan's leaf paths, its arithmetic nodes and these.  A WHEN that orders two arrays / objects is N1K_UNSUPPORTED_DATA at run
+ *   time, for the rows that reach that arm only.  Text that is no CASE (a missing THEN or END) is N1K_INVALID.
  * exactly as plan.(*Filter).MarshalJSON (plan/filter.go:46-53),
  * plan.(*InitialGroup).MarshalJSON (plan/group.go:54-70), plan/sequence.go:48-57 and
  * plan/parallel.go:54-67 emit them; expressions are expression.Stringer text.

@@ -40,6 +40,9 @@ uint32_t lookup_code(const n1k_handle* h, const char* s) {
     return it == h->dict_index.end() ? 0xFFFFFFFFu : it->second;
 }
 
+static bool cond_operand(n1k_handle* h, const Expr* e, Operand& o, PlanError& err);
+static bool cond_fn_name(const std::string& f) { return f == "ifmissing" || f == "ifnull" || f == "ifmissingornull" || f == "nullif" || f == "missingif"; }
+
 bool to_operand(n1k_handle* h, const Expr* e, Operand& o, PlanError& err) {
     memset(&o, 0, sizeof o);
     if (e->kind == EK::Path) {
@@ -65,10 +68,18 @@ bool to_operand(n1k_handle* h, const Expr* e, Operand& o, PlanError& err) {
         }
         return true;
     }
+    if (e->kind == EK::Case || (e->kind == EK::Func && cond_fn_name(e->fname))) return cond_operand(h, e, o, err);
     // arithmetic node -> derived column evaluated once per batch (expression/arith_*.go, func_num.go)
     uint32_t op;
     if (e->kind == EK::Func) {
         const std::string& f = e->fname;
+        if (h->cond_depth && (f == "greatest" || f == "least")) {
+            // (they can raise ERR_UNSUPPORTED_VALUE, and the operand of an arm that is not taken is evaluated all the same: the
+            //  reference, which evaluates lazily, would never see that error)
+            err.unsupported = true;
+            err.msg = "'" + f + "' inside CASE or a conditional function does not run on the device";
+            return false;
+        }
         if (strfn_name(f)) {  // (its value is a new string per row, not a dictionary code: only a term's predicate is tabulated)
             err.unsupported = true;
             err.msg = "string function '" + f + "' used as a value (a group key, an aggregate's operand, an operand of arithmetic or of a comparison with a path): only a Filter / HAVING term over it runs on the device";
@@ -159,41 +170,46 @@ bool to_operand(n1k_handle* h, const Expr* e, Operand& o, PlanError& err) {
     return true;
 }
 
-// condition tree -> postfix over predicate terms
-bool compile_cond(n1k_handle* h, const Expr* e, PlanError& err) {
-    Program& P = h->prog;
+// condition tree -> postfix over predicate terms, into the Filter's program or into a conditional node (T)
+static bool compile_cond(n1k_handle* h, const Expr* e, const CondTarget& T, PlanError& err) {
+    auto too_large = [&]() {
+        err.unsupported = true;
+        err.msg = T.in_node ? "the WHEN conditions of one CASE hold more than " + std::to_string(T.max_terms) + " terms or " + std::to_string(T.max_logic) + " logic ops"
+                            : std::string("condition too large for the device program");
+        return false;
+    };
     auto push_term = [&](uint32_t op, const Expr* a, const Expr* b, const Expr* c) -> bool {
-        if (P.nterms >= (uint32_t)kMaxTerms || P.nlogic >= (uint32_t)kMaxLogic) {
-            err.unsupported = true;
-            err.msg = "condition too large for the device program";
-            return false;
-        }
-        Term& t = P.terms[P.nterms];
+        if (*T.nterms >= T.max_terms || *T.nlogic >= T.max_logic) return too_large();
+        Term& t = T.terms[*T.nterms];
         memset(&t, 0, sizeof t);
         t.op = op;
         if (a && !to_operand(h, a, t.a, err)) return false;
         if (b && !to_operand(h, b, t.b, err)) return false;
         if (c && !to_operand(h, c, t.c, err)) return false;
-        P.logic[P.nlogic++] = LogicOp{LOGIC_PUSH, (uint8_t)P.nterms};
-        P.nterms++;
+        T.logic[(*T.nlogic)++] = LogicOp{LOGIC_PUSH, (uint8_t)*T.nterms};
+        (*T.nterms)++;
         return true;
     };
     auto push_logic = [&](uint8_t op, uint8_t arg) -> bool {
-        if (P.nlogic >= (uint32_t)kMaxLogic) {
-            err.unsupported = true;
-            err.msg = "condition too large for the device program";
-            return false;
-        }
-        P.logic[P.nlogic++] = LogicOp{op, arg};
+        if (*T.nlogic >= T.max_logic) return too_large();
+        T.logic[(*T.nlogic)++] = LogicOp{op, arg};
         return true;
     };
+    // The match table's bits are laid out over the Filter's program alone (MatchTable::finalize_bits): its four kinds of term
+    // stay out of a WHEN.
+    if (T.in_node && (strfn_term(e) || e->kind == EK::Like || e->kind == EK::Coll || e->kind == EK::In)) {
+        err.unsupported = true;
+        err.msg = std::string(e->kind == EK::Like ? "LIKE" : e->kind == EK::Coll ? "ANY / EVERY" : e->kind == EK::In ? "IN" : "a string function") +
+                  " in the WHEN of a CASE does not run on the device (only a Filter / HAVING term reads the match table)";
+        return false;
+    }
     // The fourth kind of the match table: a term over string functions of one leaf path (n1k_strfn.h).  Like the three
     // below: compiled once per plan, evaluated once per distinct dictionary entry; equal programs share predicate and bit.
     if (strfn_term(e)) {
         const Expr* path = nullptr;
         const int ix = h->match.add_strfn(e, path, err);
         if (ix < 0 || !push_term(TERM_STRFN, path, nullptr, nullptr)) return false;
-        Operand& b = P.terms[P.nterms - 1].b;
+        Operand& b = T.terms[*T.nterms - 1].b;
         b.is_const = 1;
         b.ctag = T_STRING;
         b.cpayload = (uint64_t)ix;
@@ -204,10 +220,10 @@ bool compile_cond(n1k_handle* h, const Expr* e, PlanError& err) {
         case EK::Or:
             if (e->ch.size() > 16) { err.unsupported = true; err.msg = "AND/OR arity > 16"; return false; }
             for (auto& c : e->ch)
-                if (!compile_cond(h, c.get(), err)) return false;
+                if (!compile_cond(h, c.get(), T, err)) return false;
             return push_logic(e->kind == EK::And ? LOGIC_AND : LOGIC_OR, (uint8_t)e->ch.size());
         case EK::Not:
-            if (!compile_cond(h, e->ch[0].get(), err)) return false;
+            if (!compile_cond(h, e->ch[0].get(), T, err)) return false;
             return push_logic(LOGIC_NOT, 0);
         case EK::Eq:
         case EK::LT:
@@ -245,7 +261,7 @@ bool compile_cond(n1k_handle* h, const Expr* e, PlanError& err) {
             }
             const int ix = h->match.add_like(pat->cstr, err);
             if (ix < 0 || !push_term(TERM_LIKE, e->ch[0].get(), nullptr, nullptr)) return false;
-            Operand& b = P.terms[P.nterms - 1].b;
+            Operand& b = T.terms[*T.nterms - 1].b;
             b.is_const = 1;
             b.ctag = T_STRING;
             b.cpayload = (uint64_t)ix;
@@ -254,7 +270,7 @@ bool compile_cond(n1k_handle* h, const Expr* e, PlanError& err) {
         case EK::Coll: {
             const int ix = h->match.add_coll(e, err);
             if (ix < 0 || !push_term(TERM_COLL, e->ch[0].get(), nullptr, nullptr)) return false;
-            Operand& b = P.terms[P.nterms - 1].b;
+            Operand& b = T.terms[*T.nterms - 1].b;
             b.is_const = 1;
             b.ctag = T_ARRAY;
             b.cpayload = (uint64_t)ix;
@@ -266,7 +282,7 @@ bool compile_cond(n1k_handle* h, const Expr* e, PlanError& err) {
             const int ix = h->match.add_in(e, err);
             if (ix < 0 || !push_term(TERM_IN, e->ch[0].get(), nullptr, nullptr)) return false;
             const InList& l = h->match.lists[(size_t)ix];
-            Term& t = P.terms[P.nterms - 1];
+            Term& t = T.terms[*T.nterms - 1];
             t.b.is_const = t.c.is_const = 1;
             t.b.ctag = t.c.ctag = T_ARRAY;
             t.b.cpayload = (uint64_t)ix;
@@ -283,10 +299,82 @@ bool compile_cond(n1k_handle* h, const Expr* e, PlanError& err) {
     }
 }
 
+// CASE / a conditional function as a value -> one conditional node (n1k_cond.h), a derived column behind those of its
+// operands.  Every operand — THEN, ELSE, function arguments, both sides of a WHEN comparison — goes through to_operand.
+static bool cond_operand(n1k_handle* h, const Expr* e, Operand& o, PlanError& err) {
+    auto refuse = [&](const std::string& m) {
+        err.unsupported = true;
+        err.msg = m;
+        return false;
+    };
+    CondNode n;
+    memset(&n, 0, sizeof n);
+    const CondTarget T{n.terms, n.logic, &n.nterms, &n.nlogic, (uint32_t)kCondMaxTerms, (uint32_t)kCondMaxLogic, true};
+    h->cond_depth++;
+    struct Leave { n1k_handle* h; ~Leave() { h->cond_depth--; } } leave{h};
+    if (e->kind == EK::Case) {
+        n.mode = COND_CASE;
+        const size_t first = e->case_simple ? 1 : 0, narms = (e->ch.size() - first - (e->case_else ? 1 : 0)) / 2;
+        if (narms > (size_t)kCondMaxArms) return refuse("CASE with " + std::to_string(narms) + " WHEN arms: the device takes 1 to " + std::to_string(kCondMaxArms));
+        Operand search{};
+        if (e->case_simple && !to_operand(h, e->ch[0].get(), search, err)) return false;  // (compiled once, read by every arm)
+        for (size_t k = 0; k < narms; k++) {
+            CondArm& arm = n.arms[n.narms++];
+            const Expr* when = e->ch[first + 2 * k].get();
+            arm.logic_begin = n.nlogic;
+            if (e->case_simple) {  // search.Equals(when).Truth(): a TERM_EQ of the two operands
+                if (n.nterms >= (uint32_t)kCondMaxTerms || n.nlogic >= (uint32_t)kCondMaxLogic)
+                    return refuse("the WHEN conditions of one CASE hold more than " + std::to_string(kCondMaxTerms) + " terms");
+                Term& t = n.terms[n.nterms];
+                t.op = TERM_EQ;
+                t.a = search;  // (a STRING constant: every copy names the same entry of const_strings and is resolved alike)
+                if (!to_operand(h, when, t.b, err)) return false;
+                n.logic[n.nlogic++] = LogicOp{LOGIC_PUSH, (uint8_t)n.nterms++};
+            } else if (!compile_cond(h, when, T, err))
+                return false;
+            arm.logic_end = n.nlogic;
+            if (!to_operand(h, e->ch[first + 2 * k + 1].get(), arm.then, err)) return false;
+        }
+        if (e->case_else) {
+            n.has_else = 1;
+            if (!to_operand(h, e->ch.back().get(), n.els, err)) return false;
+        }
+    } else {
+        const std::string& f = e->fname;
+        n.mode = f == "ifmissing" ? COND_IFMISSING : f == "ifnull" ? COND_IFNULL : f == "ifmissingornull" ? COND_IFMISSINGORNULL
+                 : f == "nullif" ? COND_NULLIF : COND_MISSINGIF;
+        if (n.mode == COND_NULLIF || n.mode == COND_MISSINGIF) {
+            CondArm& arm = n.arms[n.narms++];
+            Term& t = n.terms[n.nterms];
+            t.op = TERM_EQ;
+            if (!to_operand(h, e->ch[0].get(), t.a, err) || !to_operand(h, e->ch[1].get(), t.b, err)) return false;
+            n.logic[n.nlogic++] = LogicOp{LOGIC_PUSH, (uint8_t)n.nterms++};
+            arm.logic_end = n.nlogic;
+            arm.then = t.a;
+        } else {
+            // (chaining f(f(a, b, c, d), e) is not exact: the inner node's NULL for "none" would stop the outer one)
+            if (e->ch.size() > 4) return refuse(f + " with " + std::to_string(e->ch.size()) + " arguments: the device takes 2 to 4");
+            for (auto& c : e->ch)
+                if (!to_operand(h, c.get(), n.arms[n.narms++].then, err)) return false;
+        }
+    }
+    if (h->plan.paths.size() + h->derived.size() >= (size_t)kMaxCols) return refuse("too many columns (inputs + arithmetic and conditional nodes > 16)");
+    n1k_handle::Derived d{};
+    d.op = AR_COND;
+    d.node = (uint32_t)h->cond_nodes.size();
+    h->cond_nodes.push_back(n);
+    memset(&o, 0, sizeof o);
+    o.col = (uint32_t)(h->plan.paths.size() + h->derived.size());
+    h->derived.push_back(d);
+    return true;
+}
+
 bool compile_plan(n1k_handle* h, PlanError& err) {
     Program& P = h->prog;
     memset(&P, 0, sizeof P);
     h->derived.clear();
+    h->cond_nodes.clear();
+    h->cond_uploaded = false;
     h->const_strings.clear();
     h->match.clear_plan();
     const ParsedPlan& pl = h->plan;
@@ -294,7 +382,8 @@ bool compile_plan(n1k_handle* h, PlanError& err) {
     if (pl.keys.size() > (size_t)kMaxKeys) { err.unsupported = true; err.msg = "more than 4 group keys"; return false; }
     if (pl.aggs.size() > (size_t)kMaxAggs) { err.unsupported = true; err.msg = "more than 8 aggregates"; return false; }
     P.ncols = (uint32_t)pl.paths.size();
-    if (pl.condition && !compile_cond(h, pl.condition.get(), err)) return false;
+    const CondTarget filter{P.terms, P.logic, &P.nterms, &P.nlogic, (uint32_t)kMaxTerms, (uint32_t)kMaxLogic, false};
+    if (pl.condition && !compile_cond(h, pl.condition.get(), filter, err)) return false;
     h->match.finalize_bits(P);
     P.nkeys = (uint32_t)pl.keys.size();
     for (uint32_t k = 0; k < P.nkeys; k++)
@@ -697,6 +786,12 @@ n1k_status n1k_create(const char* plan_json, size_t len, n1k_handle** out) {
             g_create_error = "HAVING: " + g_create_error;
             delete h;
             return hst;
+        }
+        if (!h->tail.having->cond_nodes.empty()) {  // (the inner handle sees this handle's dictionary codes, not its own)
+            g_create_error = "HAVING: CASE or a conditional function over the groups does not run on the device";
+            n1k_destroy(h->tail.having);
+            delete h;
+            return N1K_UNSUPPORTED;
         }
         for (const std::string& p : h->tail.having->plan.paths) {
             int idx = -1;
@@ -1130,7 +1225,7 @@ n1k_status n1k_jit_check(n1k_handle* h, const uint32_t* col_kinds, uint32_t ncol
     FastArgs F;
     const uint32_t max_slots = (uint32_t)std::min<uint64_t>((156u * 1024u) / (h->prog.lds_words * 8), 1u << 15);
     // (plans with arithmetic: the shape that evaluates the nodes in registers, the one choose_scan tries first)
-    const bool fuse = !h->derived.empty() && h->opt.fuse_arith;
+    const bool fuse = !h->derived.empty() && h->cond_nodes.empty() && h->opt.fuse_arith;
     if (!build_fast_args(h, max_slots, F, fuse)) return fail(h, N1K_UNSUPPORTED, "the plan shape is outside the bounded family");
     std::string l;
     bool ok = shape_compiles(h, F, ShapeUse::Scan, &l);

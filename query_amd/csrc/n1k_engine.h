@@ -28,6 +28,7 @@
 #include "n1k_json.h"
 #include "n1k_kernels.h"
 #include "n1k_coll.h"
+#include "n1k_cond.h"
 #include "n1k_in.h"
 #include "n1k_like.h"
 #include "n1k_order.h"
@@ -529,8 +530,14 @@ struct n1k_handle {
     bool has_distinct = false, has_minmax = false, has_array_agg = false;
     uint32_t n_distinct = 0;
     // arithmetic operands -> derived columns (input columns first, then one per arithmetic node)
-    struct Derived { uint32_t op, nops; Operand ops[4]; };
+    struct Derived { uint32_t op, nops; Operand ops[4]; uint32_t node; };  // node: op AR_COND, the node's index in cond_nodes
     std::vector<Derived> derived;
+    // CASE and the conditional functions (n1k_cond.h): the nodes' programs, in device memory once their string constants have
+    // their codes (materialize_derived) and until the plan is compiled again
+    std::vector<CondNode> cond_nodes;
+    DevBuf<CondNode> d_cond;
+    bool cond_uploaded = false;
+    uint32_t cond_depth = 0;  // (compile time: inside how many conditional nodes to_operand is)
     std::vector<std::string> const_strings;  // string constants of the plan, interned lazily (see to_operand)
     std::vector<DevBuf<uint8_t>> dv_tags;
     std::vector<DevBuf<uint64_t>> dv_payload;

@@ -262,6 +262,85 @@ __global__ void arith_kernel(const ArithArgs A) {
     A.out_payload[i] = rp;
 }
 
+// ------------------------------------------------------------------ derived columns (CASE and the conditional functions)
+//
+// One conditional node (n1k_cond.h) over the program's columns, one row per lane.  The arms are evaluated in order and a row
+// is CLOSED by the first arm it takes: a closed row is not `valid` for load_operand / eval_term any more, so it loads
+// nothing and raises nothing — `unsupported` (arrays / objects under <) comes only from arms a row actually reaches, as in
+// the reference, which never evaluates a later WHEN (expression/case_searched.go:73-100).  A wave whose rows are all closed
+// leaves the loop.  The node is wave-uniform data in device memory; the conditions run through eval_term and the logic_*
+// helpers, as a Filter's do (eval_predicate).
+N1K_DEV uint32_t cond_eval_logic(const Program& P, const CondNode& N, uint32_t begin, uint32_t end, const uint64_t (&row)[1],
+                                 const bool (&open)[1], uint32_t& unsupported) {
+    uint64_t st = 0;
+    for (uint32_t i = begin; i < end; i++) {
+        const LogicOp op = N.logic[i];
+        if (op.op == LOGIC_PUSH) {
+            uint32_t l[1];
+            eval_term<1>(P, N.terms[op.arg], row, open, l, unsupported);
+            st = (st << 2) | l[0];
+        } else if (op.op == LOGIC_AND) {
+            const uint32_t r = logic_and(st, op.arg);
+            st = (st << 2) | r;
+        } else if (op.op == LOGIC_OR) {
+            const uint32_t r = logic_or(st, op.arg);
+            st = (st << 2) | r;
+        } else
+            st = (st & ~3ull) | logic_not((uint32_t)(st & 3ull));
+    }
+    return (uint32_t)(st & 3ull);
+}
+
+__global__ __launch_bounds__(256) void cond_kernel(const Program P, const CondArgs C) {
+    const CondNode& N = *C.node;
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    bool in = i < C.nrows;
+    if (in && C.nseg > 1) {
+        const uint64_t s = i / C.seg_rows;
+        in = s < C.nseg && i - s * C.seg_rows < C.seg_counts[s * kCursorStride];
+    } else if (in && C.nrows_dev)
+        in = i < *C.nrows_dev;
+    const uint64_t row[1] = {i};
+    bool open[1] = {in};
+    uint32_t rt = T_NULL, unsupported = 0;  // (no arm taken and no ELSE, no operand that qualifies: NULL)
+    uint64_t rp = 0;
+    uint32_t t[1];
+    uint64_t p[1];
+    if (N.mode == COND_NULLIF || N.mode == COND_MISSINGIF) {
+        // eq = a.Equals(b): MISSING / NULL -> eq itself, TRUE -> NULL (MISSING), else a (expression/func_cond_unknown.go:278-290, 347-359)
+        const uint32_t eq = cond_eval_logic(P, N, N.arms[0].logic_begin, N.arms[0].logic_end, row, open, unsupported);
+        const bool keep[1] = {in && eq == L_FALSE};
+        load_operand<1>(P, N.arms[0].then, row, keep, t, p);
+        if (keep[0]) { rt = t[0]; rp = p[0]; }
+        else rt = eq == L_MISSING ? (uint32_t)T_MISSING : (eq == L_NULL ? (uint32_t)T_NULL : (N.mode == COND_NULLIF ? (uint32_t)T_NULL : (uint32_t)T_MISSING));
+    } else {
+        for (uint32_t a = 0; a < N.narms; a++) {
+            if (__ballot(open[0]) == 0) break;
+            const CondArm& arm = N.arms[a];
+            bool hit;
+            if (N.mode == COND_CASE) {
+                hit = open[0] && cond_eval_logic(P, N, arm.logic_begin, arm.logic_end, row, open, unsupported) == L_TRUE;
+                const bool sel[1] = {hit};
+                load_operand<1>(P, arm.then, row, sel, t, p);
+            } else {  // IFMISSING / IFNULL / IFMISSINGORNULL: the operand is what is tested and what is given
+                load_operand<1>(P, arm.then, row, open, t, p);
+                hit = open[0] && (N.mode == COND_IFMISSING ? t[0] != T_MISSING : (N.mode == COND_IFNULL ? t[0] != T_NULL : t[0] > T_NULL));
+            }
+            if (hit) { rt = t[0]; rp = p[0]; }
+            open[0] = open[0] && !hit;
+        }
+        if (N.mode == COND_CASE && N.has_else && __ballot(open[0]) != 0) {
+            load_operand<1>(P, N.els, row, open, t, p);
+            if (open[0]) { rt = t[0]; rp = p[0]; }
+        }
+    }
+    if (i < C.nrows) {  // (a row the batch does not hold: NULL, which nothing reads)
+        C.out_tags[i] = (uint8_t)rt;
+        C.out_payload[i] = rp;
+    }
+    if (unsupported) atomicOr(C.err_flags, (uint32_t)ERR_UNSUPPORTED_VALUE);
+}
+
 // ------------------------------------------------------------------ K6: DISTINCT sets
 // (distinct_classify / member_word_bits / radix_bin live in n1k_tables.h: the specialised scan uses them too)
 N1K_DEV bool member_word(const ScanArgs& A, uint64_t key, uint32_t cls, uint64_t val, uint64_t& word) {
@@ -3464,6 +3543,13 @@ hipError_t launch_arith(const ArithArgs& A, hipStream_t st) {
     if (A.nrows == 0) return hipSuccess;
     uint32_t blocks = (uint32_t)((A.nrows + 255) / 256);
     hipLaunchKernelGGL(arith_kernel, dim3(blocks), dim3(256), 0, st, A);
+    return hipGetLastError();
+}
+
+hipError_t launch_cond(const Program& P, const CondArgs& C, hipStream_t st) {
+    if (C.nrows == 0) return hipSuccess;
+    uint32_t blocks = (uint32_t)((C.nrows + 255) / 256);
+    hipLaunchKernelGGL(cond_kernel, dim3(blocks), dim3(256), 0, st, P, C);
     return hipGetLastError();
 }
 

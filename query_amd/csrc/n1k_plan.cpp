@@ -417,6 +417,26 @@ struct EParser {
                     if (e->ch.size() < minargs || e->ch.size() > maxargs) return bad(w + " takes " + std::to_string(minargs) + (maxargs > minargs ? " or 2" : "") + " arguments");
                     return e;
                 }
+                // Conditional functions (expression/func_cond_unknown.go; registry names func_registry.go:321-325): a node like
+                // the numeric functions'.  How many operands the device takes is decided where it is compiled (cond_operand).
+                const bool cond_first = w == "ifmissing" || w == "ifnull" || w == "ifmissingornull", cond_eq = w == "nullif" || w == "missingif";
+                if ((cond_first || cond_eq) && lx.toks[p + 1].kind == TK::LParen) {
+                    p += 2;
+                    auto e = mk(EK::Func);
+                    e->fname = w;
+                    for (;;) {
+                        auto a = primary();
+                        if (!a) return nullptr;
+                        e->ch.push_back(std::move(a));
+                        if (cur().kind == TK::Comma) { p++; continue; }
+                        break;
+                    }
+                    if (cur().kind != TK::RParen) return bad("expected ) in " + w);
+                    p++;
+                    if (e->ch.size() < 2 || (cond_eq && e->ch.size() != 2)) return bad(w + (cond_eq ? " takes 2 arguments" : " takes at least 2 arguments"));
+                    return e;
+                }
+                if (w == "case") return case_expr();
                 if ((w == "any" || w == "every") && lx.toks[p + 1].kind != TK::LParen) return collection();
                 return unsupported("function or keyword '" + w + "'");
             }
@@ -424,6 +444,46 @@ struct EParser {
             case TK::Other: return unsupported("token '" + t.text + "'");
             default: return bad("unexpected token at offset " + std::to_string(t.begin));
         }
+    }
+
+    // stringer.go VisitSearchedCase / VisitSimpleCase (:115-154), no parentheses of its own:
+    //   case [<search>] when <w> then <v> [when <w> then <v>]* [else <v>] end
+    // ch: [search] (when, then)* [else], in text order — the order collect_paths walks.
+    std::unique_ptr<Expr> case_expr() {
+        p++;  // case
+        auto e = mk(EK::Case);
+        auto operand = [&]() -> std::unique_ptr<Expr> {  // (a keyword of the CASE itself where an expression must stand is malformed text)
+            if (is_word("when") || is_word("then") || is_word("else") || is_word("end")) return bad("expected an expression before '" + cur().text + "' in CASE");
+            return primary();
+        };
+        if (!is_word("when")) {
+            auto s = operand();
+            if (!s) return nullptr;
+            e->case_simple = true;
+            e->ch.push_back(std::move(s));
+        }
+        if (!is_word("when")) return bad("expected WHEN in CASE");
+        while (is_word("when")) {
+            p++;
+            auto c = operand();
+            if (!c) return nullptr;
+            if (!is_word("then")) return bad("expected THEN after the WHEN of a CASE");
+            p++;
+            auto v = operand();
+            if (!v) return nullptr;
+            e->ch.push_back(std::move(c));
+            e->ch.push_back(std::move(v));
+        }
+        if (is_word("else")) {
+            p++;
+            auto v = operand();
+            if (!v) return nullptr;
+            e->case_else = true;
+            e->ch.push_back(std::move(v));
+        }
+        if (!is_word("end")) return bad("expected END after CASE");
+        p++;
+        return e;
     }
 
     // stringer.go VisitAny / VisitEvery / VisitAnyEvery + visitBindings (no parentheses of its own):

@@ -27,8 +27,11 @@ enum class EK {
            // coll_any_every.go): ch[0] the binding expression, coll_* the rest
     In,    // (a in [c, c, ...]), expression/coll_in.go, over a constant list: ch[0] the left operand, ch[1..] the elements
            // (Const), `text` the bracketed list as the stringer wrote it; NOT IN arrives as (not (a in [...]))
+    Case,  // case [search] when .. then .. [else ..] end (expression/case_searched.go, case_simple.go): ch = [search] (when, then)*
+           // [else], case_simple / case_else say which of the optional ones are there
     Func  // numeric functions of one or two arguments (expression/func_num.go) and the string functions a term may hold
-          // (expression/func_str.go; n1k_strfn.h): fname
+          // (expression/func_str.go; n1k_strfn.h), and the conditional functions ifmissing / ifnull / ifmissingornull / nullif /
+          // missingif (expression/func_cond_unknown.go): fname
 };
 
 struct Expr {
@@ -42,7 +45,9 @@ struct Expr {
     std::string text;        // exact stringer text, e.g. (`default`.`price`)
     // Func
     std::string fname;       // round | trunc | abs | ceil | floor | sign | sqrt | greatest | least | lower | upper | trim | ltrim |
-                             // rtrim | contains | position[0|1] | pos[0|1]
+                             // rtrim | contains | position[0|1] | pos[0|1] | ifmissing | ifnull | ifmissingornull | nullif | missingif
+    // Case
+    bool case_simple = false, case_else = false;
     // Coll: `text` is the whole term as the stringer wrote it.  The SATISFIES tree is kept apart from ch: its paths name
     // the bound variable, not the row, so collect_paths must not meet them.
     uint32_t coll_mode = 0;  // COLL_ANY | COLL_EVERY | COLL_ANY_EVERY (n1k_coll.h)

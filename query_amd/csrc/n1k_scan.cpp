@@ -19,13 +19,15 @@ bool build_fast_args(n1k_handle* h, uint32_t max_slots, FastArgs& F, bool fuse, 
     const uint32_t ni = (uint32_t)h->plan.paths.size(), nd = (uint32_t)h->derived.size();
     if (fuse) {
         if (nd == 0 || nd > (uint32_t)kFastDerived || ni == 0 || ni > (uint32_t)kFastCols) return false;
-        for (uint32_t d = 0; d < nd; d++)
+        for (uint32_t d = 0; d < nd; d++) {
+            // (collation needs the string ranks, a conditional node its program and cond_kernel: materialised derived columns)
+            if (h->derived[d].op >= AR_GREATEST) return false;
             for (uint32_t k = 0; k < h->derived[d].nops; k++) {
                 const Operand& o = h->derived[d].ops[k];
-                if (h->derived[d].op >= AR_GREATEST) return false;  // (collation needs the string ranks: derived columns)
                 if (!o.is_const && o.col >= ni + d) return false;
                 if (o.is_const) F.dconst[d][k] = o.cpayload;
             }
+        }
         F.nderived = nd;
     }
     if (h->opt.fast == 0 || P.want_rep_row || P.ncols == 0 || (!fuse && P.ncols > (uint32_t)kFastCols)) return false;
@@ -489,6 +491,12 @@ n1k_status bind_columns(n1k_handle* h, const n1k_batch* b, bool defer) {
     for (uint32_t a = 0; a < P.naggs; a++) resolve(P.aggs[a].src);
     for (auto& d : h->derived)
         for (uint32_t k = 0; k < d.nops; k++) resolve(d.ops[k]);
+    // (a THEN constant equal to a string the dictionary holds gets that string's code: the two are one group key)
+    for (auto& n : h->cond_nodes) {
+        for (uint32_t t = 0; t < n.nterms; t++) { resolve(n.terms[t].a); resolve(n.terms[t].b); resolve(n.terms[t].c); }
+        for (uint32_t a = 0; a < n.narms; a++) resolve(n.arms[a].then);
+        resolve(n.els);
+    }
     const uint32_t ni = (uint32_t)h->plan.paths.size();
     for (uint32_t c = 0; c < ni; c++) {
         P.cols[c].kind = b->cols[c].kind == N1K_COL_DICT32 ? COLK_DICT32 : COLK_TAGGED64;
@@ -519,17 +527,23 @@ n1k_status bind_columns(n1k_handle* h, const n1k_batch* b, bool defer) {
     return defer ? N1K_OK : materialize_derived(h, b);
 }
 
-// one element-wise arith_kernel launch per arithmetic node: the node's values as a TAGGED64 column in HBM
+// one element-wise launch per node — arith_kernel, or cond_kernel for a conditional node: the node's values as a TAGGED64
+// column in HBM
 n1k_status materialize_derived(n1k_handle* h, const n1k_batch* b) {
     Program& P = h->prog;
     if (h->derived_ready) return N1K_OK;
     const uint32_t ni = (uint32_t)h->plan.paths.size();
     for (const auto& d : h->derived)
-        if (d.op >= AR_GREATEST) {  // GREATEST / LEAST collate strings by rank: the table must cover this batch's dictionary
+        if (d.op >= AR_GREATEST) {  // GREATEST / LEAST, and a WHEN that orders strings, collate them by rank: the table must cover this batch's dictionary
             n1k_status rst = ensure_rank(h);
             if (rst != N1K_OK) return rst;
             break;
         }
+    if (!h->cond_nodes.empty() && !h->cond_uploaded) {  // once per plan: bind_columns has given the string constants their codes
+        HIP_TRY(h, h->d_cond.ensure(h->cond_nodes.size()));
+        HIP_TRY(h, hipMemcpy(h->d_cond.p, h->cond_nodes.data(), h->cond_nodes.size() * sizeof(CondNode), hipMemcpyHostToDevice));
+        h->cond_uploaded = true;
+    }
     h->dv_tags.resize(h->derived.size());
     h->dv_payload.resize(h->derived.size());
     for (size_t i = 0; i < h->derived.size(); i++) {
@@ -537,6 +551,29 @@ n1k_status materialize_derived(n1k_handle* h, const n1k_batch* b) {
         if (h->dv_tags[i].n < b->nrows) HIP_TRY(h, hipStreamSynchronize(h->stream));
         HIP_TRY(h, h->dv_tags[i].ensure(std::max<uint64_t>(b->nrows, 1)));
         HIP_TRY(h, h->dv_payload[i].ensure(std::max<uint64_t>(b->nrows, 1)));
+        if (h->derived[i].op == AR_COND) {
+            // (the program by value, as the scan kernels take it: its columns, earlier nodes' among them, the ranks, the codes of
+            //  the empty string / array / object)
+            CondArgs C{};
+            C.node = h->d_cond.p + h->derived[i].node;
+            C.nrows = b->nrows;
+            C.nrows_dev = h->push_nrows_dev;
+            if (h->push_nseg > 1) {
+                C.seg_counts = h->push_seg_counts;
+                C.seg_rows = h->push_seg_rows;
+                C.nseg = h->push_nseg;
+            }
+            C.out_tags = h->dv_tags[i].p;
+            C.out_payload = h->dv_payload[i].p;
+            C.err_flags = h->groups.errp;
+            HIP_TRY(h, launch_cond(P, C, h->stream));
+            DevCol& d = P.cols[ni + i];
+            d.kind = COLK_TAGGED64;
+            d.tags = C.out_tags;
+            d.payload = C.out_payload;
+            d.codes = nullptr;
+            continue;
+        }
         ArithArgs A{};
         A.op = h->derived[i].op;
         A.nops = h->derived[i].nops;

@@ -83,7 +83,10 @@ n1k_status build_projection(n1k_handle* h) {
         h->tail.project_ops.push_back(o);
     }
     for (const auto& d : f->derived)
-        if (d.op >= AR_GREATEST) {  // (the inner operator sees this handle's dictionary codes, not its own: no string ranks there)
+        if (d.op == AR_COND) {  // (idem: its string constants would get the inner handle's codes)
+            g_create_error = "CASE or a conditional function as a projection term over the groups does not run on the device";
+            return N1K_UNSUPPORTED;
+        } else if (d.op >= AR_GREATEST) {  // (the inner operator sees this handle's dictionary codes, not its own: no string ranks there)
             g_create_error = "GREATEST / LEAST as a projection term over the groups does not run on the device";
             return N1K_UNSUPPORTED;
         }

@@ -462,7 +462,8 @@ constexpr uint32_t kRowSubs = 8;  // sub-regions (segments) of a packed row regi
 enum : uint32_t { AR_ADD = 0, AR_MULT, AR_SUB, AR_DIV, AR_MOD, AR_NEG, AR_IDIV, AR_IMOD,
                   // expression/func_num.go: ROUND / TRUNC (value [, digits]), ABS, CEIL, FLOOR, SIGN, SQRT
                   AR_ROUND, AR_TRUNC, AR_ABS, AR_CEIL, AR_FLOOR, AR_SIGN, AR_SQRT,
-                  AR_GREATEST, AR_LEAST };  // expression/func_comp.go: by value.Collate (derived columns only: they need the string ranks)
+                  AR_GREATEST, AR_LEAST,  // expression/func_comp.go: by value.Collate (derived columns only: they need the string ranks)
+                  AR_COND };  // CASE / a conditional function (n1k_cond.h): cond_kernel, not arith_kernel (derived columns only)
 struct ArithArgs {
     uint32_t op, nops;
     Operand ops[4];

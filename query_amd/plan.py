@@ -35,6 +35,34 @@ def in_list(path: str, values: Sequence) -> str:
     return "(%s in [%s])" % (path, ", ".join(const(v) for v in values))
 
 
+def case_when(arms: Sequence[tuple], else_: Optional[str] = None) -> str:
+    """Stringer text of a searched CASE (stringer.go VisitSearchedCase): arms = [(condition text, value text)];
+    case_when([("(50 < (`d`.`price`))", "(`d`.`price`)")], "0") -> case when (50 < (`d`.`price`)) then (`d`.`price`) else 0 end.
+    The operands are expression text already (field_path, a JSON constant, arithmetic in parentheses, another case_when)."""
+    if not arms:
+        raise ValueError("a CASE needs at least one WHEN arm")
+    s = "case" + "".join(" when %s then %s" % (w, t) for w, t in arms)
+    return s + (" else %s" % else_ if else_ is not None else "") + " end"
+
+
+def case_of(search: str, arms: Sequence[tuple], else_: Optional[str] = None) -> str:
+    """Stringer text of a simple CASE (VisitSimpleCase): case <search> when <value> then <value> ... [else <value>] end."""
+    if not arms:
+        raise ValueError("a CASE needs at least one WHEN arm")
+    s = "case %s" % search + "".join(" when %s then %s" % (w, t) for w, t in arms)
+    return s + (" else %s" % else_ if else_ is not None else "") + " end"
+
+
+COND_FUNCTIONS = ("ifmissing", "ifnull", "ifmissingornull", "nullif", "missingif")  # expression/func_registry.go:321-325
+
+
+def cond_fn(name: str, *args: str) -> str:
+    """Stringer text of a conditional function (VisitFunction): cond_fn("ifmissing", "(`d`.`x`)", "0") -> ifmissing((`d`.`x`), 0)."""
+    if name.lower() not in COND_FUNCTIONS:
+        raise ValueError("cond_fn takes one of %s, not %r" % (", ".join(COND_FUNCTIONS), name))
+    return "%s(%s)" % (name.lower(), ", ".join(args))
+
+
 @dataclass
 class Filter:
     condition: str
