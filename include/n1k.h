@@ -226,7 +226,8 @@ typedef struct n1k_handle n1k_handle;
  *        {"#operator":"FinalProject"}]}                                                            nests them, plan/project.go:73-110)
  *     IntermediateGroup / FinalGroup must repeat the InitialGroup's lists (plan/group.go:106-273) and are subsumed;
  *     the result terms of an InitialProject are expressions over group keys and aggregates (constants, arithmetic,
- *     round / trunc / abs / ceil / floor / sign / sqrt): n1k_result.proj then holds their values per group, and a sort
+ *     round / trunc / abs / ceil / floor / sign / sqrt, the library functions and ifinf / ifnan / ifnanorinf listed below):
+ *     n1k_result.proj then holds their values per group, and a sort
  *     term may name a term's alias (`alias`) or repeat its expression; star / raw / distinct projections are N1K_UNSUPPORTED;
  *     the HAVING condition and the sort terms may name only group keys and aggregates of the plan (by their text);
  *     offset / limit are integer constants.  n1k_finish then returns the groups filtered, ordered and cut.
@@ -245,6 +246,17 @@ typedef struct n1k_handle n1k_handle;
  *   projection over the groups, as a sort term or as a DISTINCT term of a Filter-only plan; more than 16 columns counting the
  *   plan's leaf paths, its arithmetic nodes and these.  A WHEN that orders two arrays / objects is N1K_UNSUPPORTED_DATA at run
  *   time, for the rows that reach that arm only.  Text that is no CASE (a missing THEN or END) is N1K_INVALID.
+ * Numeric library functions (expression/func_num.go), values wherever round(...) is one — HAVING and projections over the groups
+ * included:
+ *     acos asin atan cos sin tan exp ln log degrees radians (one argument; ln is math.Log, log is math.Log10)
+ *     atan2(y, x)  power(x, y)
+ *     pi()  e()  nan()  posinf()  neginf()      constants at n1k_create: FLOAT payloads, no node and no column
+ *     ifinf(a, b, …)  ifnan(a, b, …)  ifnanorinf(a, b, …)  with 2 to 4 arguments, in argument order      (func_cond_num.go:64-79)
+ *     nanif(a, b)  posinfif(a, b)  neginfif(a, b)   like nullif, giving FLOAT NaN / +Inf / -Inf; refused where nullif is
+ *   A MISSING argument gives MISSING, any other non-number NULL; the arguments go through float64 and the result through
+ *   value.NewValue (power(12, 2) is INT 144).  Out-of-domain results are values: acos(3) and ln(-1) are FLOAT NaN, ln(0) is
+ *   -Inf, exp(1000) is +Inf.  The eleven library routines are the device's, within a few ulp of Go's and not bit-identical.
+ *   random is N1K_UNSUPPORTED, as are more than 4 arguments of ifinf / ifnan / ifnanorinf; a wrong argument count is N1K_INVALID.
  * exactly as plan.(*Filter).MarshalJSON (plan/filter.go:46-53),
  * plan.(*InitialGroup).MarshalJSON (plan/group.go:54-70), plan/sequence.go:48-57 and
  * plan/parallel.go:54-67 emit them; expressions are expression.Stringer text.

@@ -11,6 +11,7 @@
 //   COND_IFMISSINGORNULL  the first operand above NULL                    (:209-217);  none in all three: NULL
 //   COND_NULLIF           eq = a.Equals(b): MISSING / NULL -> eq, TRUE -> NULL, else a      (:278-290)
 //   COND_MISSINGIF        ... TRUE -> MISSING                                               (:347-359)
+//   COND_NANIF / COND_POSINFIF / COND_NEGINFIF   ... TRUE -> FLOAT NaN / +Inf / -Inf   (func_cond_num.go:293-305 and siblings)
 //
 // The WHEN conditions are compiled by compile_cond, the Filter's own compiler, into the node's terms and postfix logic,
 // and evaluated by eval_term and the logic_* helpers, the Filter's own evaluator: a WHEN answers what the Filter answers.
@@ -24,7 +25,9 @@ constexpr int kCondMaxArms = 8;     // WHEN arms of a CASE (the functions take 2
 constexpr int kCondMaxTerms = 16;   // predicate terms of all WHEN conditions of one node
 constexpr int kCondMaxLogic = 32;   // postfix logic ops of all WHEN conditions of one node
 
-enum : uint32_t { COND_CASE = 0, COND_IFMISSING, COND_IFNULL, COND_IFMISSINGORNULL, COND_NULLIF, COND_MISSINGIF };
+enum : uint32_t { COND_CASE = 0, COND_IFMISSING, COND_IFNULL, COND_IFMISSINGORNULL, COND_NULLIF, COND_MISSINGIF,
+                  COND_NANIF, COND_POSINFIF, COND_NEGINFIF };
+constexpr bool cond_is_eq_mode(uint32_t m) { return m == COND_NULLIF || m == COND_MISSINGIF || m == COND_NANIF || m == COND_POSINFIF || m == COND_NEGINFIF; }
 
 struct CondArm {
     uint32_t logic_begin, logic_end;  // COND_CASE / NULLIF / MISSINGIF: the arm's condition, logic[logic_begin .. logic_end)

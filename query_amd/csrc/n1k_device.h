@@ -347,6 +347,69 @@ N1K_DEV void arith_apply(uint32_t op, uint32_t nops, const uint32_t (&tg)[4], co
     rp_out = rp;
 }
 
+// The library functions (expression/func_num.go: Acos ... Tan, Exp, Ln = math.Log, Log = math.Log10, Atan2, Power,
+// Degrees, Radians) and IFINF / IFNAN / IFNANORINF (func_cond_num.go:64-79 and siblings), the function chosen at COMPILE
+// time: a kernel that instantiates math_apply<OP> carries that one routine.  They are not part of arith_apply's run-time
+// switch, which every materialised arithmetic node of every plan runs through.  Out-of-domain results are values (NaN,
+// +-Inf), as in Go; Go's documented special cases of Pow / Atan2 / Log are those of C99 Annex F, which the device library
+// follows (tests/mathfn_util.py holds the table).
+template <uint32_t OP>
+N1K_DEV double math_fn(double a, double b) {
+    constexpr double pi = 3.141592653589793;  // math.Pi as a float64
+    if constexpr (OP == AR_ACOS) return acos(a);
+    else if constexpr (OP == AR_ASIN) return asin(a);
+    else if constexpr (OP == AR_ATAN) return atan(a);
+    else if constexpr (OP == AR_COS) return cos(a);
+    else if constexpr (OP == AR_SIN) return sin(a);
+    else if constexpr (OP == AR_TAN) return tan(a);
+    else if constexpr (OP == AR_EXP) return exp(a);
+    else if constexpr (OP == AR_LN) return log(a);
+    else if constexpr (OP == AR_LOG) return log10(a);
+    else if constexpr (OP == AR_DEGREES) return a * 180.0 / pi;  // (func_num.go:427-434: in this order, two IEEE operations)
+    else if constexpr (OP == AR_RADIANS) return a * pi / 180.0;  // (:1145-1153)
+    else if constexpr (OP == AR_ATAN2) return atan2(a, b);
+    else return pow(a, b);
+}
+// MISSING before NULL over ALL arguments (Atan2.Apply :303-312, Power.Apply :1088-1097), the arguments through float64
+// (intValue.Actual()), the result through value.NewValue.  IF*: the arguments in order — MISSING gives MISSING, a non-number
+// NULL, the first number that is not +-Inf / NaN / either is the result (NewValue of it); none: NULL.
+template <uint32_t OP>
+N1K_DEV void math_apply(uint32_t nops, const uint32_t (&tg)[4], const uint64_t (&pv)[4], uint32_t& rt_out, uint64_t& rp_out) {
+    static_assert(ar_is_mathfn(OP), "math_apply: not a library function");
+    auto is_num = [](uint32_t t) { return t == T_INT || t == T_FLOAT; };
+    uint32_t rt = T_NULL;
+    uint64_t rp = 0;
+    if constexpr (ar_is_ifnum(OP)) {
+        bool open = true;
+#pragma unroll
+        for (uint32_t k = 0; k < 4; k++) {
+            if (k >= nops || !open) continue;
+            if (tg[k] == T_MISSING) { rt = T_MISSING; open = false; }
+            else if (!is_num(tg[k])) open = false;  // NULL
+            else {
+                const double f = num_actual(tg[k], pv[k]);
+                const bool nan = f != f, inf = !nan && (f - f) != 0.0;
+                if (!(OP == AR_IFINF ? inf : (OP == AR_IFNAN ? nan : (nan || inf)))) {
+                    const Num n = num_new_value(f);
+                    rt = n.tag;
+                    rp = n.p;
+                    open = false;
+                }
+            }
+        }
+    } else {
+        constexpr bool two = ar_is_mathfn2(OP);
+        if (tg[0] == T_MISSING || (two && tg[1] == T_MISSING)) rt = T_MISSING;
+        else if (is_num(tg[0]) && (!two || is_num(tg[1]))) {
+            const Num n = num_new_value(math_fn<OP>(num_actual(tg[0], pv[0]), two ? num_actual(tg[1], pv[1]) : 0.0));
+            rt = n.tag;
+            rp = n.p;
+        }
+    }
+    rt_out = rt;
+    rp_out = rp;
+}
+
 N1K_DEV uint64_t mix64(uint64_t x) {
     x ^= x >> 33;
     x *= 0xff51afd7ed558ccdull;

@@ -41,7 +41,19 @@ uint32_t lookup_code(const n1k_handle* h, const char* s) {
 }
 
 static bool cond_operand(n1k_handle* h, const Expr* e, Operand& o, PlanError& err);
-static bool cond_fn_name(const std::string& f) { return f == "ifmissing" || f == "ifnull" || f == "ifmissingornull" || f == "nullif" || f == "missingif"; }
+static bool cond_fn_name(const std::string& f) {
+    return f == "ifmissing" || f == "ifnull" || f == "ifmissingornull" || f == "nullif" || f == "missingif" || f == "nanif" || f == "posinfif" || f == "neginfif";
+}
+// The library functions of expression/func_num.go and IFINF / IFNAN / IFNANORINF (func_cond_num.go): op of a name, or AR_OP_COUNT
+static uint32_t mathfn_op(const std::string& f) {
+    static const std::pair<const char*, uint32_t> ops[] = {
+        {"acos", AR_ACOS}, {"asin", AR_ASIN}, {"atan", AR_ATAN}, {"cos", AR_COS}, {"sin", AR_SIN}, {"tan", AR_TAN}, {"exp", AR_EXP}, {"ln", AR_LN},
+        {"log", AR_LOG}, {"degrees", AR_DEGREES}, {"radians", AR_RADIANS}, {"atan2", AR_ATAN2}, {"power", AR_POWER}, {"ifinf", AR_IFINF},
+        {"ifnan", AR_IFNAN}, {"ifnanorinf", AR_IFNANORINF}};
+    for (auto& o : ops)
+        if (f == o.first) return o.second;
+    return AR_OP_COUNT;
+}
 
 bool to_operand(n1k_handle* h, const Expr* e, Operand& o, PlanError& err) {
     memset(&o, 0, sizeof o);
@@ -86,10 +98,22 @@ bool to_operand(n1k_handle* h, const Expr* e, Operand& o, PlanError& err) {
             return false;
         }
         op = f == "round" ? AR_ROUND : f == "trunc" ? AR_TRUNC : f == "abs" ? AR_ABS : f == "ceil" ? AR_CEIL
-             : f == "floor" ? AR_FLOOR : f == "sign" ? AR_SIGN : f == "sqrt" ? AR_SQRT : f == "greatest" ? AR_GREATEST : AR_LEAST;
+             : f == "floor" ? AR_FLOOR : f == "sign" ? AR_SIGN : f == "sqrt" ? AR_SQRT : f == "greatest" ? AR_GREATEST
+             : f == "least" ? AR_LEAST : mathfn_op(f);
+        if (op == AR_OP_COUNT) {
+            err.unsupported = true;
+            err.msg = "function '" + f + "' is outside the device subset";
+            return false;
+        }
+        if (ar_is_ifnum(op) && e->ch.size() > 4) {
+            // (chaining is not exact: the inner node's NULL for "none" would stop the outer one)
+            err.unsupported = true;
+            err.msg = f + " with " + std::to_string(e->ch.size()) + " arguments: the device takes 2 to 4";
+            return false;
+        }
         n1k_handle::Derived d{};
         d.op = op;
-        if (op >= AR_GREATEST) h->need_rank = true;  // (strings collate by their bytewise rank)
+        if (ar_is_collating(op)) h->need_rank = true;  // (strings collate by their bytewise rank)
         for (auto& c : e->ch) {
             Operand x;
             if (!to_operand(h, c.get(), x, err)) return false;
@@ -342,8 +366,9 @@ static bool cond_operand(n1k_handle* h, const Expr* e, Operand& o, PlanError& er
     } else {
         const std::string& f = e->fname;
         n.mode = f == "ifmissing" ? COND_IFMISSING : f == "ifnull" ? COND_IFNULL : f == "ifmissingornull" ? COND_IFMISSINGORNULL
-                 : f == "nullif" ? COND_NULLIF : COND_MISSINGIF;
-        if (n.mode == COND_NULLIF || n.mode == COND_MISSINGIF) {
+                 : f == "nullif" ? COND_NULLIF : f == "missingif" ? COND_MISSINGIF : f == "nanif" ? COND_NANIF
+                 : f == "posinfif" ? COND_POSINFIF : COND_NEGINFIF;
+        if (cond_is_eq_mode(n.mode)) {
             CondArm& arm = n.arms[n.narms++];
             Term& t = n.terms[n.nterms];
             t.op = TERM_EQ;

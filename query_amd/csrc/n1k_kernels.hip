@@ -306,13 +306,19 @@ __global__ __launch_bounds__(256) void cond_kernel(const Program P, const CondAr
     uint64_t rp = 0;
     uint32_t t[1];
     uint64_t p[1];
-    if (N.mode == COND_NULLIF || N.mode == COND_MISSINGIF) {
-        // eq = a.Equals(b): MISSING / NULL -> eq itself, TRUE -> NULL (MISSING), else a (expression/func_cond_unknown.go:278-290, 347-359)
+    if (cond_is_eq_mode(N.mode)) {
+        // eq = a.Equals(b): MISSING / NULL -> eq itself, TRUE -> NULL (MISSING), else a (expression/func_cond_unknown.go:278-290, 347-359);
+        // NANIF / POSINFIF / NEGINFIF: TRUE -> FLOAT NaN / +Inf / -Inf (func_cond_num.go:293-305 and siblings)
         const uint32_t eq = cond_eval_logic(P, N, N.arms[0].logic_begin, N.arms[0].logic_end, row, open, unsupported);
         const bool keep[1] = {in && eq == L_FALSE};
         load_operand<1>(P, N.arms[0].then, row, keep, t, p);
         if (keep[0]) { rt = t[0]; rp = p[0]; }
-        else rt = eq == L_MISSING ? (uint32_t)T_MISSING : (eq == L_NULL ? (uint32_t)T_NULL : (N.mode == COND_NULLIF ? (uint32_t)T_NULL : (uint32_t)T_MISSING));
+        else if (eq == L_MISSING || eq == L_NULL) rt = eq == L_MISSING ? (uint32_t)T_MISSING : (uint32_t)T_NULL;
+        else if (N.mode == COND_NULLIF || N.mode == COND_MISSINGIF) rt = N.mode == COND_NULLIF ? (uint32_t)T_NULL : (uint32_t)T_MISSING;
+        else {
+            rt = T_FLOAT;
+            rp = N.mode == COND_NANIF ? 0x7FF8000000000001ull : (N.mode == COND_POSINFIF ? 0x7FF0000000000000ull : 0xFFF0000000000000ull);
+        }
     } else {
         for (uint32_t a = 0; a < N.narms; a++) {
             if (__ballot(open[0]) == 0) break;

@@ -294,6 +294,25 @@ struct EParser {
         return e;
     }
 
+    // name(arg, arg, ...) as the stringer writes a function (stringer.go VisitFunction), the cursor on the name: an EK::Func
+    // with the arguments in ch — none for name() —, the cursor behind the ')'.  How many a function takes is its caller's rule.
+    std::unique_ptr<Expr> call(const std::string& w) {
+        p += 2;  // name (
+        auto e = mk(EK::Func);
+        e->fname = w;
+        if (cur().kind != TK::RParen)
+            for (;;) {
+                auto a = primary();
+                if (!a) return nullptr;
+                e->ch.push_back(std::move(a));
+                if (cur().kind == TK::Comma) { p++; continue; }
+                break;
+            }
+        if (cur().kind != TK::RParen) return bad("expected ) in " + w);
+        p++;
+        return e;
+    }
+
     std::unique_ptr<Expr> primary() {
         const Tok& t = cur();
         switch (t.kind) {
@@ -362,35 +381,15 @@ struct EParser {
                 }
                 if ((w == "round" || w == "trunc" || w == "abs" || w == "ceil" || w == "floor" || w == "sign" || w == "sqrt") &&
                     lx.toks[p + 1].kind == TK::LParen) {  // expression/func_num.go; stringer: name(arg, arg)
-                    p += 2;
-                    auto e = mk(EK::Func);
-                    e->fname = w;
-                    for (;;) {
-                        auto a = primary();
-                        if (!a) return nullptr;
-                        e->ch.push_back(std::move(a));
-                        if (cur().kind == TK::Comma) { p++; continue; }
-                        break;
-                    }
-                    if (cur().kind != TK::RParen) return bad("expected ) in " + w);
-                    p++;
+                    auto e = call(w);
+                    if (!e) return nullptr;
                     const size_t maxargs = (w == "round" || w == "trunc") ? 2 : 1;
                     if (e->ch.empty() || e->ch.size() > maxargs) return bad(w + " takes 1" + (maxargs == 2 ? " or 2" : "") + " arguments");
                     return e;
                 }
                 if ((w == "greatest" || w == "least") && lx.toks[p + 1].kind == TK::LParen) {  // expression/func_comp.go
-                    p += 2;
-                    auto e = mk(EK::Func);
-                    e->fname = w;
-                    for (;;) {
-                        auto a = primary();
-                        if (!a) return nullptr;
-                        e->ch.push_back(std::move(a));
-                        if (cur().kind == TK::Comma) { p++; continue; }
-                        break;
-                    }
-                    if (cur().kind != TK::RParen) return bad("expected ) in " + w);
-                    p++;
+                    auto e = call(w);
+                    if (!e) return nullptr;
                     if (e->ch.size() < 2) return bad(w + " takes at least 2 arguments");
                     return e;
                 }
@@ -401,41 +400,48 @@ struct EParser {
                 const bool str_binary = w == "contains" || w == "position" || w == "pos" || w == "position0" || w == "pos0" ||
                                         w == "position1" || w == "pos1";
                 if ((str_unary || str_trim || str_binary) && lx.toks[p + 1].kind == TK::LParen) {
-                    p += 2;
-                    auto e = mk(EK::Func);
-                    e->fname = w;
-                    for (;;) {
-                        auto a = primary();
-                        if (!a) return nullptr;
-                        e->ch.push_back(std::move(a));
-                        if (cur().kind == TK::Comma) { p++; continue; }
-                        break;
-                    }
-                    if (cur().kind != TK::RParen) return bad("expected ) in " + w);
-                    p++;
+                    auto e = call(w);
+                    if (!e) return nullptr;
                     const size_t minargs = str_binary ? 2 : 1, maxargs = str_unary ? 1 : 2;
                     if (e->ch.size() < minargs || e->ch.size() > maxargs) return bad(w + " takes " + std::to_string(minargs) + (maxargs > minargs ? " or 2" : "") + " arguments");
                     return e;
                 }
                 // Conditional functions (expression/func_cond_unknown.go; registry names func_registry.go:321-325): a node like
                 // the numeric functions'.  How many operands the device takes is decided where it is compiled (cond_operand).
-                const bool cond_first = w == "ifmissing" || w == "ifnull" || w == "ifmissingornull", cond_eq = w == "nullif" || w == "missingif";
+                const bool cond_first = w == "ifmissing" || w == "ifnull" || w == "ifmissingornull", cond_eq = w == "nullif" || w == "missingif" || w == "nanif" || w == "posinfif" || w == "neginfif";  // (the last three: func_cond_num.go:293-305)
                 if ((cond_first || cond_eq) && lx.toks[p + 1].kind == TK::LParen) {
-                    p += 2;
-                    auto e = mk(EK::Func);
-                    e->fname = w;
-                    for (;;) {
-                        auto a = primary();
-                        if (!a) return nullptr;
-                        e->ch.push_back(std::move(a));
-                        if (cur().kind == TK::Comma) { p++; continue; }
-                        break;
-                    }
-                    if (cur().kind != TK::RParen) return bad("expected ) in " + w);
-                    p++;
+                    auto e = call(w);
+                    if (!e) return nullptr;
                     if (e->ch.size() < 2 || (cond_eq && e->ch.size() != 2)) return bad(w + (cond_eq ? " takes 2 arguments" : " takes at least 2 arguments"));
                     return e;
                 }
+                // The library functions and constants of expression/func_num.go, and the numeric conditionals of
+                // func_cond_num.go (registry names func_registry.go:191-219, 334-339).  PI / E / NAN / POSINF / NEGINF are
+                // constants here: no node and no column.
+                const bool num_nullary = w == "pi" || w == "e" || w == "nan" || w == "posinf" || w == "neginf";
+                if (num_nullary && lx.toks[p + 1].kind == TK::LParen) {
+                    if (lx.toks[p + 2].kind != TK::RParen) return bad(w + " takes no arguments");
+                    p += 3;
+                    auto e = mk(EK::Const);
+                    e->ctag = T_FLOAT;
+                    const uint64_t nan_bits = 0x7FF8000000000001ull;  // math.NaN()
+                    const double v = w == "pi" ? 3.14159265358979323846 : w == "e" ? 2.71828182845904523536 : w == "posinf" ? HUGE_VAL : -HUGE_VAL;
+                    if (w == "nan") e->cpayload = nan_bits;
+                    else memcpy(&e->cpayload, &v, 8);
+                    return e;
+                }
+                const bool num_unary = w == "acos" || w == "asin" || w == "atan" || w == "cos" || w == "sin" || w == "tan" || w == "exp" ||
+                                       w == "ln" || w == "log" || w == "degrees" || w == "radians";
+                const bool num_binary = w == "atan2" || w == "power", num_if = w == "ifinf" || w == "ifnan" || w == "ifnanorinf";
+                if ((num_unary || num_binary || num_if) && lx.toks[p + 1].kind == TK::LParen) {
+                    auto e = call(w);
+                    if (!e) return nullptr;
+                    if (num_if ? e->ch.size() < 2 : e->ch.size() != (num_unary ? 1u : 2u))
+                        return bad(w + (num_if ? " takes at least 2 arguments" : num_unary ? " takes 1 argument" : " takes 2 arguments"));
+                    return e;
+                }
+                // (with a seed it is Go's generator, without one it is no function of the row: func_num.go Random)
+                if (w == "random" && lx.toks[p + 1].kind == TK::LParen) return unsupported("function 'random'");
                 if (w == "case") return case_expr();
                 if ((w == "any" || w == "every") && lx.toks[p + 1].kind != TK::LParen) return collection();
                 return unsupported("function or keyword '" + w + "'");

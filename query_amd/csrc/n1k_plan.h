@@ -31,7 +31,8 @@ enum class EK {
            // [else], case_simple / case_else say which of the optional ones are there
     Func  // numeric functions of one or two arguments (expression/func_num.go) and the string functions a term may hold
           // (expression/func_str.go; n1k_strfn.h), and the conditional functions ifmissing / ifnull / ifmissingornull / nullif /
-          // missingif (expression/func_cond_unknown.go): fname
+          // missingif (expression/func_cond_unknown.go), the library functions acos ... power (func_num.go; pi() / e() / nan() /
+          // posinf() / neginf() parse to Const) and ifinf / ifnan / ifnanorinf / nanif / posinfif / neginfif (func_cond_num.go): fname
 };
 
 struct Expr {
@@ -46,6 +47,8 @@ struct Expr {
     // Func
     std::string fname;       // round | trunc | abs | ceil | floor | sign | sqrt | greatest | least | lower | upper | trim | ltrim |
                              // rtrim | contains | position[0|1] | pos[0|1] | ifmissing | ifnull | ifmissingornull | nullif | missingif
+                             // | acos | asin | atan | cos | sin | tan | exp | ln | log | degrees | radians | atan2 | power | ifinf | ifnan |
+                             // ifnanorinf | nanif | posinfif | neginfif
     // Case
     bool case_simple = false, case_else = false;
     // Coll: `text` is the whole term as the stringer wrote it.  The SATISFIES tree is kept apart from ch: its paths name

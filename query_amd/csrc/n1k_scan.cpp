@@ -21,7 +21,7 @@ bool build_fast_args(n1k_handle* h, uint32_t max_slots, FastArgs& F, bool fuse, 
         if (nd == 0 || nd > (uint32_t)kFastDerived || ni == 0 || ni > (uint32_t)kFastCols) return false;
         for (uint32_t d = 0; d < nd; d++) {
             // (collation needs the string ranks, a conditional node its program and cond_kernel: materialised derived columns)
-            if (h->derived[d].op >= AR_GREATEST) return false;
+            if (!ar_fuses(h->derived[d].op)) return false;
             for (uint32_t k = 0; k < h->derived[d].nops; k++) {
                 const Operand& o = h->derived[d].ops[k];
                 if (!o.is_const && o.col >= ni + d) return false;
@@ -534,7 +534,7 @@ n1k_status materialize_derived(n1k_handle* h, const n1k_batch* b) {
     if (h->derived_ready) return N1K_OK;
     const uint32_t ni = (uint32_t)h->plan.paths.size();
     for (const auto& d : h->derived)
-        if (d.op >= AR_GREATEST) {  // GREATEST / LEAST, and a WHEN that orders strings, collate them by rank: the table must cover this batch's dictionary
+        if (ar_needs_rank(d.op)) {  // GREATEST / LEAST, and a WHEN that orders strings, collate them by rank: the table must cover this batch's dictionary
             n1k_status rst = ensure_rank(h);
             if (rst != N1K_OK) return rst;
             break;
@@ -584,7 +584,8 @@ n1k_status materialize_derived(n1k_handle* h, const n1k_batch* b) {
         A.out_payload = h->dv_payload[i].p;
         A.str_rank = h->d_rank.p;
         A.err_flags = h->groups.errp;
-        HIP_TRY(h, launch_arith(A, h->stream));
+        // (a library function has a kernel of its own, which carries that routine alone)
+        HIP_TRY(h, ar_is_mathfn(A.op) ? launch_mathfn(A, h->stream) : launch_arith(A, h->stream));
         DevCol& d = P.cols[ni + i];
         d.kind = COLK_TAGGED64;
         d.tags = A.out_tags;

@@ -370,6 +370,19 @@ N1K_DEV void spec_tile_arrived(uint32_t (&tt)[R][kFastCols], uint64_t (&pv)[R][W
     }
 }
 
+// Fused node D of the shape: arith_apply with its op a constant, or — a library function — math_apply<op>, so that the
+// shape carries the routines its own nodes name and no other (the loop below is unrolled: d is a constant there).
+template <class Spec, int D>
+N1K_DEV void spec_derived_apply(const uint32_t (&ot)[4], const uint64_t (&op)[4], uint32_t& rt, uint64_t& rp) {
+    if constexpr (D < Spec::nderived) {
+        if constexpr (ar_is_mathfn(Spec::derived[D].op)) math_apply<Spec::derived[D].op>(Spec::derived[D].nops, ot, op, rt, rp);
+        else arith_apply(Spec::derived[D].op, Spec::derived[D].nops, ot, op, rt, rp);
+    } else {
+        rt = T_MISSING;
+        rp = 0;
+    }
+}
+
 // Decode: the rows' tags from what spec_issue_tile loaded, and the fused arithmetic nodes (expression/arith_*.go,
 // func_num.go): column slot ncols + d from the slots before it, in registers — no derived column in HBM (the element-wise
 // arith_kernel writes 9 B per row and node and the scan reads them back).
@@ -414,7 +427,10 @@ N1K_DEV void spec_decode_tile(const FastArgs& F, const uint32_t (&tt)[R][kFastCo
                 }
                 uint32_t rt;
                 uint64_t rp;
-                arith_apply(Spec::derived[d].op, Spec::derived[d].nops, ot, op, rt, rp);
+                static_assert(kFastDerived == 3, "spec_derived_apply is instantiated per node index");
+                if (d == 0) spec_derived_apply<Spec, 0>(ot, op, rt, rp);
+                else if (d == 1) spec_derived_apply<Spec, 1>(ot, op, rt, rp);
+                else spec_derived_apply<Spec, 2>(ot, op, rt, rp);
                 tg[j][h][Spec::ncols + d] = rt;
                 pv[j][h][Spec::ncols + d] = rp;
             }

@@ -86,7 +86,7 @@ n1k_status build_projection(n1k_handle* h) {
         if (d.op == AR_COND) {  // (idem: its string constants would get the inner handle's codes)
             g_create_error = "CASE or a conditional function as a projection term over the groups does not run on the device";
             return N1K_UNSUPPORTED;
-        } else if (d.op >= AR_GREATEST) {  // (the inner operator sees this handle's dictionary codes, not its own: no string ranks there)
+        } else if (ar_is_collating(d.op)) {  // (the inner operator sees this handle's dictionary codes, not its own: no string ranks there)
             g_create_error = "GREATEST / LEAST as a projection term over the groups does not run on the device";
             return N1K_UNSUPPORTED;
         }

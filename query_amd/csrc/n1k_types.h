@@ -463,7 +463,24 @@ enum : uint32_t { AR_ADD = 0, AR_MULT, AR_SUB, AR_DIV, AR_MOD, AR_NEG, AR_IDIV, 
                   // expression/func_num.go: ROUND / TRUNC (value [, digits]), ABS, CEIL, FLOOR, SIGN, SQRT
                   AR_ROUND, AR_TRUNC, AR_ABS, AR_CEIL, AR_FLOOR, AR_SIGN, AR_SQRT,
                   AR_GREATEST, AR_LEAST,  // expression/func_comp.go: by value.Collate (derived columns only: they need the string ranks)
-                  AR_COND };  // CASE / a conditional function (n1k_cond.h): cond_kernel, not arith_kernel (derived columns only)
+                  AR_COND,  // CASE / a conditional function (n1k_cond.h): cond_kernel, not arith_kernel (derived columns only)
+                  // expression/func_num.go, the library functions: math_apply<OP> (n1k_device.h), one mathfn_kernel<OP> each —
+                  // never arith_apply's run-time switch.  Unary first, then ATAN2(y, x) and POWER(x, y).
+                  AR_ACOS, AR_ASIN, AR_ATAN, AR_COS, AR_SIN, AR_TAN, AR_EXP, AR_LN, AR_LOG, AR_DEGREES, AR_RADIANS, AR_ATAN2, AR_POWER,
+                  // expression/func_cond_num.go: IFINF / IFNAN / IFNANORINF of 2 to 4 numbers, eager
+                  AR_IFINF, AR_IFNAN, AR_IFNANORINF,
+                  AR_OP_COUNT };
+// What an op needs, by name and not by its place in the enum.
+constexpr bool ar_is_mathfn(uint32_t op) {  // math_apply<OP> / mathfn_kernel<OP>
+    return op == AR_ACOS || op == AR_ASIN || op == AR_ATAN || op == AR_COS || op == AR_SIN || op == AR_TAN || op == AR_EXP || op == AR_LN ||
+           op == AR_LOG || op == AR_DEGREES || op == AR_RADIANS || op == AR_ATAN2 || op == AR_POWER || op == AR_IFINF || op == AR_IFNAN ||
+           op == AR_IFNANORINF;
+}
+constexpr bool ar_is_mathfn2(uint32_t op) { return op == AR_ATAN2 || op == AR_POWER; }
+constexpr bool ar_is_ifnum(uint32_t op) { return op == AR_IFINF || op == AR_IFNAN || op == AR_IFNANORINF; }
+constexpr bool ar_is_collating(uint32_t op) { return op == AR_GREATEST || op == AR_LEAST; }       // by value.Collate: the string ranks
+constexpr bool ar_needs_rank(uint32_t op) { return ar_is_collating(op) || op == AR_COND; }        // (a WHEN may order strings)
+constexpr bool ar_fuses(uint32_t op) { return !ar_needs_rank(op) && op < AR_OP_COUNT; }           // evaluable in the scan's registers
 struct ArithArgs {
     uint32_t op, nops;
     Operand ops[4];

@@ -53,7 +53,26 @@ def case_of(search: str, arms: Sequence[tuple], else_: Optional[str] = None) -> 
     return s + (" else %s" % else_ if else_ is not None else "") + " end"
 
 
-COND_FUNCTIONS = ("ifmissing", "ifnull", "ifmissingornull", "nullif", "missingif")  # expression/func_registry.go:321-325
+COND_FUNCTIONS = ("ifmissing", "ifnull", "ifmissingornull", "nullif", "missingif",  # expression/func_registry.go:321-325
+                  "nanif", "posinfif", "neginfif")  # :337-339 (func_cond_num.go): Equals, like nullif, giving NaN / +Inf / -Inf
+
+# expression/func_registry.go:191-219, 334-336 -> (least, most) arguments.  Values, usable wherever round(...) is.
+NUM_FUNCTIONS = {"acos": (1, 1), "asin": (1, 1), "atan": (1, 1), "cos": (1, 1), "sin": (1, 1), "tan": (1, 1), "exp": (1, 1), "ln": (1, 1),
+                 "log": (1, 1), "degrees": (1, 1), "radians": (1, 1), "atan2": (2, 2), "power": (2, 2),
+                 "pi": (0, 0), "e": (0, 0), "nan": (0, 0), "posinf": (0, 0), "neginf": (0, 0),
+                 "ifinf": (2, 4), "ifnan": (2, 4), "ifnanorinf": (2, 4)}
+
+
+def num_fn(name: str, *args: str) -> str:
+    """Stringer text of a numeric function (VisitFunction): num_fn("power", "(`d`.`x`)", "2") -> power((`d`.`x`), 2);
+    num_fn("pi") -> pi().  ln is the natural logarithm and log the decimal one; ifinf / ifnan / ifnanorinf take 2 to 4
+    arguments on the device."""
+    lo_hi = NUM_FUNCTIONS.get(name.lower())
+    if lo_hi is None:
+        raise ValueError("num_fn takes one of %s, not %r" % (", ".join(sorted(NUM_FUNCTIONS)), name))
+    if not lo_hi[0] <= len(args) <= lo_hi[1]:
+        raise ValueError("%s takes %d to %d arguments, not %d" % (name, lo_hi[0], lo_hi[1], len(args)))
+    return "%s(%s)" % (name.lower(), ", ".join(args))
 
 
 def cond_fn(name: str, *args: str) -> str:
