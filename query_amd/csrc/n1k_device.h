@@ -246,8 +246,12 @@ N1K_DEV double pow10_go(int n) {
     for (int i = 0; i < a; i++) p *= 10.0;
     return n < 0 ? 1.0 / p : p;
 }
-// roundFloat (expression/func_num.go:1715-1736): half away from zero, except that an exact .5 goes to the even neighbour
+// roundFloat (expression/func_num.go:1715-1736): half away from zero, except that an exact .5 goes to the even neighbour.
+// Go on amd64 rounds x * pow and then the sum; the compiler's default contracts the two into one fused multiply-add, which
+// rounds once and gives another last digit (round(80548699656784.55, 2) is ...84.56, fused ...84.55): contraction is off
+// for this body, wherever it is inlined.
 N1K_DEV double round_float(double x, int prec) {
+#pragma clang fp contract(off)
     if (x != x || x == __longlong_as_double(0x7FF0000000000000ll) || x == __longlong_as_double((long long)0xFFF0000000000000ull)) return x;
     double sign = 1.0;
     if (x < 0) { sign = -1.0; x = -x; }
