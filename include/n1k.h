@@ -521,6 +521,40 @@ n1k_status n1k_coll_eval_device(int device, const char *predicate_text, size_t l
  * predicates of the plan, out[3] the number of new dictionary entries from which the device route is taken */
 n1k_status n1k_coll_stats(const n1k_handle *h, uint64_t out[4]);
 
+/* -------------------------------------------------------- array functions -- */
+
+/*
+ * array_length(a) (expression/func_array.go:888-897), array_count(a) (:376-393), array_sum(a) (:1911-1928, adding with
+ * value/integer.go:266-352), array_avg(a) (:141-164), array_contains(a, c) (:307-323) and array_position(a, c)
+ * (:1094-1110), with `a` a leaf path of the row and `c` a constant (NUMBER, STRING, TRUE, FALSE, null, missing), are
+ * values wherever a plan takes one.  Such a term is a function of the ARRAY alone, so it runs as one evaluation per
+ * DISTINCT array — one tag byte and one 8-byte payload per dictionary code and term, for the entries that are the
+ * canonical text of an array — and one lookup per row: MISSING for MISSING, NULL for anything but an ARRAY.  Elements
+ * are typed as the reference types them, value.NewValue over the decoded array (value/value.go:367-381,
+ * value/parsed.go:120-122, 362): every number is a float64 first.  At most 4 distinct terms per plan.  The two entry
+ * points below run the evaluators on their own (tests, diagnostics); n1k_arrfn_stats says which route built a handle's
+ * tables.
+ *
+ * n1k_arrfn_eval: the host evaluator, no GPU needed.  term_text is one whole term as expression/stringer.go writes it
+ * (array_contains((`d`.`tags`), "x")); the path is parsed and otherwise unused.  Entry i is the canonical JSON text
+ * bytes[offsets[i] - offsets[0], offsets[i + 1] - offsets[0]); out_tags[i] / out_payload[i] are the term's value for that
+ * array (N1K_T_*; INT: int64, FLOAT: float64 bits), N1K_T_NULL when the text is no array.  N1K_UNSUPPORTED for a term
+ * n1k_create refuses in a plan, N1K_INVALID for text that is no such term.
+ */
+n1k_status n1k_arrfn_eval(const char *term_text, size_t len, uint64_t n, const uint64_t *offsets, const char *bytes,
+                          uint8_t *out_tags, uint64_t *out_payload);
+/* The same through arrfn_table_kernel on `device`.  *out_left_to_host counts the arrays the kernel left to the host
+ * evaluator: text longer than 192 bytes; under array_sum, array_avg and array_contains / array_position with a NUMBER
+ * constant a number beyond the exact conversions (over 18 digits; over 15 digits or a decimal exponent beyond +-22 with
+ * a fraction) or an integer that float64 does not hold exactly; under array_contains / array_position with a STRING
+ * constant a STRING element with a backslash escape that is reached before a match.  array_length and array_count hand
+ * over nothing but the long texts.  The results are those of n1k_arrfn_eval. */
+n1k_status n1k_arrfn_eval_device(int device, const char *term_text, size_t len, uint64_t n, const uint64_t *offsets,
+                                 const char *bytes, uint8_t *out_tags, uint64_t *out_payload, uint64_t *out_left_to_host);
+/* out[0] arrays of the dictionary evaluated on the device so far, out[1] on the host, out[2] distinct array-function
+ * terms of the plan, out[3] the number of new dictionary entries from which the device route is taken */
+n1k_status n1k_arrfn_stats(const n1k_handle *h, uint64_t out[4]);
+
 /* --------------------------------------------------------------------- IN -- */
 
 /*

@@ -12,21 +12,28 @@
 namespace n1k {
 
 #define N1K_DEV __device__ __forceinline__
+// the few helpers the host flavour of an evaluator shares with its kernel (n1k_arrfn.h): the same code on both sides
+#define N1K_HDEV __host__ __device__ __forceinline__
 
 // type-order class of a tag (value/value.go:69-79):
 // MISSING 0, NULL 1, BOOLEAN 2, NUMBER 3, STRING 4, ARRAY 5, OBJECT 6
 N1K_DEV uint32_t cls_of(uint32_t tag) { return (uint32_t)((0x654332210ull >> (tag * 4u)) & 0xFu); }
 
+#if defined(__HIP_DEVICE_COMPILE__) || defined(__HIPCC_RTC__)
 N1K_DEV double as_f64(uint64_t bits) { return __longlong_as_double((long long)bits); }
 N1K_DEV uint64_t f64_bits(double d) { return (uint64_t)__double_as_longlong(d); }
+#else  // (the host pass of a kernel unit: the same bits without the device intrinsics)
+N1K_HDEV double as_f64(uint64_t bits) { return __builtin_bit_cast(double, bits); }
+N1K_HDEV uint64_t f64_bits(double d) { return __builtin_bit_cast(uint64_t, d); }
+#endif
 
 // Go float64 -> int64 on amd64 (cvttsd2si): out of range / NaN -> MinInt64
-N1K_DEV int64_t go_f2i(double f) {
+N1K_HDEV int64_t go_f2i(double f) {
     if (!(f >= -9223372036854775808.0 && f < 9223372036854775808.0)) return INT64_MIN;
     return (int64_t)f;
 }
 // value.IsInt (value/integer.go:354-356)
-N1K_DEV bool is_int_f64(double x) { return x == (double)go_f2i(x); }
+N1K_HDEV bool is_int_f64(double x) { return x == (double)go_f2i(x); }
 
 // monotone u64 image of a double; NaN -> 0 ("NaN sorts first", value/float.go:123-172)
 N1K_DEV uint64_t f64_sortable(double d) {
@@ -47,7 +54,7 @@ N1K_DEV int collate_f64(double t, double o) {
     return t < o ? -1 : (t > o ? 1 : 0);
 }
 
-N1K_DEV double num_actual(uint32_t tag, uint64_t p) { return tag == T_INT ? (double)(int64_t)p : as_f64(p); }
+N1K_HDEV double num_actual(uint32_t tag, uint64_t p) { return tag == T_INT ? (double)(int64_t)p : as_f64(p); }
 
 // result of X.Compare(Y): -1/0/1, or these two
 constexpr int CMP_NULL = 2, CMP_MISSING = 3;
@@ -185,12 +192,12 @@ struct Num {
     uint32_t tag;
     uint64_t p;
 };
-N1K_DEV Num num_int(int64_t v) { return Num{T_INT, (uint64_t)v}; }
-N1K_DEV Num num_flt(double v) { return Num{T_FLOAT, f64_bits(v)}; }
+N1K_HDEV Num num_int(int64_t v) { return Num{T_INT, (uint64_t)v}; }
+N1K_HDEV Num num_flt(double v) { return Num{T_FLOAT, f64_bits(v)}; }
 // value.NewValue(float64): integral values fold to int64 (value/value.go:377-382)
-N1K_DEV Num num_new_value(double d) { return is_int_f64(d) ? num_int(go_f2i(d)) : num_flt(d); }
+N1K_HDEV Num num_new_value(double d) { return is_int_f64(d) ? num_int(go_f2i(d)) : num_flt(d); }
 // intValue.Add keeps int64 only for same-sign operands without overflow (value/integer.go:266-277)
-N1K_DEV Num num_add(Num a, Num b) {
+N1K_HDEV Num num_add(Num a, Num b) {
     if (a.tag == T_INT && b.tag == T_INT) {
         int64_t x = (int64_t)a.p, y = (int64_t)b.p;
         int64_t rv = (int64_t)((uint64_t)x + (uint64_t)y);

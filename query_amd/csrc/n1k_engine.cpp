@@ -92,6 +92,39 @@ bool to_operand(n1k_handle* h, const Expr* e, Operand& o, PlanError& err) {
             err.msg = "'" + f + "' inside CASE or a conditional function does not run on the device";
             return false;
         }
+        if (arrfn_name(f)) {
+            // A function of the ARRAY alone whose result is a number, a boolean, NULL or MISSING (n1k_arrfn.h): one entry per
+            // dictionary code in the term's value table, one lookup per row into a derived column.
+            if (e->ch.size() == 2 && e->ch[1]->ctag == T_MISSING) {  // (MISSING whatever the first argument: func_array.go:308, 1095)
+                o.is_const = 1;
+                o.ctag = T_MISSING;
+                return true;
+            }
+            Operand a;
+            if (!to_operand(h, e->ch[0].get(), a, err)) return false;
+            const int ix = h->arrfn.add(e, err);
+            if (ix < 0) return false;
+            for (size_t d = 0; d < h->derived.size(); d++)  // the same term once more (a key and its HAVING, two conjuncts): its column
+                if (h->derived[d].op == AR_ARRFN && h->derived[d].node == (uint32_t)ix && h->derived[d].ops[0].col == a.col) {
+                    memset(&o, 0, sizeof o);
+                    o.col = (uint32_t)(h->plan.paths.size() + d);
+                    return true;
+                }
+            if (h->plan.paths.size() + h->derived.size() >= (size_t)kMaxCols) {
+                err.unsupported = true;
+                err.msg = "too many columns (inputs + arithmetic nodes > 16)";
+                return false;
+            }
+            n1k_handle::Derived d{};
+            d.op = AR_ARRFN;
+            d.nops = 1;
+            d.ops[0] = a;
+            d.node = (uint32_t)ix;
+            memset(&o, 0, sizeof o);
+            o.col = (uint32_t)(h->plan.paths.size() + h->derived.size());
+            h->derived.push_back(d);
+            return true;
+        }
         if (strfn_name(f)) {  // (its value is a new string per row, not a dictionary code: only a term's predicate is tabulated)
             err.unsupported = true;
             err.msg = "string function '" + f + "' used as a value (a group key, an aggregate's operand, an operand of arithmetic or of a comparison with a path): only a Filter / HAVING term over it runs on the device";
@@ -402,6 +435,7 @@ bool compile_plan(n1k_handle* h, PlanError& err) {
     h->cond_uploaded = false;
     h->const_strings.clear();
     h->match.clear_plan();
+    h->arrfn.clear_plan();
     const ParsedPlan& pl = h->plan;
     if (pl.paths.size() > (size_t)kMaxCols) { err.unsupported = true; err.msg = "more than 16 leaf paths"; return false; }
     if (pl.keys.size() > (size_t)kMaxKeys) { err.unsupported = true; err.msg = "more than 4 group keys"; return false; }

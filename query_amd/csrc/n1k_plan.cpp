@@ -440,6 +440,10 @@ struct EParser {
                         return bad(w + (num_if ? " takes at least 2 arguments" : num_unary ? " takes 1 argument" : " takes 2 arguments"));
                     return e;
                 }
+                // The scalar functions over arrays (expression/func_array.go; registry names func_registry.go): the six whose
+                // result is a number, a boolean, NULL or MISSING are a node over a leaf path of the row and, for the two binary
+                // ones, a constant (n1k_arrfn.h).  Every other array_* function is refused by its name.
+                if (w.compare(0, 6, "array_") == 0 && w != "array_agg" && lx.toks[p + 1].kind == TK::LParen) return array_fn(w);
                 // (with a seed it is Go's generator, without one it is no function of the row: func_num.go Random)
                 if (w == "random" && lx.toks[p + 1].kind == TK::LParen) return unsupported("function 'random'");
                 if (w == "case") return case_expr();
@@ -450,6 +454,31 @@ struct EParser {
             case TK::Other: return unsupported("token '" + t.text + "'");
             default: return bad("unexpected token at offset " + std::to_string(t.begin));
         }
+    }
+
+    // array_length(a) / array_count / array_sum / array_avg, array_contains(a, c) / array_position(a, c), the cursor on the
+    // name: `a` a leaf path of the row, `c` a constant — NUMBER, STRING, TRUE, FALSE, null or missing.  `text` is the whole
+    // term as the stringer wrote it: the plan's distinct terms are told apart by it.
+    std::unique_ptr<Expr> array_fn(const std::string& w) {
+        const bool unary = w == "array_length" || w == "array_count" || w == "array_sum" || w == "array_avg";
+        const bool binary = w == "array_contains" || w == "array_position";
+        if (!unary && !binary) {
+            const bool value = w == "array_min" || w == "array_max";
+            return unsupported("array function '" + w + "' (" + (value ? "its result can be a new string, not a number or a boolean" : "its result is not a number or a boolean") + ")");
+        }
+        const size_t begin = cur().begin;
+        const Tok& a0 = lx.toks[p + 2];
+        if (a0.kind == TK::LBrack) return unsupported(w + " over an array constructor (its first argument must be a leaf path)");
+        if (a0.kind == TK::Word && a0.text != "cover" && a0.text != "meta")
+            return unsupported(w + " over '" + a0.text + "' (a function, an aggregate or a comprehension, not a leaf path)");
+        auto e = call(w);
+        if (!e) return nullptr;
+        if (e->ch.size() != (unary ? 1u : 2u)) return bad(w + (unary ? " takes 1 argument" : " takes 2 arguments"));
+        if (e->ch[0]->kind != EK::Path) return unsupported(w + " over an expression that is not a leaf path (arithmetic, a constant, a function)");
+        if (binary && e->ch[1]->kind != EK::Const)
+            return unsupported(w + " whose second argument is not a constant (a path or an expression)");
+        e->text = src.substr(begin, lx.toks[p - 1].end - begin);
+        return e;
     }
 
     // stringer.go VisitSearchedCase / VisitSimpleCase (:115-154), no parentheses of its own:

@@ -32,7 +32,9 @@ enum class EK {
     Func  // numeric functions of one or two arguments (expression/func_num.go) and the string functions a term may hold
           // (expression/func_str.go; n1k_strfn.h), and the conditional functions ifmissing / ifnull / ifmissingornull / nullif /
           // missingif (expression/func_cond_unknown.go), the library functions acos ... power (func_num.go; pi() / e() / nan() /
-          // posinf() / neginf() parse to Const) and ifinf / ifnan / ifnanorinf / nanif / posinfif / neginfif (func_cond_num.go): fname
+          // posinf() / neginf() parse to Const) and ifinf / ifnan / ifnanorinf / nanif / posinfif / neginfif (func_cond_num.go), and
+          // array_length / array_count / array_sum / array_avg / array_contains / array_position over a leaf path (expression/
+          // func_array.go; n1k_arrfn.h; `text` is then the whole term as the stringer wrote it): fname
 };
 
 struct Expr {

@@ -527,8 +527,8 @@ n1k_status bind_columns(n1k_handle* h, const n1k_batch* b, bool defer) {
     return defer ? N1K_OK : materialize_derived(h, b);
 }
 
-// one element-wise launch per node — arith_kernel, or cond_kernel for a conditional node: the node's values as a TAGGED64
-// column in HBM
+// one element-wise launch per node — arith_kernel, cond_kernel for a conditional node, arrfn_lookup_kernel for an array
+// function: the node's values as a TAGGED64 column in HBM
 n1k_status materialize_derived(n1k_handle* h, const n1k_batch* b) {
     Program& P = h->prog;
     if (h->derived_ready) return N1K_OK;
@@ -539,6 +539,7 @@ n1k_status materialize_derived(n1k_handle* h, const n1k_batch* b) {
             if (rst != N1K_OK) return rst;
             break;
         }
+    ST_TRY(ensure_value_table(h));  // array functions: their value tables must cover this batch's dictionary
     if (!h->cond_nodes.empty() && !h->cond_uploaded) {  // once per plan: bind_columns has given the string constants their codes
         HIP_TRY(h, h->d_cond.ensure(h->cond_nodes.size()));
         HIP_TRY(h, hipMemcpy(h->d_cond.p, h->cond_nodes.data(), h->cond_nodes.size() * sizeof(CondNode), hipMemcpyHostToDevice));
@@ -571,6 +572,30 @@ n1k_status materialize_derived(n1k_handle* h, const n1k_batch* b) {
             d.kind = COLK_TAGGED64;
             d.tags = C.out_tags;
             d.payload = C.out_payload;
+            d.codes = nullptr;
+            continue;
+        }
+        if (h->derived[i].op == AR_ARRFN) {  // one lookup per row in the term's value table (n1k_arrfn.h)
+            const ArrFnTable& T = h->arrfn;
+            ArrFnLookupArgs L{};
+            L.col = P.cols[h->derived[i].ops[0].col];  // (a leaf path: an input column)
+            L.tab_tags = T.d_tags[h->derived[i].node].p;
+            L.tab_payload = T.d_payload[h->derived[i].node].p;
+            L.tab_n = (uint32_t)T.built_for;
+            L.nrows = b->nrows;
+            L.nrows_dev = h->push_nrows_dev;
+            if (h->push_nseg > 1) {
+                L.seg_counts = h->push_seg_counts;
+                L.seg_rows = h->push_seg_rows;
+                L.nseg = h->push_nseg;
+            }
+            L.out_tags = h->dv_tags[i].p;
+            L.out_payload = h->dv_payload[i].p;
+            HIP_TRY(h, launch_arrfn_lookup(L, h->stream));
+            DevCol& d = P.cols[ni + i];
+            d.kind = COLK_TAGGED64;
+            d.tags = L.out_tags;
+            d.payload = L.out_payload;
             d.codes = nullptr;
             continue;
         }

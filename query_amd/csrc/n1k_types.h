@@ -469,7 +469,11 @@ enum : uint32_t { AR_ADD = 0, AR_MULT, AR_SUB, AR_DIV, AR_MOD, AR_NEG, AR_IDIV, 
                   AR_ACOS, AR_ASIN, AR_ATAN, AR_COS, AR_SIN, AR_TAN, AR_EXP, AR_LN, AR_LOG, AR_DEGREES, AR_RADIANS, AR_ATAN2, AR_POWER,
                   // expression/func_cond_num.go: IFINF / IFNAN / IFNANORINF of 2 to 4 numbers, eager
                   AR_IFINF, AR_IFNAN, AR_IFNANORINF,
-                  AR_OP_COUNT };
+                  AR_OP_COUNT,
+                  // array_length / _count / _sum / _avg / _contains / _position of an ARRAY column (n1k_arrfn.h): one lookup per
+                  // row in the term's value table, arrfn_lookup_kernel (derived columns only).  Behind AR_OP_COUNT: no arith_apply
+                  // switch, fused or not, ever sees it.
+                  AR_ARRFN };
 // What an op needs, by name and not by its place in the enum.
 constexpr bool ar_is_mathfn(uint32_t op) {  // math_apply<OP> / mathfn_kernel<OP>
     return op == AR_ACOS || op == AR_ASIN || op == AR_ATAN || op == AR_COS || op == AR_SIN || op == AR_TAN || op == AR_EXP || op == AR_LN ||
