@@ -555,6 +555,56 @@ n1k_status n1k_arrfn_eval_device(int device, const char *term_text, size_t len, 
  * terms of the plan, out[3] the number of new dictionary entries from which the device route is taken */
 n1k_status n1k_arrfn_stats(const n1k_handle *h, uint64_t out[4]);
 
+/* --------------------------------------------------------- date functions -- */
+
+/*
+ * Five date functions (expression/func_date.go) are values wherever round(...) is one — operands of a Filter or HAVING
+ * comparison and of arithmetic, group keys, aggregate operands, projection terms over the groups:
+ *     date_part_millis(x, part [, "UTC"])   date_trunc_millis(x, part)   date_add_millis(x, n, part)
+ *         x (and n) any NUMBER-valued operand; evaluated per row, fusable into the run-time-built scan
+ *     str_to_millis(s)   date_part_str(s, part)
+ *         s a leaf path of the row; evaluated once per DISTINCT dictionary string into the term's value table (one tag byte
+ *         and one 8-byte payload per code), one lookup per row.  At most 4 distinct terms per plan.
+ * `part` is a STRING constant, lower-cased; datePart's names: millennium century decade year quarter month day hour minute
+ * second millisecond week day_of_year (doy) day_of_week (dow) iso_week iso_year iso_dow timezone timezone_hour
+ * timezone_minute; dateAdd's: millennium ... millisecond and week; dateTrunc's: the same without week.  Any other name, a
+ * part that is no constant and a third argument other than the constant "UTC" are N1K_UNSUPPORTED, the part named.
+ * A MISSING argument gives MISSING, otherwise a wrong type NULL, a non-integral n NULL.  A call of constants is a constant.
+ * time.Local is UTC on this path — the one divergence: a string without a zone is read as UTC, the timezone parts of a millis
+ * value are 0; a string that carries an offset keeps it.  Results are exact (integer and plain float64 arithmetic).
+ * Where the reference's answer would depend on wrapped or out-of-range arithmetic the ROW raises and the call that meets it
+ * answers N1K_UNSUPPORTED_DATA: a millis operand or a result outside years 1 to 9999 UTC (-62135596800000 ...
+ * 253402300799999), NaN or an infinity, |n| beyond 2^31, n * unit beyond int64 nanoseconds, and a date string whose
+ * reading depends on the reference's toolchain (a 1-digit hour, day 00, a zone hour over 23 or minute over 59, more than 9
+ * fraction digits, ',' for the fraction's '.').  Every other string that is no date of the 13 _DATE_FORMATS is NULL.
+ * Hence the five are N1K_UNSUPPORTED inside CASE and the conditional functions (an arm that is not taken is evaluated all
+ * the same), as are: every other date function (date_diff_*, date_add_str, date_trunc_str, millis_to_*, date_format_str,
+ * weekday_*, date_range_*, now_*, clock_*, str_to_utc / _zone_name / _tz / _duration, duration_to_str), a first argument of
+ * the string functions that is neither a leaf path nor a constant, and any of them inside SATISFIES.
+ *
+ * n1k_datefn_eval: the host evaluator, no GPU needed.  call_text is one whole call as expression/stringer.go writes it, its
+ * first argument a leaf path that stands for the value, the others constants (date_add_millis((`d`.`t`), 3, "month")).
+ * Value i is (in_tags[i], in_payload[i]) (N1K_T_*; INT: int64, FLOAT: float64 bits); where in_tags[i] is N1K_T_STRING the
+ * string is bytes[offsets[i] - offsets[0], offsets[i + 1] - offsets[0]) (offsets: n + 1; needed by the string functions
+ * only).  out_tags[i] / out_payload[i]: the call's value; out_raise[i] = 1 where a row holding the value raises (its value
+ * is then NULL).  N1K_UNSUPPORTED for a call n1k_create refuses in a plan, N1K_INVALID for text that is no such call.
+ */
+n1k_status n1k_datefn_eval(const char *call_text, size_t len, uint64_t n, const uint8_t *in_tags, const uint64_t *in_payload,
+                           const uint64_t *offsets, const char *bytes, uint8_t *out_tags, uint64_t *out_payload,
+                           uint8_t *out_raise);
+/* The same through the kernels on `device`: datefn_kernel for the millis functions — it has one flag for all rows, so
+ * out_raise stays 0 and *out_any_raise says whether some value raised —, datestr_table_kernel for the string functions,
+ * with out_raise per value; *out_left_to_host counts the strings of more than 64 bytes, which the kernel leaves to the host
+ * evaluator.  The results are those of n1k_datefn_eval. */
+n1k_status n1k_datefn_eval_device(int device, const char *call_text, size_t len, uint64_t n, const uint8_t *in_tags,
+                                  const uint64_t *in_payload, const uint64_t *offsets, const char *bytes, uint8_t *out_tags,
+                                  uint64_t *out_payload, uint8_t *out_raise, uint32_t *out_any_raise,
+                                  uint64_t *out_left_to_host);
+/* out[0] dictionary entries evaluated by datestr_table_kernel so far, out[1] by the host evaluator, out[2] distinct
+ * str_to_millis / date_part_str terms of the plan, out[3] the number of new dictionary entries from which the device route
+ * is taken */
+n1k_status n1k_datefn_stats(const n1k_handle *h, uint64_t out[4]);
+
 /* --------------------------------------------------------------------- IN -- */
 
 /*

@@ -91,6 +91,7 @@ SYMBOLS = [
     "n1k_in_match", "n1k_in_match_device", "n1k_in_stats",
     "n1k_strfn_eval", "n1k_strfn_eval_device", "n1k_strfn_stats",
     "n1k_arrfn_eval", "n1k_arrfn_eval_device", "n1k_arrfn_stats",
+    "n1k_datefn_eval", "n1k_datefn_eval_device", "n1k_datefn_stats",
     "n1k_device_bytes_live",
     "n1k_filter_device_batch", "n1k_selected_to_host32", "n1k_gather_selected", "n1k_order_key", "n1k_rowdistinct_stats",
 ]
@@ -268,6 +269,15 @@ def lib():
                                             C.POINTER(C.c_uint64)]
         L.n1k_arrfn_stats.restype = C.c_int
         L.n1k_arrfn_stats.argtypes = [H, C.POINTER(C.c_uint64 * 4)]
+    if hasattr(L, "n1k_datefn_eval"):  # (idem)
+        L.n1k_datefn_eval.restype = C.c_int
+        L.n1k_datefn_eval.argtypes = [C.c_char_p, C.c_size_t, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p]
+        L.n1k_datefn_eval_device.restype = C.c_int
+        L.n1k_datefn_eval_device.argtypes = [C.c_int, C.c_char_p, C.c_size_t, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
+        L.n1k_datefn_stats.restype = C.c_int
+        L.n1k_datefn_stats.argtypes = [H, C.POINTER(C.c_uint64 * 4)]
     if hasattr(L, "n1k_device_bytes_live"):  # (idem)
         L.n1k_device_bytes_live.restype = C.c_uint64
         L.n1k_device_bytes_live.argtypes = []

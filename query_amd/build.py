@@ -12,9 +12,9 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libn1k.so")
-SOURCES = ["n1k_kernels.hip", "n1k_bins.hip", "n1k_jsondev.hip", "n1k_matchtable.hip", "n1k_order.hip", "n1k_rowdistinct.hip", "n1k_mathfn.hip", "n1k_arrfn.hip", "n1k_order.cpp", "n1k_rowdistinct.cpp", "n1k_matchtable.cpp", "n1k_like.cpp", "n1k_coll.cpp", "n1k_arrfn.cpp", "n1k_in.cpp", "n1k_strfn.cpp", "n1k_jsonpush.cpp", "n1k_plan.cpp", "n1k_engine.cpp", "n1k_scan.cpp", "n1k_select.cpp", "n1k_partitioned.cpp", "n1k_distinct.cpp",
+SOURCES = ["n1k_kernels.hip", "n1k_bins.hip", "n1k_jsondev.hip", "n1k_matchtable.hip", "n1k_order.hip", "n1k_rowdistinct.hip", "n1k_mathfn.hip", "n1k_arrfn.hip", "n1k_datefn.hip", "n1k_order.cpp", "n1k_rowdistinct.cpp", "n1k_matchtable.cpp", "n1k_like.cpp", "n1k_coll.cpp", "n1k_arrfn.cpp", "n1k_datefn.cpp", "n1k_in.cpp", "n1k_strfn.cpp", "n1k_jsonpush.cpp", "n1k_plan.cpp", "n1k_engine.cpp", "n1k_scan.cpp", "n1k_select.cpp", "n1k_partitioned.cpp", "n1k_distinct.cpp",
            "n1k_finish.cpp", "n1k_tail.cpp", "n1k_exchange.cpp", "n1k_jit.cpp", "n1k_json.cpp"]
-HEADERS = ["n1k_types.h", "n1k_device.h", "n1k_tables.h", "n1k_fold.h", "n1k_scatter.h", "n1k_spec.h", "n1k_like.h", "n1k_coll.h", "n1k_arrfn.h", "n1k_cond.h", "n1k_in.h", "n1k_strfn.h", "n1k_order.h", "n1k_rowdistinct.h", "n1k_jit.h", "n1k_kernels.h", "n1k_plan.h", os.path.join("..", "..", "include", "n1k.h")]
+HEADERS = ["n1k_types.h", "n1k_device.h", "n1k_tables.h", "n1k_fold.h", "n1k_scatter.h", "n1k_spec.h", "n1k_like.h", "n1k_coll.h", "n1k_arrfn.h", "n1k_datefn.h", "n1k_cond.h", "n1k_in.h", "n1k_strfn.h", "n1k_order.h", "n1k_rowdistinct.h", "n1k_jit.h", "n1k_kernels.h", "n1k_plan.h", os.path.join("..", "..", "include", "n1k.h")]
 HOST_HEADERS = ["n1k_engine.h", "n1k_buf.h", "n1k_wire.h"]  # host-only: not part of source_hash()
 ARCH = "gfx950"
 

@@ -421,6 +421,227 @@ N1K_DEV void math_apply(uint32_t nops, const uint32_t (&tg)[4], const uint64_t (
     rp_out = rp;
 }
 
+// ---- Date functions over a millis NUMBER (expression/func_date.go): DATE_PART_MILLIS, DATE_TRUNC_MILLIS, DATE_ADD_MILLIS.
+// Integer calendar arithmetic and plain float64 operations only, host and device the same code.  time.Local is UTC here
+// ("Date functions").  A DateTime is Go's (Unix seconds, nanoseconds 0 .. 999999999); a "wall" time is the same
+// pair counted in the time's own zone, which for a millis value is UTC again.
+struct DateTime {
+    int64_t sec;
+    int32_t ns;
+};
+constexpr double kDateMinMillis = -62135596800000.0, kDateMaxMillis = 253402300799999.0;  // 0001-01-01T00:00:00Z .. 9999-12-31T23:59:59.999Z
+constexpr int64_t kDateMinSec = -62135596800ll, kDateMaxSec = 253402300799ll;
+constexpr int64_t kDateMinDay = -719162, kDateMaxDay = 2932896;  // the same two instants as days since 1970-01-01
+constexpr int64_t kDateYear0Sec = kDateMinSec - 366ll * 86400;   // 0000-01-01T00:00:00Z: where the times of date strings begin
+
+N1K_HDEV int64_t date_floor_div(int64_t a, int64_t b) {  // b > 0
+    const int64_t q = a / b;
+    return a % b < 0 ? q - 1 : q;
+}
+// days since 1970-01-01 of the proleptic Gregorian date y-m-d, m in 1 .. 12; linear in d, so a day outside the month
+// normalises as time.Date does
+N1K_HDEV int64_t days_from_civil(int64_t y, int64_t m, int64_t d) {
+    y -= m <= 2;
+    const int64_t era = date_floor_div(y, 400);
+    const int64_t yoe = y - era * 400;                                   // [0, 399]
+    const int64_t doy = (153 * (m > 2 ? m - 3 : m + 9) + 2) / 5 + d - 1;  // March 1 is day 0
+    const int64_t doe = yoe * 365 + yoe / 4 - yoe / 100 + doy;
+    return era * 146097 + doe - 719468;
+}
+N1K_HDEV void civil_from_days(int64_t z, int64_t& y, int32_t& m, int32_t& d) {
+    z += 719468;
+    const int64_t era = date_floor_div(z, 146097);
+    const int64_t doe = z - era * 146097;                                        // [0, 146096]
+    const int64_t yoe = (doe - doe / 1460 + doe / 36524 - doe / 146096) / 365;  // [0, 399]
+    const int64_t doy = doe - (365 * yoe + yoe / 4 - yoe / 100);                 // [0, 365]
+    const int64_t mp = (5 * doy + 2) / 153;                                      // [0, 11]
+    d = (int32_t)(doy - (153 * mp + 2) / 5 + 1);
+    m = (int32_t)(mp < 10 ? mp + 3 : mp - 9);
+    y = yoe + era * 400 + (m <= 2);
+}
+
+// millisToTime (func_date.go:2395-2397): time.Unix(int64(millis / 1000), int64(math.Mod(millis, 1000) * 1000000.0)) with
+// time.Unix's normalisation of the nanoseconds.  false: the operand, or — the quotient may round across a second — the
+// time, lies outside years 1 .. 9999, or is NaN / an infinity.
+N1K_HDEV bool date_millis_to_time(double m, DateTime& t) {
+    if (!(m >= kDateMinMillis && m <= kDateMaxMillis)) return false;
+    int64_t sec = (int64_t)(m / 1000.0);
+    int64_t nsec = (int64_t)(fmod(m, 1000.0) * 1000000.0);
+    if (nsec < 0 || nsec >= 1000000000ll) {
+        const int64_t n = nsec / 1000000000ll;
+        sec += n;
+        nsec -= n * 1000000000ll;
+        if (nsec < 0) {
+            nsec += 1000000000ll;
+            sec--;
+        }
+    }
+    t.sec = sec;
+    t.ns = (int32_t)nsec;
+    return sec >= kDateMinSec && sec <= kDateMaxSec;
+}
+// timeToMillis (:2403-2405): float64(t.Unix() * 1000) + float64(t.Round(time.Millisecond).Nanosecond()) / 1000000.  The
+// seconds are those of the unrounded time: a round-up that carries into the next second leaves nanosecond 0 and is lost.
+N1K_HDEV double date_time_to_millis(DateTime t) {
+    const int32_t r = t.ns % 1000000;
+    int32_t ns = r + r < 1000000 ? t.ns - r : t.ns + (1000000 - r);  // Time.Round: halfway values round up
+    if (ns >= 1000000000) ns -= 1000000000;
+    return (double)(t.sec * 1000) + (double)ns / 1000000.0;
+}
+
+// datePart (:2440-2498) of the wall time `wall` (seconds counted in the time's own zone) whose zone lies `zone` seconds
+// east of UTC.
+N1K_HDEV int64_t date_part(int64_t wall, int32_t ns, int32_t zone, uint32_t part) {
+    const int64_t days = date_floor_div(wall, 86400);
+    const int32_t sod = (int32_t)(wall - days * 86400);
+    if (part == DP_HOUR) return sod / 3600;
+    if (part == DP_MINUTE) return sod / 60 % 60;
+    if (part == DP_SECOND) return sod % 60;
+    if (part == DP_MILLISECOND) return ns / 1000000;
+    if (part == DP_TIMEZONE) return zone;
+    if (part == DP_TIMEZONE_HOUR) return zone / 3600;
+    if (part == DP_TIMEZONE_MINUTE) return (zone - zone / 3600 * 3600) / 60;
+    const int32_t wd = (int32_t)(days - date_floor_div(days + 4, 7) * 7 + 4);  // Time.Weekday: Sunday = 0 (1970-01-01 was a Thursday)
+    if (part == DP_DOW) return wd;
+    if (part == DP_ISO_DOW) return wd == 0 ? 7 : wd;
+    int64_t at = days;
+    if (part == DP_ISO_WEEK || part == DP_ISO_YEAR) at = days - (wd + 6) % 7 + 3;  // Time.ISOWeek: the Thursday of the same Monday-based week
+    int64_t y;
+    int32_t m, d;
+    civil_from_days(at, y, m, d);
+    const int32_t yday = (int32_t)(at - days_from_civil(y, 1, 1)) + 1;
+    switch (part) {
+        case DP_MILLENNIUM: return y / 1000 + 1;
+        case DP_CENTURY: return y / 100 + 1;
+        case DP_DECADE: return y / 10;
+        case DP_YEAR: case DP_ISO_YEAR: return y;
+        case DP_QUARTER: return (m + 2) / 3;
+        case DP_MONTH: return m;
+        case DP_DAY: return d;
+        case DP_WEEK: return (yday + 6) / 7;  // int(math.Ceil(float64(t.YearDay()) / 7.0))
+        case DP_ISO_WEEK: return (yday - 1) / 7 + 1;
+        default: return yday;  // DP_DOY
+    }
+}
+
+// dateTrunc (:2541-2605) in UTC.  Day and below are Time.Truncate, which counts from the zero time, 0001-01-01T00:00:00Z: a
+// day boundary, so for times from year 1 on it is the floor of the Unix seconds.  Month and above: the first day of the
+// month / quarter / year / decade / century / millennium (monthTrunc, yearTrunc, AddDate).  false: year 0 (a decade,
+// century or millennium that begins before year 1).
+N1K_HDEV bool date_trunc(DateTime& t, uint32_t part) {
+    if (part == DP_MILLISECOND) {
+        t.ns -= t.ns % 1000000;
+        return true;
+    }
+    t.ns = 0;
+    if (part == DP_SECOND) return true;
+    if (part == DP_MINUTE || part == DP_HOUR || part == DP_DAY) {
+        const int64_t unit = part == DP_MINUTE ? 60 : (part == DP_HOUR ? 3600 : 86400);
+        t.sec = date_floor_div(t.sec, unit) * unit;
+        return true;
+    }
+    int64_t y;
+    int32_t m, d;
+    civil_from_days(date_floor_div(t.sec, 86400), y, m, d);
+    if (part == DP_QUARTER) m -= (m - 1) % 3;
+    else if (part != DP_MONTH) m = 1;
+    if (part == DP_DECADE) y -= y % 10;
+    else if (part == DP_CENTURY) y -= y % 100;
+    else if (part == DP_MILLENNIUM) y -= y % 1000;
+    if (y < 1) return false;
+    t.sec = days_from_civil(y, m, 1) * 86400;
+    return true;
+}
+
+// dateAdd (:2504-2535), |n| <= 2^31.  Millennium .. day: Time.AddDate, i.e. time.Date(year + y, month + m, day + d, ...) with
+// its normalisation — the months carry into the year, the days are counted on from the first of that month (Jan 31 + 1
+// month is March 2 or 3).  Hour .. millisecond: Time.Add(time.Duration(n) * unit).  false: the product overflows int64
+// nanoseconds, or the result lies outside years 1 .. 9999.
+N1K_HDEV bool date_add(DateTime& t, int64_t n, uint32_t part) {
+    if (part >= DP_HOUR) {
+        const int64_t unit = part == DP_HOUR ? 3600000000000ll : (part == DP_MINUTE ? 60000000000ll : (part == DP_SECOND ? 1000000000ll : 1000000ll));
+        const int64_t most = part == DP_HOUR ? INT64_MAX / 3600000000000ll : (part == DP_MINUTE ? INT64_MAX / 60000000000ll : (int64_t)1 << 31);
+        if (n > most || n < -most) return false;  // (2^31 seconds or milliseconds fit)
+        const int64_t dur = n * unit;
+        int64_t dsec = dur / 1000000000ll;
+        int32_t ns = t.ns + (int32_t)(dur % 1000000000ll);
+        if (ns >= 1000000000) {
+            dsec++;
+            ns -= 1000000000;
+        } else if (ns < 0) {
+            dsec--;
+            ns += 1000000000;
+        }
+        t.sec += dsec;
+        t.ns = ns;
+        return t.sec >= kDateMinSec && t.sec <= kDateMaxSec;
+    }
+    const int64_t days = date_floor_div(t.sec, 86400);
+    const int64_t sod = t.sec - days * 86400;
+    int64_t y;
+    int32_t m, d;
+    civil_from_days(days, y, m, d);
+    int64_t mon = m - 1, add_days = 0;
+    switch (part) {
+        case DP_MILLENNIUM: y += n * 1000; break;
+        case DP_CENTURY: y += n * 100; break;
+        case DP_DECADE: y += n * 10; break;
+        case DP_YEAR: y += n; break;
+        case DP_QUARTER: mon += n * 3; break;
+        case DP_MONTH: mon += n; break;
+        case DP_WEEK: add_days = n * 7; break;
+        default: add_days = n; break;  // DP_DAY
+    }
+    const int64_t carry = date_floor_div(mon, 12);
+    y += carry;
+    mon -= carry * 12;
+    const int64_t nd = days_from_civil(y, mon + 1, 1) + (d - 1) + add_days;
+    if (nd < kDateMinDay || nd > kDateMaxDay) return false;
+    t.sec = nd * 86400 + sod;
+    return true;
+}
+
+// One call over a row's operands: tg / pv hold the millis operand, then (DATE_ADD) n, then the part as an INT constant.
+// The argument tests are the reference's (DatePartMillis.Apply :726-772, DateTruncMillis.Apply :1213-1231,
+// DateAddMillis.Apply :376-395): a MISSING argument gives MISSING, otherwise a non-number NULL, a non-integral n NULL.
+// Returns true when the row must raise ERR_UNSUPPORTED_VALUE — Go's answer would depend on wrapped or out-of-range
+// arithmetic: the millis or the result outside years 1 .. 9999 UTC, NaN / an infinity, |n| > 2^31, n * unit beyond int64.
+template <uint32_t OP>
+N1K_HDEV bool date_apply(const uint32_t (&tg)[4], const uint64_t (&pv)[4], uint32_t& rt_out, uint64_t& rp_out) {
+    static_assert(ar_is_datefn(OP), "date_apply: not a date function");
+    auto is_num = [](uint32_t t) { return t == T_INT || t == T_FLOAT; };
+    constexpr bool add = OP == AR_DATE_ADD;
+    rt_out = T_NULL;
+    rp_out = 0;
+    if (tg[0] == T_MISSING || (add && tg[1] == T_MISSING)) {
+        rt_out = T_MISSING;
+        return false;
+    }
+    if (!is_num(tg[0]) || (add && !is_num(tg[1]))) return false;
+    double na = 0.0;
+    if constexpr (add) {
+        na = num_actual(tg[1], pv[1]);
+        if (na != trunc(na)) return false;  // NULL (NaN too)
+    }
+    const uint32_t part = (uint32_t)pv[add ? 2 : 1];
+    DateTime t;
+    if (!date_millis_to_time(num_actual(tg[0], pv[0]), t)) return true;
+    if constexpr (OP == AR_DATE_PART) {
+        rt_out = T_INT;
+        rp_out = (uint64_t)date_part(t.sec, t.ns, 0, part);
+        return false;
+    } else {
+        if constexpr (add) {
+            if (!(na >= -2147483648.0 && na <= 2147483648.0)) return true;
+            if (!date_add(t, (int64_t)na, part)) return true;
+        } else if (!date_trunc(t, part)) return true;
+        const Num n = num_new_value(date_time_to_millis(t));
+        rt_out = n.tag;
+        rp_out = n.p;
+        return false;
+    }
+}
+
 N1K_DEV uint64_t mix64(uint64_t x) {
     x ^= x >> 33;
     x *= 0xff51afd7ed558ccdull;

@@ -55,6 +55,123 @@ static uint32_t mathfn_op(const std::string& f) {
     return AR_OP_COUNT;
 }
 
+// date_part_millis / date_trunc_millis / date_add_millis -> one Derived node: the millis operand, (ADD) n, the part as an INT
+// constant.  A call of constants only is a constant.
+static bool date_operand(n1k_handle* h, const Expr* e, uint32_t op, Operand& o, PlanError& err) {
+    const std::string& f = e->fname;
+    if (h->cond_depth) {
+        // (they can raise ERR_UNSUPPORTED_VALUE, and the operand of an arm that is not taken is evaluated all the same)
+        err.unsupported = true;
+        err.msg = "'" + f + "' inside CASE or a conditional function does not run on the device";
+        return false;
+    }
+    uint32_t part;
+    if (!datefn_part(e, part, err)) return false;
+    if (part == DP_COUNT) {  // (a MISSING part: MISSING whatever the other arguments)
+        o.is_const = 1;
+        o.ctag = T_MISSING;
+        return true;
+    }
+    n1k_handle::Derived d{};
+    d.op = op;
+    bool all_const = true;
+    for (size_t k = 0; k < (op == AR_DATE_ADD ? 2u : 1u); k++) {
+        Operand x;
+        if (!to_operand(h, e->ch[k].get(), x, err)) return false;
+        all_const = all_const && x.is_const;
+        d.ops[d.nops++] = x;
+    }
+    Operand& pc = d.ops[d.nops++];
+    pc.is_const = 1;
+    pc.ctag = T_INT;
+    pc.cpayload = part;
+    memset(&o, 0, sizeof o);
+    if (all_const) {
+        uint32_t tg[4] = {T_MISSING, T_MISSING, T_MISSING, T_MISSING}, rt;
+        uint64_t pv[4] = {0, 0, 0, 0}, rp;
+        for (uint32_t k = 0; k < d.nops; k++) {
+            tg[k] = d.ops[k].ctag;
+            pv[k] = d.ops[k].cpayload;
+        }
+        if (datefn_eval_host(op, tg, pv, rt, rp)) {
+            err.unsupported = true;
+            err.msg = f + " over constants: the millis, the result or n is outside what the device computes exactly (years 1 to 9999 UTC, |n| <= 2^31)";
+            return false;
+        }
+        o.is_const = 1;
+        o.ctag = rt;
+        o.cpayload = rp;
+        return true;
+    }
+    if (h->plan.paths.size() + h->derived.size() >= (size_t)kMaxCols) {
+        err.unsupported = true;
+        err.msg = "too many columns (inputs + arithmetic nodes > 16)";
+        return false;
+    }
+    o.col = (uint32_t)(h->plan.paths.size() + h->derived.size());
+    h->derived.push_back(d);
+    return true;
+}
+
+// str_to_millis(s) / date_part_str(s, part) over a leaf path -> one AR_DATESTR node naming its term (n1k_datefn.h): one entry
+// per dictionary code in the term's value table, one lookup per row into a derived column.  Over a constant: a constant.
+static bool datestr_operand(n1k_handle* h, const Expr* e, Operand& o, PlanError& err) {
+    const std::string& f = e->fname;
+    if (h->cond_depth) {
+        // (a row that reads an UNSURE entry raises ERR_UNSUPPORTED_VALUE, and the operand of an arm that is not taken is evaluated all the same)
+        err.unsupported = true;
+        err.msg = "'" + f + "' inside CASE or a conditional function does not run on the device";
+        return false;
+    }
+    const Expr* a0 = e->ch[0].get();
+    if (a0->kind == EK::Const) {
+        DateStrProg g;
+        bool missing;
+        if (!datestr_compile(e, g, missing, err)) return false;
+        o.is_const = 1;
+        o.ctag = missing || a0->ctag == T_MISSING ? T_MISSING : T_NULL;
+        if (!missing && a0->ctag == T_STRING) {
+            const uint64_t off[2] = {0, a0->cstr.size()};
+            uint8_t tg = T_NULL;
+            datestr_eval_block_host(&g, 1, 1, off, (const uint8_t*)a0->cstr.data(), &tg, &o.cpayload, 1);
+            if (tg == DS_UNSURE) {
+                err.unsupported = true;
+                err.msg = f + " over the constant \"" + a0->cstr + "\": a date string whose reading depends on the reference's toolchain (a 1-digit hour, day 00, a zone beyond 23:59, over 9 fraction digits or a ',')";
+                return false;
+            }
+            o.ctag = tg;
+        }
+        return true;
+    }
+    Operand a;
+    if (!to_operand(h, a0, a, err)) return false;
+    const int ix = h->datestr.add(e, err);
+    if (ix == -1) return false;
+    if (ix == -2) {  // (a MISSING part: MISSING whatever the string)
+        o.is_const = 1;
+        o.ctag = T_MISSING;
+        return true;
+    }
+    for (size_t d = 0; d < h->derived.size(); d++)  // the same term once more (a key and its HAVING, two conjuncts): its column
+        if (h->derived[d].op == AR_DATESTR && h->derived[d].node == (uint32_t)ix && h->derived[d].ops[0].col == a.col) {
+            o.col = (uint32_t)(h->plan.paths.size() + d);
+            return true;
+        }
+    if (h->plan.paths.size() + h->derived.size() >= (size_t)kMaxCols) {
+        err.unsupported = true;
+        err.msg = "too many columns (inputs + arithmetic nodes > 16)";
+        return false;
+    }
+    n1k_handle::Derived d{};
+    d.op = AR_DATESTR;
+    d.nops = 1;
+    d.ops[0] = a;
+    d.node = (uint32_t)ix;
+    o.col = (uint32_t)(h->plan.paths.size() + h->derived.size());
+    h->derived.push_back(d);
+    return true;
+}
+
 bool to_operand(n1k_handle* h, const Expr* e, Operand& o, PlanError& err) {
     memset(&o, 0, sizeof o);
     if (e->kind == EK::Path) {
@@ -125,6 +242,8 @@ bool to_operand(n1k_handle* h, const Expr* e, Operand& o, PlanError& err) {
             h->derived.push_back(d);
             return true;
         }
+        if (datefn_op(f) != AR_OP_COUNT) return date_operand(h, e, datefn_op(f), o, err);
+        if (datestr_name(f)) return datestr_operand(h, e, o, err);
         if (strfn_name(f)) {  // (its value is a new string per row, not a dictionary code: only a term's predicate is tabulated)
             err.unsupported = true;
             err.msg = "string function '" + f + "' used as a value (a group key, an aggregate's operand, an operand of arithmetic or of a comparison with a path): only a Filter / HAVING term over it runs on the device";
@@ -436,6 +555,7 @@ bool compile_plan(n1k_handle* h, PlanError& err) {
     h->const_strings.clear();
     h->match.clear_plan();
     h->arrfn.clear_plan();
+    h->datestr.clear_plan();
     const ParsedPlan& pl = h->plan;
     if (pl.paths.size() > (size_t)kMaxCols) { err.unsupported = true; err.msg = "more than 16 leaf paths"; return false; }
     if (pl.keys.size() > (size_t)kMaxKeys) { err.unsupported = true; err.msg = "more than 4 group keys"; return false; }

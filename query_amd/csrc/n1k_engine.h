@@ -28,6 +28,7 @@
 #include "n1k_json.h"
 #include "n1k_kernels.h"
 #include "n1k_arrfn.h"
+#include "n1k_datefn.h"
 #include "n1k_coll.h"
 #include "n1k_cond.h"
 #include "n1k_in.h"
@@ -113,6 +114,27 @@ struct ArrFnTable {
     } scratch;
     uint64_t dev = 0, host = 0;  // array entries evaluated by the kernel / by the host evaluator (n1k_arrfn_stats)
     int add(const Expr* e, PlanError& err);  // find the term by its text or compile and append it; the index, or -1 and err
+    void clear_plan() {
+        terms.clear();
+        built_for = 0;
+    }
+};
+
+// str_to_millis / date_part_str: their value tables ("Date functions"; n1k_datefn.h), ArrFnTable's sibling with
+// STRING as the expected tag and the same life cycle: built before the first launch that needs them, EXTENDED when the
+// dictionary has grown (ensure_datestr_table), kept across n1k_reset, freed with the handle.
+struct DateStrTable {
+    std::vector<DateStrTerm> terms;  // distinct by their stringer text: equal text shares one table
+    DevBuf<uint8_t> d_tags[kDateStrMaxTerms];
+    DevBuf<uint64_t> d_payload[kDateStrMaxTerms];
+    size_t built_for = 0;  // dictionary codes the tables cover
+    struct {               // device scratch of the device route, kept from one extension to the next
+        DevBuf<uint8_t> bytes, left, tags;
+        DevBuf<uint64_t> off, payload;
+    } scratch;
+    uint64_t dev = 0, host = 0;  // entries evaluated by the kernel / by the host evaluator (n1k_datefn_stats)
+    // find the term by its text or compile and append it; the index, -1 and err, or -2: the part is the constant MISSING
+    int add(const Expr* e, PlanError& err);
     void clear_plan() {
         terms.clear();
         built_for = 0;
@@ -310,6 +332,8 @@ n1k_status push_json_device(n1k_handle* h, uint64_t ndocs, const uint64_t* offse
 n1k_status ensure_match_table(n1k_handle* h);
 // n1k_arrfn.cpp: the value tables of the array-function terms, built and extended before the lookups that read them
 n1k_status ensure_value_table(n1k_handle* h);
+// n1k_datefn.cpp: the value tables of the str_to_millis / date_part_str terms, likewise
+n1k_status ensure_datestr_table(n1k_handle* h);
 
 // ---- n1k_scan.cpp: one batch through Filter + InitialGroup (kernel choice), Filter-only batches, staging of host batches
 // Staging for host batches (n1k_scan.cpp alone).
@@ -545,6 +569,7 @@ struct n1k_handle {
 
     MatchTable match;  // LIKE, ANY / EVERY, IN, string functions: the plan's predicates over dictionary entries and their table
     ArrFnTable arrfn;  // array_length ... array_position: the plan's terms over dictionary entries and their value tables
+    DateStrTable datestr;  // str_to_millis / date_part_str: the plan's terms over dictionary strings and their value tables
 
     // compiled program (column pointers are patched per batch)
     Program prog{};
@@ -554,7 +579,7 @@ struct n1k_handle {
     bool has_distinct = false, has_minmax = false, has_array_agg = false;
     uint32_t n_distinct = 0;
     // arithmetic operands -> derived columns (input columns first, then one per arithmetic node)
-    struct Derived { uint32_t op, nops; Operand ops[4]; uint32_t node; };  // node: op AR_COND, the node's index in cond_nodes; op AR_ARRFN, the term's in arrfn.terms
+    struct Derived { uint32_t op, nops; Operand ops[4]; uint32_t node; };  // node: op AR_COND, the node's index in cond_nodes; op AR_ARRFN, the term's in arrfn.terms; op AR_DATESTR, the term's in datestr.terms
     std::vector<Derived> derived;
     // CASE and the conditional functions (n1k_cond.h): the nodes' programs, in device memory once their string constants have
     // their codes (materialize_derived) and until the plan is compiled again

@@ -289,17 +289,18 @@ const JitKernel* jit_get(const SpecSig& sig) {
         } else
             cache_write(cpath, code);
     }
-    // A fused library function (math_apply<OP>, n1k_device.h) brings a double-precision routine into a 512-thread scan: a
+    // A fused library function (math_apply<OP>, n1k_device.h) brings a double-precision routine into a 512-thread scan, a
+    // fused date function (date_apply<OP>) its 64-bit calendar arithmetic: a
     // shape whose registers then spill to scratch memory is not used — choose_scan takes the materialised route, as for a
     // shape that does not compile.
-    bool mathfn = false;
-    for (uint32_t d = 0; d < sig.nderived; d++) mathfn = mathfn || ar_is_mathfn(sig.derived[d].op);
-    if (!k->failed && mathfn) {
+    bool heavy = false;  // a library or a date function among the fused nodes
+    for (uint32_t d = 0; d < sig.nderived; d++) heavy = heavy || ar_is_mathfn(sig.derived[d].op) || ar_is_datefn(sig.derived[d].op);
+    if (!k->failed && heavy) {
         for (hipFunction_t f : {k->wide, k->narrow, k->rec_wide, k->rec_narrow, k->part_wide, k->part_wide256, k->part_narrow}) {
             int scratch = 0;
             if (f && hipFuncGetAttribute(&scratch, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, f) == hipSuccess && scratch > 0) {
                 k->failed = true;
-                k->log = "a fused library function spills " + std::to_string(scratch) + " B per lane to scratch memory: the nodes are materialised instead";
+                k->log = "a fused library or date function spills " + std::to_string(scratch) + " B per lane to scratch memory: the nodes are materialised instead";
                 break;
             }
         }

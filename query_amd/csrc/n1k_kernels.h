@@ -97,6 +97,7 @@ hipError_t launch_merge_partials(const Program& P, const GlobalTable& G, uint32_
                                  uint64_t limit = 0, bool unique_keys = false);
 hipError_t launch_arith(const ArithArgs& A, hipStream_t st);
 hipError_t launch_mathfn(const ArithArgs& A, hipStream_t st);  // ar_is_mathfn(A.op): mathfn_kernel<A.op>, the same arguments and layout
+hipError_t launch_datefn(const ArithArgs& A, hipStream_t st);  // ar_is_datefn(A.op): datefn_kernel<A.op> (n1k_datefn.hip); rows outside the batch are skipped
 hipError_t launch_cond(const Program& P, const CondArgs& C, hipStream_t st);  // one conditional node (n1k_cond.h) over P's columns
 hipError_t launch_publish_counters(const unsigned long long* src, unsigned long long* dst, uint32_t n, hipStream_t st);
 hipError_t launch_partition(const Program& P, const PartArgs& A, uint32_t grid, hipStream_t st);

@@ -446,6 +446,39 @@ struct EParser {
                 if (w.compare(0, 6, "array_") == 0 && w != "array_agg" && lx.toks[p + 1].kind == TK::LParen) return array_fn(w);
                 // (with a seed it is Go's generator, without one it is no function of the row: func_num.go Random)
                 if (w == "random" && lx.toks[p + 1].kind == TK::LParen) return unsupported("function 'random'");
+                // The date functions (expression/func_date.go; registry names func_registry.go:106-140).  Three over a millis
+                // NUMBER are nodes (to_operand); every other one is refused by its name.
+                if (lx.toks[p + 1].kind == TK::LParen) {
+                    const bool date3 = w == "date_add_millis", date2 = w == "date_trunc_millis", date23 = w == "date_part_millis";
+                    if (date3 || date2 || date23) {
+                        auto e = call(w);
+                        if (!e) return nullptr;
+                        const size_t lo = date3 ? 3 : 2, hi = date2 ? 2 : 3;
+                        if (e->ch.size() < lo || e->ch.size() > hi) return bad(w + " takes " + std::to_string(lo) + (hi > lo ? " or 3" : "") + " arguments");
+                        return e;
+                    }
+                    // str_to_millis(s) and date_part_str(s, part) over a leaf path: one value per dictionary string
+                    // (n1k_datefn.h); `text` is the whole term as the stringer wrote it, which tells the plan's terms apart
+                    if (w == "str_to_millis" || w == "date_part_str") {
+                        const size_t begin = cur().begin;
+                        auto e = call(w);
+                        if (!e) return nullptr;
+                        const size_t want = w == "str_to_millis" ? 1 : 2;
+                        if (e->ch.size() != want) return bad(w + (want == 1 ? " takes 1 argument" : " takes 2 arguments"));
+                        if (e->ch[0]->kind != EK::Path && e->ch[0]->kind != EK::Const)  // (a constant folds at create)
+                            return unsupported(w + " over an expression that is not a leaf path (arithmetic, a function)");
+                        e->text = src.substr(begin, lx.toks[p - 1].end - begin);
+                        return e;
+                    }
+                    // (the registry's other date functions, func_registry.go:106-140)
+                    static const char* const other_dates[] = {
+                        "clock_local", "clock_millis", "clock_str", "clock_tz", "clock_utc", "date_add_str", "date_diff_millis", "date_diff_str",
+                        "date_format_str", "date_range_millis", "date_range_str", "date_trunc_str", "duration_to_str", "millis", "millis_to_local",
+                        "millis_to_str", "millis_to_tz", "millis_to_utc", "millis_to_zone_name", "now_local", "now_millis", "now_str", "now_tz",
+                        "now_utc", "str_to_duration", "str_to_tz", "str_to_utc", "str_to_zone_name", "weekday_millis", "weekday_str"};
+                    for (const char* name : other_dates)
+                        if (w == name) return unsupported("date function '" + w + "'");
+                }
                 if (w == "case") return case_expr();
                 if ((w == "any" || w == "every") && lx.toks[p + 1].kind != TK::LParen) return collection();
                 return unsupported("function or keyword '" + w + "'");

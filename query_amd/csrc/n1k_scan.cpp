@@ -540,6 +540,7 @@ n1k_status materialize_derived(n1k_handle* h, const n1k_batch* b) {
             break;
         }
     ST_TRY(ensure_value_table(h));  // array functions: their value tables must cover this batch's dictionary
+    ST_TRY(ensure_datestr_table(h));  // str_to_millis / date_part_str: likewise
     if (!h->cond_nodes.empty() && !h->cond_uploaded) {  // once per plan: bind_columns has given the string constants their codes
         HIP_TRY(h, h->d_cond.ensure(h->cond_nodes.size()));
         HIP_TRY(h, hipMemcpy(h->d_cond.p, h->cond_nodes.data(), h->cond_nodes.size() * sizeof(CondNode), hipMemcpyHostToDevice));
@@ -599,6 +600,31 @@ n1k_status materialize_derived(n1k_handle* h, const n1k_batch* b) {
             d.codes = nullptr;
             continue;
         }
+        if (h->derived[i].op == AR_DATESTR) {  // one lookup per row in the term's value table (n1k_datefn.h)
+            const DateStrTable& T = h->datestr;
+            DateStrLookupArgs L{};
+            L.col = P.cols[h->derived[i].ops[0].col];  // (a leaf path: an input column)
+            L.tab_tags = T.d_tags[h->derived[i].node].p;
+            L.tab_payload = T.d_payload[h->derived[i].node].p;
+            L.tab_n = (uint32_t)T.built_for;
+            L.nrows = b->nrows;
+            L.nrows_dev = h->push_nrows_dev;
+            if (h->push_nseg > 1) {
+                L.seg_counts = h->push_seg_counts;
+                L.seg_rows = h->push_seg_rows;
+                L.nseg = h->push_nseg;
+            }
+            L.out_tags = h->dv_tags[i].p;
+            L.out_payload = h->dv_payload[i].p;
+            L.err_flags = h->groups.errp;
+            HIP_TRY(h, launch_datestr_lookup(L, h->stream));
+            DevCol& d = P.cols[ni + i];
+            d.kind = COLK_TAGGED64;
+            d.tags = L.out_tags;
+            d.payload = L.out_payload;
+            d.codes = nullptr;
+            continue;
+        }
         ArithArgs A{};
         A.op = h->derived[i].op;
         A.nops = h->derived[i].nops;
@@ -609,8 +635,16 @@ n1k_status materialize_derived(n1k_handle* h, const n1k_batch* b) {
         A.out_payload = h->dv_payload[i].p;
         A.str_rank = h->d_rank.p;
         A.err_flags = h->groups.errp;
-        // (a library function has a kernel of its own, which carries that routine alone)
-        HIP_TRY(h, ar_is_mathfn(A.op) ? launch_mathfn(A, h->stream) : launch_arith(A, h->stream));
+        if (ar_is_datefn(A.op)) {  // (it can raise: the rows a received region does not hold are skipped, as cond_kernel skips them)
+            A.nrows_dev = h->push_nrows_dev;
+            if (h->push_nseg > 1) {
+                A.seg_counts = h->push_seg_counts;
+                A.seg_rows = h->push_seg_rows;
+                A.nseg = h->push_nseg;
+            }
+        }
+        // (a library or date function has a kernel of its own, which carries that routine alone)
+        HIP_TRY(h, ar_is_datefn(A.op) ? launch_datefn(A, h->stream) : ar_is_mathfn(A.op) ? launch_mathfn(A, h->stream) : launch_arith(A, h->stream));
         DevCol& d = P.cols[ni + i];
         d.kind = COLK_TAGGED64;
         d.tags = A.out_tags;

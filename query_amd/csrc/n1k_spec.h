@@ -372,24 +372,38 @@ N1K_DEV void spec_tile_arrived(uint32_t (&tt)[R][kFastCols], uint64_t (&pv)[R][W
 
 // Fused node D of the shape: arith_apply with its op a constant, or — a library function — math_apply<op>, so that the
 // shape carries the routines its own nodes name and no other (the loop below is unrolled: d is a constant there).
+// A date function (date_apply<op>) is the one kind of fused node that can raise: true when the row must set
+// ERR_UNSUPPORTED_VALUE — if the batch holds that row, which the caller of spec_decode_tile knows.
 template <class Spec, int D>
-N1K_DEV void spec_derived_apply(const uint32_t (&ot)[4], const uint64_t (&op)[4], uint32_t& rt, uint64_t& rp) {
+N1K_DEV bool spec_derived_apply(const uint32_t (&ot)[4], const uint64_t (&op)[4], uint32_t& rt, uint64_t& rp) {
     if constexpr (D < Spec::nderived) {
-        if constexpr (ar_is_mathfn(Spec::derived[D].op)) math_apply<Spec::derived[D].op>(Spec::derived[D].nops, ot, op, rt, rp);
+        if constexpr (ar_is_datefn(Spec::derived[D].op)) return date_apply<Spec::derived[D].op>(ot, op, rt, rp);
+        else if constexpr (ar_is_mathfn(Spec::derived[D].op)) math_apply<Spec::derived[D].op>(Spec::derived[D].nops, ot, op, rt, rp);
         else arith_apply(Spec::derived[D].op, Spec::derived[D].nops, ot, op, rt, rp);
     } else {
         rt = T_MISSING;
         rp = 0;
     }
+    return false;
+}
+template <class Spec>
+constexpr bool spec_can_raise() {
+    for (int d = 0; d < Spec::nderived; d++)
+        if (ar_is_datefn(Spec::derived[d].op)) return true;
+    return false;
 }
 
 // Decode: the rows' tags from what spec_issue_tile loaded, and the fused arithmetic nodes (expression/arith_*.go,
 // func_num.go): column slot ncols + d from the slots before it, in registers — no derived column in HBM (the element-wise
 // arith_kernel writes 9 B per row and node and the scan reads them back).
+// Returns the rows of the tile on which a fused date function raised, bit j * rows-per-item + h for item j's row h (0 for
+// a shape without one): the caller sets ERR_UNSUPPORTED_VALUE for those of them the batch holds (spec_raise).
 template <class Spec, int R, bool WIDE>
-N1K_DEV void spec_decode_tile(const FastArgs& F, const uint32_t (&tt)[R][kFastCols], uint64_t (&pv)[R][WIDE ? 2 : 1][kSpecCols],
-                              uint32_t (&tg)[R][WIDE ? 2 : 1][kSpecCols]) {
+N1K_DEV uint32_t spec_decode_tile(const FastArgs& F, const uint32_t (&tt)[R][kFastCols], uint64_t (&pv)[R][WIDE ? 2 : 1][kSpecCols],
+                                  uint32_t (&tg)[R][WIDE ? 2 : 1][kSpecCols]) {
     constexpr uint32_t kRowsPerItem = WIDE ? 2u : 1u;
+    static_assert(R * (int)kRowsPerItem <= 32, "one bit per row of the tile");
+    uint32_t raised = 0;
 #pragma unroll
     for (int j = 0; j < R; j++) {
 #pragma unroll
@@ -428,13 +442,24 @@ N1K_DEV void spec_decode_tile(const FastArgs& F, const uint32_t (&tt)[R][kFastCo
                 uint32_t rt;
                 uint64_t rp;
                 static_assert(kFastDerived == 3, "spec_derived_apply is instantiated per node index");
-                if (d == 0) spec_derived_apply<Spec, 0>(ot, op, rt, rp);
-                else if (d == 1) spec_derived_apply<Spec, 1>(ot, op, rt, rp);
-                else spec_derived_apply<Spec, 2>(ot, op, rt, rp);
+                bool up;
+                if (d == 0) up = spec_derived_apply<Spec, 0>(ot, op, rt, rp);
+                else if (d == 1) up = spec_derived_apply<Spec, 1>(ot, op, rt, rp);
+                else up = spec_derived_apply<Spec, 2>(ot, op, rt, rp);
+                if (up) raised |= 1u << (j * (int)kRowsPerItem + h);
                 tg[j][h][Spec::ncols + d] = rt;
                 pv[j][h][Spec::ncols + d] = rp;
             }
         }
+    }
+    return raised;
+}
+// Row `at` of the tile is one the batch holds: report what a fused date function raised on it.  A shape without a date
+// function compiles to nothing.
+template <class Spec>
+N1K_DEV void spec_raise(const FastArgs& F, uint32_t raised, int at) {
+    if constexpr (spec_can_raise<Spec>()) {
+        if ((raised >> at) & 1u) atomicOr(F.err_flags, (uint32_t)ERR_UNSUPPORTED_VALUE);
     }
 }
 
@@ -535,7 +560,7 @@ N1K_DEV void scan_spec_records_body(const Program& P, const FastArgs& F, const W
                        uint32_t base) {
         spec_tile_arrived<Spec, R, WIDE>(tt, pv);
         uint32_t tg[R][kRowsPerItem][kSpecCols];
-        spec_decode_tile<Spec, R, WIDE>(F, tt, pv, tg);
+        const uint32_t raised = spec_decode_tile<Spec, R, WIDE>(F, tt, pv, tg);
         Rec16 recs[kNW];
         uint32_t bins[kNW];
 #pragma unroll
@@ -547,6 +572,7 @@ N1K_DEV void scan_spec_records_body(const Program& P, const FastArgs& F, const W
                 recs[at].v = 0;
                 bins[at] = kScatterNone;
                 const bool row_ok = valid[j] && (!WIDE || h == 0 || 2u * (base + (uint32_t)j * BLOCK + tid) + 1u < nrows);
+                if (row_ok) spec_raise<Spec>(F, raised, at);
                 if (row_ok) spec_row_record<Spec>(P, F, tg[j][h], pv[j][h], selected, unpackable, recs[at], bins[at], K);
             }
         }
@@ -673,7 +699,7 @@ N1K_DEV void scan_spec_partition_body(const Program& P, const FastArgs& F, const
         __builtin_amdgcn_sched_barrier(0);  // (nothing of the decode moves up between the loads of a tile issued just before)
         if (piped) spec_tile_arrived<Spec, R, WIDE>(tt, pv);  // (another tile in flight: wait for this one here, with a count)
         uint32_t tg[R][kRowsPerItem][kSpecCols];
-        spec_decode_tile<Spec, R, WIDE>(F, tt, pv, tg);
+        const uint32_t raised = spec_decode_tile<Spec, R, WIDE>(F, tt, pv, tg);
         bool pass[kNW];
         uint32_t dest[kNW], rk[kNW];
 #pragma unroll
@@ -682,6 +708,7 @@ N1K_DEV void scan_spec_partition_body(const Program& P, const FastArgs& F, const
             for (int h = 0; h < (int)kRowsPerItem; h++) {
                 const int at = j * (int)kRowsPerItem + h;
                 bool ok = valid[j] && (!WIDE || h == 0 || 2u * (base + (uint32_t)j * BLOCK + tid) + 1u < nrows);
+                if (ok) spec_raise<Spec>(F, raised, at);
 #pragma unroll
                 for (int t = 0; t < Spec::nterms; t++) ok = ok && spec_term_true<Spec>(t, F, K, tg[j][h][Spec::terms[t].col], pv[j][h][Spec::terms[t].col]);
                 // the destination is a function of the key VALUES (the same function as partition_kernel's)
@@ -897,7 +924,7 @@ N1K_DEV void scan_spec_body(const Program& P, const FastArgs& F, const GlobalTab
         // (another tile in flight: wait for this one here, with a count; else the compiler's own waits, item by item, do better)
         if (piped) spec_tile_arrived<Spec, R, WIDE>(tt, pv);
         uint32_t tg[R][kRowsPerItem][kSpecCols];
-        spec_decode_tile<Spec, R, WIDE>(F, tt, pv, tg);
+        const uint32_t raised = spec_decode_tile<Spec, R, WIDE>(F, tt, pv, tg);
         uint64_t mw[kSpecDistinct][kNW];  // this thread's member words of the tile (kEmptyKey = none) and their hash regions
         uint32_t mb[kSpecDistinct][kNW];
 #pragma unroll
@@ -909,6 +936,7 @@ N1K_DEV void scan_spec_body(const Program& P, const FastArgs& F, const GlobalTab
 #pragma unroll
                 for (int d = 0; d < (int)kSpecDistinct; d++) { words[d] = kEmptyKey; bins[d] = kScatterNone; }
                 const bool row_ok = valid[j] && (!WIDE || h == 0 || 2u * (base + (uint32_t)j * BLOCK + tid) + 1u < nr);
+                if (row_ok) spec_raise<Spec>(F, raised, j * (int)kRowsPerItem + h);
                 if (row_ok) spec_row<Spec>(P, F, G, ngroups, lds, S, &lds_fill, tg[j][h], pv[j][h], selected, unpackable, L, dcache, words, bins, K);
 #pragma unroll
                 for (int d = 0; d < (int)kSpecDistinct; d++) { mw[d][j * (int)kRowsPerItem + h] = words[d]; mb[d][j * (int)kRowsPerItem + h] = bins[d]; }

@@ -245,8 +245,9 @@ n1k_status project_groups(n1k_handle* h, uint64_t ng) {
                 const n1k_value& v = source(c, g);
                 tags[c][g] = v.tag;
                 pay[c][g] = v.v.code;  // (strings keep this operator's codes: arithmetic over a non-number is NULL anyway)
-                // ... but an array function reads the array's text through the INNER operator's dictionary, as HAVING's terms do
-                if (!f->arrfn.terms.empty() && v.tag >= N1K_T_STRING && (size_t)v.v.code < h->dict.size()) pay[c][g] = intern(f, h->dict[(size_t)v.v.code]);
+                // ... but an array function, and str_to_millis / date_part_str, read the entry's text through the INNER operator's
+                // dictionary, as HAVING's terms do
+                if ((!f->arrfn.terms.empty() || !f->datestr.terms.empty()) && v.tag >= N1K_T_STRING && (size_t)v.v.code < h->dict.size()) pay[c][g] = intern(f, h->dict[(size_t)v.v.code]);
             }
         std::vector<n1k_col> cols(nc ? nc : 1);
         for (size_t c = 0; c < nc; c++) {

@@ -469,11 +469,17 @@ enum : uint32_t { AR_ADD = 0, AR_MULT, AR_SUB, AR_DIV, AR_MOD, AR_NEG, AR_IDIV, 
                   AR_ACOS, AR_ASIN, AR_ATAN, AR_COS, AR_SIN, AR_TAN, AR_EXP, AR_LN, AR_LOG, AR_DEGREES, AR_RADIANS, AR_ATAN2, AR_POWER,
                   // expression/func_cond_num.go: IFINF / IFNAN / IFNANORINF of 2 to 4 numbers, eager
                   AR_IFINF, AR_IFNAN, AR_IFNANORINF,
+                  // expression/func_date.go over a millis NUMBER: date_apply<OP> (n1k_device.h), one datefn_kernel<OP> each
+                  // (n1k_datefn.hip) — never arith_apply's run-time switch.  Operands: the millis, (ADD) n, the part (DP_*) as an INT
+                  // constant.  They can raise ERR_UNSUPPORTED_VALUE.
+                  AR_DATE_PART, AR_DATE_TRUNC, AR_DATE_ADD,
                   AR_OP_COUNT,
                   // array_length / _count / _sum / _avg / _contains / _position of an ARRAY column (n1k_arrfn.h): one lookup per
                   // row in the term's value table, arrfn_lookup_kernel (derived columns only).  Behind AR_OP_COUNT: no arith_apply
                   // switch, fused or not, ever sees it.
-                  AR_ARRFN };
+                  AR_ARRFN,
+                  // str_to_millis / date_part_str of a dictionary string (n1k_datefn.h): likewise, datestr_lookup_kernel
+                  AR_DATESTR };
 // What an op needs, by name and not by its place in the enum.
 constexpr bool ar_is_mathfn(uint32_t op) {  // math_apply<OP> / mathfn_kernel<OP>
     return op == AR_ACOS || op == AR_ASIN || op == AR_ATAN || op == AR_COS || op == AR_SIN || op == AR_TAN || op == AR_EXP || op == AR_LN ||
@@ -482,9 +488,16 @@ constexpr bool ar_is_mathfn(uint32_t op) {  // math_apply<OP> / mathfn_kernel<OP
 }
 constexpr bool ar_is_mathfn2(uint32_t op) { return op == AR_ATAN2 || op == AR_POWER; }
 constexpr bool ar_is_ifnum(uint32_t op) { return op == AR_IFINF || op == AR_IFNAN || op == AR_IFNANORINF; }
+constexpr bool ar_is_datefn(uint32_t op) { return op == AR_DATE_PART || op == AR_DATE_TRUNC || op == AR_DATE_ADD; }  // date_apply<OP> / datefn_kernel<OP>
 constexpr bool ar_is_collating(uint32_t op) { return op == AR_GREATEST || op == AR_LEAST; }       // by value.Collate: the string ranks
 constexpr bool ar_needs_rank(uint32_t op) { return ar_is_collating(op) || op == AR_COND; }        // (a WHEN may order strings)
 constexpr bool ar_fuses(uint32_t op) { return !ar_needs_rank(op) && op < AR_OP_COUNT; }           // evaluable in the scan's registers
+// The date parts (expression/func_date.go), numbered as the engine passes them in a constant operand.  DATE_ADD takes DP_MILLENNIUM .. DP_MILLISECOND,
+// DATE_TRUNC the same without DP_WEEK, DATE_PART all of them (datePart / dateAdd / dateTrunc, :2440-2605).
+enum : uint32_t { DP_MILLENNIUM = 0, DP_CENTURY, DP_DECADE, DP_YEAR, DP_QUARTER, DP_MONTH, DP_WEEK, DP_DAY, DP_HOUR, DP_MINUTE, DP_SECOND,
+                  DP_MILLISECOND, DP_DOY, DP_DOW, DP_ISO_WEEK, DP_ISO_YEAR, DP_ISO_DOW, DP_TIMEZONE, DP_TIMEZONE_HOUR, DP_TIMEZONE_MINUTE,
+                  DP_COUNT };
+
 struct ArithArgs {
     uint32_t op, nops;
     Operand ops[4];
@@ -494,6 +507,12 @@ struct ArithArgs {
     uint64_t* out_payload;
     const uint32_t* str_rank;  // AR_GREATEST / AR_LEAST: bytewise rank of every dictionary string
     uint32_t* err_flags;       // ... and where ordering two arrays / objects is reported
+    // datefn_kernel only (a row the batch does not hold must not raise): the rows a region received from another GPU really
+    // holds, as CondArgs has them — min(nrows, *nrows_dev) rows, or nseg > 1 segments of seg_rows rows capacity with their
+    // counts kCursorStride words apart
+    const unsigned long long* nrows_dev;
+    const unsigned long long* seg_counts;
+    uint32_t seg_rows, nseg;
 };
 
 constexpr uint32_t kMaxParts = 64;  // destinations of one partition launch (ranks of a node, with room)

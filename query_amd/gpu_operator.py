@@ -409,6 +409,14 @@ class GpuFilterGroup:
         self._check(self._lib.n1k_arrfn_stats(self._h, C.byref(out)))
         return {"device_arrays": int(out[0]), "host_arrays": int(out[1]), "terms": int(out[2]), "device_threshold": int(out[3])}
 
+    def datefn_stats(self) -> dict:
+        """How the value tables of this operator's str_to_millis / date_part_str terms were built: dictionary strings
+        evaluated on the device / on the host, distinct terms of the plan, and the number of new dictionary entries from which
+        the device route is taken.  (date_part_millis / date_trunc_millis / date_add_millis keep no table: one value per row.)"""
+        out = (C.c_uint64 * 4)()
+        self._check(self._lib.n1k_datefn_stats(self._h, C.byref(out)))
+        return {"device_strings": int(out[0]), "host_strings": int(out[1]), "terms": int(out[2]), "device_threshold": int(out[3])}
+
     def rowdistinct_stats(self) -> dict:
         """The last DISTINCT over rows of this operator: survivors of the Filter, distinct rows before the cut, slots of the
         table of ordinals, and the rows that reached it (all, unless rowdistinct_lds_slots is set)."""

@@ -75,6 +75,31 @@ def num_fn(name: str, *args: str) -> str:
     return "%s(%s)" % (name.lower(), ", ".join(args))
 
 
+# expression/func_registry.go:111-135 -> (least, most) arguments: the date functions the device evaluates
+DATE_FUNCTIONS = {"date_part_millis": (2, 3), "date_trunc_millis": (2, 2), "date_add_millis": (3, 3), "str_to_millis": (1, 1), "date_part_str": (2, 2)}
+DATE_PARTS = ("millennium", "century", "decade", "year", "quarter", "month", "week", "day", "hour", "minute", "second", "millisecond",
+              "day_of_year", "doy", "day_of_week", "dow", "iso_week", "iso_year", "iso_dow", "timezone", "timezone_hour", "timezone_minute")
+
+
+def date_fn(name: str, *args: str) -> str:
+    """Stringer text of a date function (VisitFunction): date_fn("date_trunc_millis", "(`d`.`ts`)", '"day"') ->
+    date_trunc_millis((`d`.`ts`), "day").  The arguments are expression text already; the part is a STRING constant
+    (date_part("day") writes one), date_part_millis's optional third argument the constant "UTC"."""
+    lo_hi = DATE_FUNCTIONS.get(name.lower())
+    if lo_hi is None:
+        raise ValueError("date_fn takes one of %s, not %r" % (", ".join(sorted(DATE_FUNCTIONS)), name))
+    if not lo_hi[0] <= len(args) <= lo_hi[1]:
+        raise ValueError("%s takes %d to %d arguments, not %d" % (name, lo_hi[0], lo_hi[1], len(args)))
+    return "%s(%s)" % (name.lower(), ", ".join(args))
+
+
+def date_part(part: str) -> str:
+    """A date part as the STRING constant a date function takes: date_part("iso_week") -> "iso_week" (quoted)."""
+    if part.lower() not in DATE_PARTS:
+        raise ValueError("date part %r: one of %s" % (part, ", ".join(DATE_PARTS)))
+    return json.dumps(part)
+
+
 def cond_fn(name: str, *args: str) -> str:
     """Stringer text of a conditional function (VisitFunction): cond_fn("ifmissing", "(`d`.`x`)", "0") -> ifmissing((`d`.`x`), 0)."""
     if name.lower() not in COND_FUNCTIONS:
