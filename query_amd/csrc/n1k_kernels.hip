@@ -2435,7 +2435,12 @@ __global__ __launch_bounds__(BLOCK) void agg_bins_kernel(const Program P, const 
     const uint32_t S = A.lds_slots, tid = threadIdx.x;
     uint32_t new_groups = 0;
     const Rec16* const rec16 = (const Rec16*)A.rec;
-    for (uint32_t bin = blockIdx.x; bin < A.nbins; bin += gridDim.x) {
+    // A bin goes in segments of 2^23 records, each through an LDS table of its own: acc_lds adds ints below 2^40 into one
+    // wrapping 64-bit word per slot, and nothing else bounds the records of one key in a bin.  A later segment's groups repeat
+    // keys of an earlier one, which the region says as it does for rows that leave on their own (emit_singletons).
+    constexpr uint64_t kBinSegment = 1ull << 23;
+    uint64_t scanned = 0;  // records of `bin` that earlier turns of the loop took
+    for (uint32_t bin = blockIdx.x, next = 0; bin < A.nbins; bin = next) {
         uint64_t lo, hi;
         if (rec16) {
             const uint64_t c = A.bin_count[(size_t)bin * (A.bin_count_stride ? A.bin_count_stride : 1u)];
@@ -2445,7 +2450,18 @@ __global__ __launch_bounds__(BLOCK) void agg_bins_kernel(const Program P, const 
             lo = A.bin_start[bin];
             hi = A.bin_start[bin + 1];
         }
+        const bool first_segment = scanned == 0;
+        lo += scanned;
+        if (hi - lo > kBinSegment) {
+            hi = lo + kBinSegment;
+            scanned += kBinSegment;
+            next = bin;
+        } else {
+            scanned = 0;
+            next = bin + gridDim.x;
+        }
         if (lo == hi) continue;
+        if (!first_segment && A.emit && tid == 0) atomicAdd(A.emit_singletons, 1ull);
         __syncthreads();
         lds_table_init<BLOCK>(P, lds, S, tid);
         if (tid == 0) lds_fill = 0;

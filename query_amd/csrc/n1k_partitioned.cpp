@@ -240,7 +240,10 @@ n1k_status run_group_records(n1k_handle* h, const n1k_batch* b, const PartitionP
     // six deviations and an eighth (a quarter) on top.  Whatever overflows raises a flag and the batch takes the exact path.
     const double rows_per_group = std::min<double>((double)n, 2.0 * (double)n / (double)std::max<uint64_t>(groups, 1) + 1.0);
     const uint64_t mean = n / nbins + 1;
-    const uint64_t bin_cap = mean + mean / 8 + (uint64_t)(6.0 * std::sqrt((double)mean * (rows_per_group + 1.0))) + 64;
+    if (mean > (1ull << 23)) return N1K_OK;  // every bin would overflow its 2^23 records (below): the exact path at once
+    // (never more than 2^23 records: one workgroup adds a bin's ints below 2^40 into one wrapping 64-bit LDS word, and a
+    //  bin that would hold more overflows like any other and sends the batch to the exact path)
+    const uint64_t bin_cap = std::min<uint64_t>(1ull << 23, mean + mean / 8 + (uint64_t)(6.0 * std::sqrt((double)mean * (rows_per_group + 1.0))) + 64);
     const uint64_t nsub = 256ull * kRecSubs, sub_mean = n / nsub + 1;
     const uint64_t cap = sub_mean + sub_mean / 4 + (uint64_t)(6.0 * std::sqrt((double)sub_mean * (rows_per_group + 1.0))) + 256;
     HIP_TRY(h, h->part.rregion.ensure(2 * nsub * cap));

@@ -291,6 +291,15 @@ static ScanChoice choose_scan(n1k_handle* h, uint64_t nrows) {
     return c;
 }
 
+// Every LDS accumulator keeps an int SUM / AVG as ONE wrapping 64-bit word per slot and takes |x| < 2^40 into it (acc_lds,
+// acc_lds_value, spec_acc): a workgroup whose share of a launch is at most 2^23 rows cannot wrap that word, whatever the
+// rows hold.  Workgroup b takes the tiles b, b + grid, b + 2 grid, ...: the smallest grid that keeps its
+// ceil(tiles / grid) tiles within 2^23 rows.  It overrides grid_blocks; the default grids are above it up to 2^31 rows.
+static uint32_t min_grid_for_narrow_sums(uint64_t tiles, uint64_t tile_rows) {
+    const uint64_t per_workgroup = std::max<uint64_t>(1, (1ull << 23) / tile_rows);
+    return (uint32_t)((tiles + per_workgroup - 1) / per_workgroup);
+}
+
 // Rows [off, off + n) of the bound columns through the chosen kernel on program P: slabs for the grid, the launch, the
 // merge — or, slabs_to_rows, none: the slabs stay for n1k_finish.
 // A specialised kernel takes its WIDE form (2 adjacent rows per lane and load) over the even prefix of aligned
@@ -313,7 +322,10 @@ static n1k_status launch_chunk(n1k_handle* h, const ScanChoice& c, const Program
     const uint32_t rpl = !c.kernel ? h->opt.rows_per_lane : (wide ? 2 : 4);
     uint64_t tiles = (items + (uint64_t)c.fblock * rpl - 1) / ((uint64_t)c.fblock * rpl);
     if (c.ndist) tiles = (tiles + 3) / 4;  // a workgroup reserves chunks in every hash region: give it a few tiles to fill them
-    const uint32_t g = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(c.grid_cap, tiles));
+    const uint64_t tile_rows = (uint64_t)c.fblock * rpl * (wide ? 2u : 1u) * (c.ndist ? 4u : 1u);
+    // (a segmented batch numbers its tiles segment by segment: up to one partial tile more per segment)
+    const uint64_t share_tiles = tiles + (h->push_nseg > 1 ? h->push_nseg : 0u);
+    const uint32_t g = (uint32_t)std::max<uint64_t>(std::max<uint32_t>(1, min_grid_for_narrow_sums(share_tiles, tile_rows)), std::min<uint64_t>(c.grid_cap, tiles));
     if (c.use_slabs && g > 1) {  // (F.slabs is null here: build_fast_args, and below)
         HIP_TRY(h, h->groups.slabs.ensure((size_t)g * P.lds_words * F.lds_slots));
         HIP_TRY(h, h->groups.block_sel.ensure(g));
@@ -382,7 +394,7 @@ static n1k_status run_interpreter(n1k_handle* h, const ScanChoice& c, ScanArgs& 
     uint64_t ntiles = (nrows + tile_rows - 1) / tile_rows;
     uint32_t per_cu = c.block == 1024 ? 1 : (c.block == 512 ? 2 : 4);
     uint32_t grid = h->opt.grid_blocks ? h->opt.grid_blocks : (uint32_t)(h->num_cus * per_cu);
-    grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(grid, ntiles));
+    grid = (uint32_t)std::max<uint64_t>(std::max<uint32_t>(1, min_grid_for_narrow_sums(ntiles, tile_rows)), std::min<uint64_t>(grid, ntiles));
     hipEvent_t e0 = get_event(h), e1 = get_event(h);
     if (e0) (void)hipEventRecord(e0, h->stream);
     if (h->push_nseg > 1) {
@@ -395,7 +407,7 @@ static n1k_status run_interpreter(n1k_handle* h, const ScanChoice& c, ScanArgs& 
             As.nrows = h->push_seg_rows;
             As.nrows_dev = h->push_seg_counts + (size_t)sg * kCursorStride;
             const uint64_t nt = (h->push_seg_rows + tile_rows - 1) / tile_rows;
-            const uint32_t g = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(grid, nt));
+            const uint32_t g = (uint32_t)std::max<uint64_t>(std::max<uint32_t>(1, min_grid_for_narrow_sums(nt, tile_rows)), std::min<uint64_t>(grid, nt));
             HIP_TRY(h, launch_scan_group(Ps, As, h->groups.table, h->groups.counters.p + CTR_GROUPS, g, c.block, c.rpl, c.direct, h->stream));
         }
     } else
